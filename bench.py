@@ -24,15 +24,22 @@ GPU, RCCL over 127.0.0.1); under `python -m torch.distributed.run` the ranks are
 Trunk arithmetic (round 6): batches of more than 32 boards run the 128 -> 128 trunk convolutions on the fp16 matrix pipe
 with every fp32 operand split into two fp16 terms and fp32 accumulation (csrc/trunk15_wino3h.h, `--trunk-arith f16x2`, the
 default "auto"): <= 1e-4 on the logits against the float64 oracle like the exact kernel, different low-order bits.
-`--trunk-arith f32` runs the exact-fp32 kernel; the default line carries its rate as `value_exact_f32`.
+`--trunk-arith f32` runs the exact-fp32 kernel; the `--full` line carries its rate as `value_exact_f32`.
 
-`value` is COUNTED inside this run when the `counted` leg succeeds (default command, N = 1: a child process plays with
-continuous refill until every slot has finished a game, then counts finished games over 60 s); `value_derived` keeps the
-rate derived from the timed region.
+A plain run does only what the headline figure needs: set up, pre-warm, W warm-up steps, K timed steps, the outputs
+(`--dump-outputs DIR`) and the JSON line; its `value` is derived from the timed region.  `roofline` (dominant kernel =
+trunk 3x3 conv; `frac` = EXECUTED MFMA flops / time / peak of the pipe it runs on) comes from HIP events inside the
+timed region and stays on every line.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = trunk 3x3 conv; `frac` = EXECUTED MFMA flops / time / peak
-of the pipe it runs on), `roofline_stem` (north_star's HBM target shape 8192x4x15x15 and the real C_in=9 stem),
-`cpu_baseline` (sequential CPU oracle port, bounded sample).
+`--full` (N = 1) adds the measurements that take runs of their own: `roofline_stem` (north_star's HBM target shape
+8192x4x15x15 and the real C_in=9 stem), `latency`, the other trunk arithmetic, `train_step`, `config2`, `cpu_baseline`
+(sequential CPU oracle port, bounded sample), `exchange`, and the `counted` leg: a child process plays with continuous
+refill until every slot has finished a game, then counts finished games over 60 s; `value` is then COUNTED and
+`value_derived` keeps the rate derived from the timed region.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (the evaluator's answers to the leaves of
+that step, rows ordered by game slot, and every game's root visit counts after it) as float32 .npy files.  The inputs
+are seeded: the same arguments give the same games.
 """
 import argparse
 import json
@@ -427,6 +434,25 @@ def config2_child(timeout_s=120.0, trunk_arith="auto"):
         return {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
 
 
+def dump_outputs(out_dir, batches, root_visits):
+    """`--dump-outputs`: the evaluator's answers to the leaves of the last timed step (batches of (slot ids, probs, values),
+    rows put in slot order) and every game's root visit counts after that step, as float32 DIR/<name>.npy (1.8 MB at
+    1024 games).  -> {name: shape}"""
+    ids = np.concatenate([b[0] for b in batches]).astype(np.int64)
+    order = np.argsort(ids, kind="stable")
+    arrays = {"leaf_slots": ids[order],
+              "leaf_probs": np.concatenate([b[1] for b in batches])[order],
+              "leaf_values": np.concatenate([np.reshape(b[2], -1) for b in batches])[order],
+              "root_visits": root_visits}
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def _rank_log_dir(tag=None):
     """gpurun_out/ (travels back from the GPU box), one sub-directory per self-spawned job: two bench runs on one host
     must not truncate each other's rank logs, and the supervisor's silence watchdog sums the sizes of its OWN ranks' logs.
@@ -629,7 +655,14 @@ def main():
                     help="count finished games over a steady-state window of this many seconds (continuous refill; the "
                          "window opens once every slot has finished a game or after --count-warmup-max seconds)")
     ap.add_argument("--count-warmup-max", type=float, default=420.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline_stem, latency, trunk_exact_f32, train_step, config2, cpu_baseline and the counted leg")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the line's own measurement also run roofline_stem, latency, trunk_exact_f32, train_step, "
+                         "config2, cpu_baseline, the exchange probe and the counted leg (minutes); off: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the evaluator outputs of the last timed step and the root visit counts after it to DIR/*.npy "
+                         "(N > 1: rank 0's games)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline_stem, latency, trunk_exact_f32, train_step, "
+                                                             "config2, cpu_baseline and the counted leg")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)   # child of cpu_baseline()
     ap.add_argument("--exchange-probe", type=int, default=0, metavar="ROWS", help=argparse.SUPPRESS)   # child of exchange_probe_world1()
     ap.add_argument("--config2-worker", action="store_true", help=argparse.SUPPRESS)                   # child of config2_child()
@@ -865,6 +898,16 @@ def main():
     p0, l0 = playouts_done(), eng.stats["leaf_evals"]
     host0, eval0 = eng.timers["host_s"], eng.timers["eval_s"]
     eng.step_times = []
+    last_step = {"round": -1, "batches": []}
+    if args.dump_outputs:
+        def keep_last_round(ids, codes, probs, values):
+            # collected while round k + 1 runs = dispatched by round k; the batches collected after the last round (the
+            # final drain of run_steps) are the evaluations the last timed step dispatched
+            k = len(eng.step_times)
+            if k != last_step["round"]:
+                last_step["round"], last_step["batches"] = k, []
+            last_step["batches"].append((ids, probs, values))
+        eng.tap = keep_last_round
     dist.barrier()
     for ln in lanes:
         ln.set_profiling(prof_stride)                # stream synchronize (== torch.cuda.synchronize() for the engine stream) + counters reset
@@ -1000,6 +1043,12 @@ def main():
                                      "direct-convolution minimum 158 MB, see there)" % traffic_src,
                      "us_per_launch": trunk_avg_ms * 1e3, "launches": trunk_cnt, "boards_per_launch": batch},
     }
+    if args.dump_outputs:
+        eng.tap = None
+        if last_step["round"] != args.steps:
+            raise SystemExit("bench.py: no evaluation of the last timed step was collected")
+        line["outputs"] = dump_outputs(args.dump_outputs, last_step["batches"],
+                                       eng.pool.root_visits_dense(np.arange(G, dtype=np.int32))[0])
     eng.close()
     for ln in lanes:
         ln.close()
@@ -1026,7 +1075,7 @@ def main():
                     pass
         line["cpu_baseline"] = dict(prev or {}, note="timed on rank 0 of the N = 1 run only (the host cores are busy feeding N GPUs "
                                     "here); this is the committed N = 1 measurement, not part of this run")
-    if not args.no_extras and world == 1 and not args.plumbing_test:
+    if args.full and not args.no_extras and world == 1 and not args.plumbing_test:
         for key, fn in (("roofline_stem", lambda: stem_roofline(local)), ("latency", lambda: latency_probe(local)),
                         ("trunk_exact_f32" if arith != "f32" else "trunk_f16x2",
                          lambda: arith_line("f32" if arith != "f32" else "f16x2", local, threads, G, args.pipeline, mean_plies)),

@@ -251,7 +251,7 @@ def test_closed_loop_selfplay_train_selfplay():
     net.close()
 
 
-def test_train_pipeline_runs_a_few_batches():
+def test_train_pipeline_runs_a_few_batches(tmp_path):
     """TrainPipeline (reference train_mxnet.py:38-300 wired onto the engine): a few batches of
     self-play + update + one arena evaluation complete and produce finite numbers."""
     pytest.importorskip("torch")
@@ -259,7 +259,7 @@ def test_train_pipeline_runs_a_few_batches():
     conf = dict(board_width=8, board_height=8, n_in_row=4, learn_rate=2e-3, lr_multiplier=1.0, temp=1.0,
                 n_playout=30, c_puct=5, buffer_size=5000, batch_size=64, epochs=2, kl_targ=0.02, check_freq=3,
                 pure_mcts_playout_num=30, game_batch_num=3, play_batch_size=2, concurrent_games=16, n_blocks=1,
-                n_filter=64, eval_games=4, model_dir="/tmp/apz_models_test", async_update=False)
+                n_filter=64, eval_games=4, model_dir=str(tmp_path / "models"), async_update=False)
     tp = TrainPipeline(conf, seed=3)
     hist = tp.run()
     assert len(hist) == 3 and "win_ratio" in hist[-1] and 0.0 <= hist[-1]["win_ratio"] <= 1.0
@@ -268,7 +268,7 @@ def test_train_pipeline_runs_a_few_batches():
     tp.close()
 
 
-def test_asynchronous_train_pipeline_on_the_gpu():
+def test_asynchronous_train_pipeline_on_the_gpu(tmp_path):
     """The asynchronous schedule with the REAL pieces on one GPU (alphapig_amd/pipeline.py: train_mxnet.py:265-300 with
     the update in a trainer thread): self-play rounds keep stepping while the HIP trainer updates on its own stream with
     its own evaluator handle; every published version is installed into the self-play evaluator device to device, the
@@ -279,7 +279,7 @@ def test_asynchronous_train_pipeline_on_the_gpu():
     conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=1e-3, lr_multiplier=1.0, temp=1.0,
                 n_playout=12, c_puct=5, buffer_size=200000, batch_size=64, epochs=3, kl_targ=0.02, check_freq=25,
                 pure_mcts_playout_num=20, game_batch_num=60, play_batch_size=1, concurrent_games=64, n_blocks=2,
-                n_filter=128, eval_games=2, model_dir="/tmp/apz_models_async", async_update=True, round_seconds=0.1)
+                n_filter=128, eval_games=2, model_dir=str(tmp_path / "models"), async_update=True, round_seconds=0.1)
     tp = TrainPipeline(conf, seed=5)
     steps_log, run_steps = [], tp.engine.run_steps
 
@@ -301,7 +301,7 @@ def test_asynchronous_train_pipeline_on_the_gpu():
     assert inside >= 1, (tp.update_intervals[:3], steps_log[:5])
     ups = [h for h in tp.trainer_history if "loss" in h]
     assert ups and all(np.isfinite(h["loss"]) and np.isfinite(h["kl"]) for h in ups)
-    assert any("win_ratio" in h for h in tp.trainer_history) and os.path.exists("/tmp/apz_models_async/current_policy.model")
+    assert any("win_ratio" in h for h in tp.trainer_history) and (tmp_path / "models" / "current_policy.model").exists()
     planes = (np.random.RandomState(2).rand(5, 9, 15, 15) < 0.2).astype(np.float32)
     pa, va = tp.policy_value_net.policy_value(planes)          # installed from the last published snapshot
     tp._async_trainer.sync_evaluator(tp._eval_net)

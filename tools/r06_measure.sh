@@ -10,7 +10,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$PART" = a ]; then
     echo "== driver command" | tee -a $OUT/log.txt
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2>> $OUT/log.txt || echo "bench failed" | tee -a $OUT/log.txt
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2>> $OUT/log.txt || echo "bench failed" | tee -a $OUT/log.txt
     echo "== bench trace + pmc (tools/profile_gpu.sh)" | tee -a $OUT/log.txt
     bash tools/profile_gpu.sh > $OUT/profile_gpu.txt 2>&1 || echo "profile_gpu failed" | tee -a $OUT/log.txt
     echo "== trunk kernels side by side: tools/_build/wino3h_bench" | tee -a $OUT/log.txt
