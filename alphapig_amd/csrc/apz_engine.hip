@@ -21,6 +21,7 @@
 #include "trunk15_wino3s.h"
 #include "trunk15_wino3b.h"
 #include "trunk15_wino3h.h"
+#include "trunk15_wino3h16.h"
 #include "conv8_split.h"
 #include "conv8_small.h"
 #include "wgrad_wino3.h"
@@ -163,6 +164,9 @@ struct apz_engine {
     unsigned* ovf_dev = nullptr;             // the same words as the device sees them
     unsigned* ovf_cur = nullptr;             // (device pointer) the word of the forward being queued
     bool force_f32 = false;                  // the repeat of an overflowed forward
+    // APZ_ARITH_F16X2, batches > 32: trunk15_wino3h16_kernel (16-channel chunks, three products); APZ_F16X2_K8=1 in the
+    // environment at engine creation selects its predecessor trunk15_wino3h_kernel instead (A/B measurements)
+    bool f16x2_k8 = false;
     long ovf_repeats = 0;                    // forwards repeated so far (apz_trunk_overflows)
     int trunk_kernel = APZ_TRUNK_WINOGRAD;   // or APZ_TRUNK_DIRECT (trunk15_ring_kernel): apz_test_select_trunk, tests only
     // profiling
@@ -459,21 +463,21 @@ int launch_wino3b_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
     return APZ_OK;
 }
 
-// The 2 x fp16 split kernel: same layouts, same grids, 512 threads
-template <bool RESID>
+// The 2 x fp16 split kernels (K16: trunk15_wino3h16_kernel, else trunk15_wino3h_kernel): same layouts, same grids, 512 threads
+template <bool RESID, bool K16>
 int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    using T = apz::Wino3H;
+    using T = typename std::conditional<K16, apz::Wino3H16, apz::Wino3H>::type;
+    const auto kern = K16 ? apz::trunk15_wino3h16_kernel<RESID, true> : apz::trunk15_wino3h_kernel<RESID, true>;
     bool& configured = e->lds_attr_set[attr_slot];
     if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3h_kernel<RESID, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    T::LDS_BYTES));
+        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
         configured = true;
     }
     for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS) {
         const int nb = std::min(n - b0, WINO3_MAX_BOARDS);
         const size_t off = (size_t)b0 * T::C * T::GPLANE;
         const int grid = apz::wino3_grid(nb, e->num_cu);
-        hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
                            (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
     }
     HIP_TRY(hipGetLastError());
@@ -483,8 +487,12 @@ int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
 int launch_trunk_wino3(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     if (e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur &&
         (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
-        if (resid) return launch_wino3h_t<true>(e, 32, L, in, resid, out, n);
-        return launch_wino3h_t<false>(e, 33, L, in, resid, out, n);
+        if (e->f16x2_k8) {
+            if (resid) return launch_wino3h_t<true, false>(e, 32, L, in, resid, out, n);
+            return launch_wino3h_t<false, false>(e, 33, L, in, resid, out, n);
+        }
+        if (resid) return launch_wino3h_t<true, true>(e, 36, L, in, resid, out, n);
+        return launch_wino3h_t<false, true>(e, 37, L, in, resid, out, n);
     }
     if (e->trunk_arith == APZ_ARITH_BF16X3 && L.upk3b && (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
         if (resid) return launch_wino3b_t<true>(e, 26, L, in, resid, out, n);
@@ -856,6 +864,10 @@ apz_engine* apz_create(const apz_config* cfg) {
     hipDeviceProp_t prop;
     if ((err = hipGetDeviceProperties(&prop, cfg->device)) != hipSuccess) return bail("hipGetDeviceProperties", err);
     e->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    {
+        const char* k8 = getenv("APZ_F16X2_K8");
+        e->f16x2_k8 = k8 && atoi(k8) != 0;
+    }
     if ((err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess)
         return bail("hipStreamCreate", err);
     e->ring = cfg->net_kind == APZ_NET_RESNET && cfg->height == 15 && cfg->width == 15 && cfg->n_filter == 128;
@@ -1022,16 +1034,16 @@ int apz_load_weights(apz_engine* e, const char* const* names, const float* const
                 std::vector<uint16_t> uh;
                 std::vector<float> b3(apz::Wino3H::BIAS_FLOATS);
                 for (int o = 0; o < 128; o++) b3[o] = (float)shift[o];
-                apz::wino3h_pack_host(
-                    [&](int co, int ci, int pos) {
-                        double g[3][3], t[3];
-                        for (int a = 0; a < 3; a++)
-                            for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-                        const int i = pos / 6, k = pos % 6;
-                        for (int b = 0; b < 3; b++) t[b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-                        return t[0] * G[k][0] + t[1] * G[k][1] + t[2] * G[k][2];
-                    },
-                    uh, b3.data() + 128);
+                auto u_of = [&](int co, int ci, int pos) {
+                    double g[3][3], t[3];
+                    for (int a = 0; a < 3; a++)
+                        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
+                    const int i = pos / 6, k = pos % 6;
+                    for (int b = 0; b < 3; b++) t[b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
+                    return t[0] * G[k][0] + t[1] * G[k][1] + t[2] * G[k][2];
+                };
+                if (e->f16x2_k8) apz::wino3h_pack_host<apz::Wino3H>(u_of, uh, b3.data() + 128);
+                else apz::wino3h_pack_host<apz::Wino3H16>(u_of, uh, b3.data() + 128);
                 if (!L.upk3h) HIP_TRY(hipMalloc(&L.upk3h, apz::Wino3H::UPK_BYTES));
                 HIP_TRY(hipMemcpy(L.upk3h, uh.data(), apz::Wino3H::UPK_BYTES, hipMemcpyHostToDevice));
                 rc = upload(&L.bias3h, b3);
@@ -1444,8 +1456,12 @@ int apz_load_weights_dev(apz_engine* e, const char* const* names, const void* co
             if (x4 && e->trunk_arith == APZ_ARITH_F16X2) {
                 if (!L.upk3h) HIP_TRY(hipMalloc(&L.upk3h, apz::Wino3H::UPK_BYTES));
                 if (!L.bias3h) HIP_TRY(hipMalloc(&L.bias3h, apz::Wino3H::BIAS_FLOATS * sizeof(float)));
-                hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel, dim3(128), dim3(128), 0, st, w, scale, shift,
-                                   (unsigned short*)L.upk3h, L.bias3h);
+                if (e->f16x2_k8)
+                    hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H>, dim3(128), dim3(128), 0, st, w, scale, shift,
+                                       (unsigned short*)L.upk3h, L.bias3h);
+                else
+                    hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H16>, dim3(128), dim3(128), 0, st, w, scale, shift,
+                                       (unsigned short*)L.upk3h, L.bias3h);
             }
             if (e->small8 && L.wpk12)
                 hipLaunchKernelGGL(apz::pack_direct_kernel, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, w, scale,

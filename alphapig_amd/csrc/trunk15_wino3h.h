@@ -83,10 +83,11 @@ struct Wino3H {
 };
 
 // Host packing: U[pos][co][ci] (double) -> the kernel's fp16 x 2 layout + the per-channel inverse scales.
-// `u_of(co, ci, pos)` returns the value.  inv_scale: 128 floats (goes behind the 128 biases).
-template <class F>
+// `u_of(co, ci, pos)` returns the value.  inv_scale: 128 floats (goes behind the 128 biases).  L: the layout (Wino3H, or
+// Wino3H16 of trunk15_wino3h16.h: the same terms and scales, another order).
+template <class L = Wino3H, class F>
 inline void wino3h_pack_host(F u_of, std::vector<uint16_t>& out, float* inv_scale) {
-    out.assign(Wino3H::UPK_BYTES / 2, 0);
+    out.assign(L::UPK_BYTES / 2, 0);
     for (int co = 0; co < 128; co++) {
         double m = 0;
         for (int ci = 0; ci < 128; ci++)
@@ -101,8 +102,8 @@ inline void wino3h_pack_host(F u_of, std::vector<uint16_t>& out, float* inv_scal
                 uint16_t hb, lb;
                 std::memcpy(&hb, &hi, 2);
                 std::memcpy(&lb, &lo, 2);
-                out[Wino3H::upk_offset(co, ci, pos, 0) / 2] = hb;
-                out[Wino3H::upk_offset(co, ci, pos, 1) / 2] = lb;
+                out[L::upk_offset(co, ci, pos, 0) / 2] = hb;
+                out[L::upk_offset(co, ci, pos, 1) / 2] = lb;
             }
     }
 }

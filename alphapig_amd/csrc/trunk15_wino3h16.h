@@ -1,0 +1,463 @@
+// Trunk 3x3 convolution (128 -> 128 channels, 15x15 board) + folded BN + (residual) + ReLU: trunk15_wino3h.h's fused
+// F(4x4,3x3) Winograd convolution on the fp16 matrix pipe with two-term operands, K loop repacked (round 7).  gfx950 only.
+//
+// What stays: the arithmetic (x = hi + lo, two fp16 terms, weights times S[co] = 2^k, 1 / S[co] in the bias FMA, activations
+// unscaled, the overflow word), the work item (board pair x 64 output channels x 36 positions), the grid and duo scheme, eight
+// waves = (32-channel half, 3x3 position block) with 144 accumulators each, and the epilogue, line for line.
+//
+// What changes -- the K packing.  trunk15_wino3h.h contracts k = 16 as 8 channels x the two WEIGHT terms (A = [Whi | Wlo],
+// B = [Vt | Vt]): four products per 8 channels, lo.lo included, and both lane halves of a B fragment read the same 16 bytes.
+// Here k = 16 is 16 channels of ONE term, and a chunk of 16 input channels takes three MFMAs per (position, 32 output channels):
+//     H . Vlo  +  L . Vhi  +  H . Vhi        (H = [Whi ch 0-7 | Whi ch 8-15], L = the same of Wlo, V likewise)
+// -- the three products the accuracy argument rests on (|error| <= 2^-22 relative per operand); lo.lo is dropped.  Per wave and
+// 16 input channels: 27 MFMAs instead of 36, 18 V fragment reads instead of 36, one chunk barrier instead of two; the weight
+// bytes are the same (two 1 KB units per position).
+//
+// LDS.  A 16-channel V buffer is 36 x 2 terms x 32 columns x 16 ch x 2 B = 72 KiB; two of them are 144 KiB of the 160, and the
+// raw input tiles no longer fit beside them.  So they are not staged: every thread owns one (board, channel, tile) of a chunk
+// -- 2 x 16 x 16 = 512 -- and buffer-loads the tile's 4 x 4 pixels into 16 registers a chunk ahead (the twin workgroup of the
+// duo scheme reads the same planes: L2).  A board's 16 tiles are one 16-lane DPP row, so the halo rows -1 and 4 of the patch
+// are row_shr:4 / row_shl:4 of the neighbouring tiles' rows 3 and 0 (zero across the board edge by bound_ctrl), and the halo
+// columns come from the quad neighbours' column-pass inputs as in trunk15_wino3h.h.  Each thread transforms the whole 6 x 6
+// patch of its channel (the old kernel: half of it, for 8 channels).
+//
+// Layouts.  in / resid / out: rows16 [n][128][15][16] (col 15 == 0).  V (LDS): [pos 36][term 2 (hi, lo)][col 32][half 2][8 ch]
+// fp16, col = board * 16 + tile, and the channel half stored at half ^ (col >> 3 & 1): a B fragment (lane: col = lane & 31,
+// channels 8 (lane >> 5) .. + 7) is ONE ds_read_b128 with no bank conflict (unswizzled, the 32-byte column stride puts two lanes
+// of every b128 lane group on one bank quad), and the transform's ds_write_b32 of 32 lanes fall on 16 banks (2-way: free).
+// upk: [cog 4][block 4][chunk 8][position 9][unit 2 (H, L)][half 2][co 32][8 ch] fp16.  bias: [128 bias][128 1/S].
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <type_traits>
+
+#include "trunk15_wino3h.h"
+
+namespace apz {
+
+struct Wino3H16 {
+    static constexpr int C = 128, CK = 16, NCHUNK = C / CK;            // 8 chunks of 16 input channels
+    static constexpr int GPLANE = 240;
+    static constexpr int VTERM = 32 * 32, VPOS = 2 * VTERM, V_BYTES = 36 * VPOS;   // 1024, 2048, 73728 bytes
+    static constexpr int UNIT = 2 * 32 * 16;                           // bytes of one weight unit (H or L of a position): 1024
+    static constexpr size_t UPK_BYTES = (size_t)4 * 4 * NCHUNK * 9 * 2 * UNIT;     // 2.36 MB per layer (as Wino3H)
+    static constexpr int BIAS_FLOATS = 256;                            // [bias 128][1 / S 128]
+    // epilogue: M and the store staging alias the two V buffers
+    static constexpr int MQ_FLOATS = 36 * 16 * 32;                     // 73728 bytes
+    static constexpr int SROW = 20, SPLANE = 16 * SROW;                // staging plane: 16 rows x 20 floats
+    static constexpr int STG_FLOATS = 8 * 4 * SPLANE;                  // 8 waves x 4 planes (40 KiB)
+    static constexpr int LDS_BYTES = 2 * V_BYTES;                      // 147456
+    static_assert((MQ_FLOATS + STG_FLOATS) * 4 <= LDS_BYTES, "the epilogue area fits over V");
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static_assert(UPK_BYTES == Wino3H::UPK_BYTES, "same weight buffer as trunk15_wino3h.h");
+    // byte offset of element (co, ci, pos, term) in the packed weights
+    __host__ __device__ static size_t upk_offset(int co, int ci, int pos, int term) {
+        const int i = pos / 6, k = pos % 6, ri = i / 3, ki = k / 3, p9 = 3 * (i % 3) + (k % 3);
+        const int cog = co >> 5, r = co & 31, chunk = ci >> 4, half = (ci >> 3) & 1, w = 2 * ri + ki;
+        return ((((size_t)(cog * 4 + w) * NCHUNK + chunk) * 9 + p9) * 2 + term) * UNIT + half * 512 + r * 16 + (ci & 7) * 2;
+    }
+    static float scale_for(double m) { return Wino3H::scale_for(m); }
+};
+
+#ifdef APZ_WINO3H_STAMPS
+__device__ unsigned long long apz_wino3h16_stamps[4 * 8 * 12];   // [workgroup 4][wave 8][phase 12]
+#endif
+
+#ifndef APZH16_RING
+#define APZH16_RING 3        /* positions (H + L: 8 registers each) of the weight ring; RING - 1 in flight.  Must divide 18 */
+#endif
+#ifndef APZH16_RAW_SLOT
+#define APZH16_RAW_SLOT 4    /* the MFMA slot whose end requests the raw tiles of the chunk after next */
+#endif
+
+template <bool RESID, bool RELU = true>
+__global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __restrict__ in, const void* __restrict__ upk,
+                                                               const float* __restrict__ bias, const float* __restrict__ resid,
+                                                               float* __restrict__ out, int n, unsigned* __restrict__ flag) {
+    using T = Wino3H16;
+#ifdef APZ_WINO3H_STAMPS
+    // phases as trunk15_wino3h.h: 0 item prologue, 1 chunk barrier waits, 2 chunk bodies, 3 staging + stores, 4 epilogue first
+    // barriers, 5 item start, 6 s_memrealtime ticks, 7 total, 8 M write + residual, 9 gather + output transform, 10 second barriers
+    unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st_t = __builtin_readcyclecounter();
+    const unsigned long long st_t0 = st_t, st_r0 = __builtin_amdgcn_s_memrealtime();
+#define APZH16_STAMP(ph_)                                             \
+    {                                                                 \
+        const unsigned long long now_ = __builtin_readcyclecounter(); \
+        st_acc[ph_] += now_ - st_t;                                   \
+        st_t = now_;                                                  \
+    }
+#else
+#define APZH16_STAMP(ph_)
+#endif
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    char* vbase = reinterpret_cast<char*>(lds);                           // [2][V_BYTES]
+    float* mq = lds;                                                      // epilogue: M[pos 36][co 16][col 32] (over V)
+    float* stg = mq + T::MQ_FLOATS;                                       // epilogue: [wave 8][plane 4][16 x 20]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    // ---- work items: as trunk15_wino3h_kernel
+    const int npairs = (n + 1) >> 1, G_ = (int)gridDim.x, b_ = (int)blockIdx.x;
+    const bool duo = (G_ & 15) == 0;
+    const int pair0 = duo ? ((b_ >> 4) * 8 + (b_ & 7)) : b_;
+    const int pstride = duo ? (G_ >> 1) : G_;
+    const int h_fix = (b_ >> 3) & 1;
+    const int np = pair0 < npairs ? (npairs - pair0 + pstride - 1) / pstride : 0;
+    const int nitems = duo ? np : 2 * np;
+    if (np == 0) return;
+    auto item_pair = [&](int t) { return pair0 + (duo ? t : (t >> 1)) * pstride; };
+    auto item_half = [&](int t) { return duo ? h_fix : (t & 1); };
+
+    const unsigned plane_b = T::GPLANE * 4;
+    const unsigned act_bytes = (unsigned)n * T::C * plane_b;
+    const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, act_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_res =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RESID ? resid : in), 0, act_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_u =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)T::UPK_BYTES, 0x00020000);
+    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+    };
+    auto bstore = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, const f32x4 v) {   // soffset = 0: see trunk15_wino3.h
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, 0);
+    };
+
+    // ---- transform role: board tb, channels 4 cq .. 4 cq + 3 of the chunk.  lane -> (tile = bits 0-3: ttx = bits 0-1, tty =
+    // bits 2-3; channel pair cpl = bit 4; channel parity e = bit 5): a board's 16 tiles are one DPP row (halo rows: row_shr /
+    // row_shl by 4 lanes), the tile columns of a tile row are a quad (halo columns: quad_perm), the two channels of a pair sit
+    // 32 lanes apart (v_permlane32_swap_b32 exchanges them).
+    const int tb = wave & 1, cq = wave >> 1;
+    const int ttx = lane & 3, tty = (lane >> 2) & 3, tile = lane & 15, cpl = (lane >> 4) & 1, e = lane >> 5;
+    const int chl = 4 * cq + 2 * cpl + e;                          // channel of the chunk (0..15)
+    const int cpair = 2 * cq + cpl;                                // channel pair (0..7): V half cpair >> 2, dword cpair & 3
+    const int vcol = tb * 16 + tile;
+    // bytes in a V term: column vcol, swizzled half, dword of the pair; lanes of the even channel write positions k = 0..2 of a
+    // row, lanes of the odd channel k = 3..5
+    const int tv_off = vcol * 32 + (((cpair >> 2) ^ ((vcol >> 3) & 1)) * 16) + (cpair & 3) * 4 + e * 3 * T::VPOS;
+    const unsigned col16_mask = ttx == 3 ? 0u : 0xffffffffu;       // column 16 does not exist
+    const float c4l = ttx == 0 ? 0.f : 4.f;                        // column -1 of the first tile column is the zero border
+    // raw tile rows: the lane part of the address (channel within the wave's four, tile); row 15 (tile row 3, its row 3) is
+    // out of range (0x80000000: the load returns zeros)
+    const unsigned raw_vo = (unsigned)(2 * cpl + e) * plane_b + (unsigned)(tty * 4 * 16 + ttx * 4) * 4;
+    const unsigned raw_vo3 = tty == 3 ? 0x80000000u : raw_vo + 3u * 64u;
+    f32x4 raw[4];
+    auto raw_load = [&](int t, int c) {                            // chunk c of item t -> raw
+        const int bdp = 2 * item_pair(t) + tb;
+        const int bd = bdp < n ? bdp : n - 1;
+        const unsigned so = (unsigned)(bd * T::C + c * T::CK + 4 * cq) * plane_b;
+#pragma unroll
+        for (int r = 0; r < 3; r++) raw[r] = bload(r_in, raw_vo + (unsigned)r * 64u, so);
+        raw[3] = bload(r_in, raw_vo3, so);
+    };
+
+    f32x2 tt[6][2];                                // vertical-pass results: rows 0..5, column pairs (0, 1), (2, 3)
+    float oo[6];
+    // B^T over the rows of the 6 x 6 patch (x0 = row -1 .. x5 = row 4), on column pairs
+    auto vpass = [&](int kc) {
+        f32x2 x[6];
+        // rows -1 and 4: row 3 of the tile above, row 0 of the tile below (zero beyond the board: bound_ctrl)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const float r3 = raw[3][2 * kc + j], r0 = raw[0][2 * kc + j];
+            x[0][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r3), 0x114, 0xF, 0xF, true));   // row_shr:4
+            x[5][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r0), 0x104, 0xF, 0xF, true));   // row_shl:4
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) x[r + 1] = f32x2{raw[r][2 * kc], raw[r][2 * kc + 1]};
+        const f32x2 a = fma2(-4.f, x[2], x[4]), b = fma2(-4.f, x[1], x[3]);
+        const f32x2 c = x[4] - x[2], d = x[3] - x[1];
+        tt[0][kc] = fma2(4.f, x[0], fma2(-5.f, x[2], x[4]));
+        tt[1][kc] = a + b;
+        tt[2][kc] = a - b;
+        tt[3][kc] = fma2(2.f, d, c);
+        tt[4][kc] = fma2(-2.f, d, c);
+        tt[5][kc] = fma2(4.f, x[1], fma2(-5.f, x[3], x[5]));
+    };
+    // B^T over the columns of row j: the halo columns (-1 and 4) are the quad neighbours' columns 3 and 0 of the same row
+    // (quad_perm [0,0,1,2] / [1,2,3,3]); v = (v1, v2), (v3, v4), (v0, v5) -> o[0..5]
+    auto col_pass = [&](int j) {
+        const float c3 = tt[j][1][1], c0 = tt[j][0][0];
+        const int l = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c3), 0x90, 0xF, 0xF, true);
+        const int r = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c0), 0xF9, 0xF, 0xF, true);
+        const float v0 = __builtin_bit_cast(float, l), v5 = __builtin_bit_cast(float, (unsigned)r & col16_mask);
+        const f32x2 ab = fma2(-4.f, tt[j][0], tt[j][1]);   // (b, a) = (v3 - 4 v1, v4 - 4 v2)
+        const f32x2 dc = tt[j][1] - tt[j][0];              // (d, c) = (v3 - v1, v4 - v2)
+        oo[0] = __builtin_fmaf(c4l, v0, __builtin_fmaf(-5.f, tt[j][0][1], tt[j][1][1]));
+        oo[3] = __builtin_fmaf(2.f, dc[0], dc[1]);
+        oo[1] = ab[1] + ab[0];
+        oo[4] = __builtin_fmaf(-2.f, dc[0], dc[1]);
+        oo[2] = ab[1] - ab[0];
+        oo[5] = __builtin_fmaf(4.f, tt[j][0][0], __builtin_fmaf(-5.f, tt[j][1][0], v5));
+    };
+    // lanes of the even channel keep o[0..2] and hand o[3..5] to their pair partner (32 lanes up), lanes of the odd channel
+    // the other way round: afterwards (o[k], o[k + 3]) = (even channel's value, odd channel's value) of position k in the even
+    // channel's lanes and of position k + 3 in the odd channel's.  (two wait states after a vector write of an operand)
+    auto exchange = [&]() {
+        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5"
+            : "+v"(oo[0]), "+v"(oo[1]), "+v"(oo[2]), "+v"(oo[3]), "+v"(oo[4]), "+v"(oo[5]));
+    };
+    // (even channel's value, odd channel's value) of one position -> hi = both rounded to fp16, lo = the exact remainders
+    // (v_fma_mix) rounded to fp16
+    auto emit = [&](char* vp, float ev, float od) {
+        typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
+        const f16x2_ h2 = {(_Float16)ev, (_Float16)od};                  // v_cvt_pk_f16_f32
+        const unsigned hu = __builtin_bit_cast(unsigned, h2);
+        unsigned lu;
+        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(ev));
+        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(od));
+        *reinterpret_cast<unsigned*>(vp) = hu;
+        *reinterpret_cast<unsigned*>(vp + T::VTERM) = lu;
+    };
+    // The transform of one chunk (raw -> V[vpar]) in 27 slices, three per MFMA slot: 0, 1 the vertical pass (raw is free
+    // behind it), 2 nothing, then per row j = 0..5: column pass, exchange, positions k = 0, 1, position k = 2
+    auto tslice = [&](int vpar, auto KK) {
+        constexpr int K = decltype(KK)::value;
+        char* vp = vbase + vpar * T::V_BYTES + tv_off;
+        if constexpr (K < 2) vpass(K);
+        else if constexpr (K >= 3) {
+            constexpr int j = (K - 3) / 4, part = (K - 3) % 4;
+            if constexpr (part == 0) col_pass(j);
+            else if constexpr (part == 1) exchange();
+            else if constexpr (part == 2) {
+                emit(vp + (j * 6 + 0) * T::VPOS, oo[0], oo[3]);
+                emit(vp + (j * 6 + 1) * T::VPOS, oo[1], oo[4]);
+            } else emit(vp + (j * 6 + 2) * T::VPOS, oo[2], oo[5]);
+        }
+    };
+    auto transform = [&](int vpar) {
+#define APZH16_TS(k) tslice(vpar, std::integral_constant<int, k>{});
+        APZH16_TS(0) APZH16_TS(1) APZH16_TS(2) APZH16_TS(3) APZH16_TS(4) APZH16_TS(5) APZH16_TS(6) APZH16_TS(7) APZH16_TS(8)
+        APZH16_TS(9) APZH16_TS(10) APZH16_TS(11) APZH16_TS(12) APZH16_TS(13) APZH16_TS(14) APZH16_TS(15) APZH16_TS(16)
+        APZH16_TS(17) APZH16_TS(18) APZH16_TS(19) APZH16_TS(20) APZH16_TS(21) APZH16_TS(22) APZH16_TS(23) APZH16_TS(24)
+        APZH16_TS(25) APZH16_TS(26)
+#undef APZH16_TS
+    };
+
+    // ---- MFMA role: 32-channel half cc of the item's 64, position block (ri, ki)
+    const int cc = wave >> 2, ri = (wave >> 1) & 1, ki = wave & 1, blk = wave & 3;
+    const int r31 = lane & 31, hh = lane >> 5;
+    const unsigned a_vo = lane * 16;                  // a unit: lanes 0-31 channels 0-7 of their output channel, 32-63 channels 8-15
+    const int wpos0 = 18 * ri + 3 * ki;               // first position of this wave's block
+    auto pos_off = [](int p9) { return (6 * (p9 / 3) + (p9 % 3)) * T::VPOS; };   // position p9 of the block, relative to wpos0
+
+    // weight stream: the 18 units (position p9, H / L) of a chunk are contiguous, 144 per item and wave; a load is base +
+    // (u / 4) * 4096 as the scalar offset + (u % 4) * 1024 as the immediate (u = 2 p9 + term)
+    static constexpr int RING = APZH16_RING;
+    static_assert(18 % RING == 0 && RING >= 2, "ring slots must tile two chunks");
+    f16x8 ah[RING], al[RING];
+    auto unit_base = [&](int t, int c) {
+        const int cog = 2 * item_half(t) + cc;
+        return (unsigned)(((cog * 4 + blk) * T::NCHUNK + c) * 18) * T::UNIT;
+    };
+    unsigned ub_cur = 0, ub_nxt = 0;
+    auto unit_pair_at = [&](unsigned base, int p9, int slot) {
+        const int u = 2 * p9;
+        ah[slot] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_u, a_vo + (unsigned)(u & 3) * T::UNIT,
+                                                                                  base + (unsigned)(u >> 2) * 4u * T::UNIT, 0));
+        al[slot] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_u, a_vo + (unsigned)((u + 1) & 3) * T::UNIT,
+                                                                                  base + (unsigned)((u + 1) >> 2) * 4u * T::UNIT, 0));
+    };
+    // position p9 (0 .. 8 + RING - 1) counted from the start of the current chunk
+    auto unit_load = [&](int p9, int slot) {
+        if (p9 < 9) unit_pair_at(ub_cur, p9, slot);
+        else unit_pair_at(ub_nxt, p9 - 9, slot);
+    };
+
+    unsigned nonfinite = 0;                           // any pre-ReLU output of this thread that is not a finite number
+
+    ub_cur = ub_nxt = unit_base(0, 0);
+#pragma unroll
+    for (int u = 0; u < RING - 1; u++) unit_load(u, u);
+    raw_load(0, 0);
+    // the later-dispatched half of the workgroup (waves 4..7, the SIMD partners of 0..3) loses every issue arbitration by age
+    // (MI355X_MICROARCH.md, "Two waves per SIMD", item 4): one static priority raise evens it out
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+
+    for (int t = 0; t < nitems; t++) {
+        const int h = item_half(t);
+        const int bd0 = 2 * item_pair(t);
+        const bool two = bd0 + 1 < n;
+        // ---- item prologue: raw holds chunk 0 (requested in front of the loop / in the last epilogue step): V[0]
+        __syncthreads();                              // the previous item's M / staging (over V) consumed
+        APZH16_STAMP(5)
+        transform(0);
+        raw_load(t, 1);
+        f32x16h acc[9];
+#pragma unroll
+        for (int p = 0; p < 9; p++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) acc[p][v] = 0.f;
+        APZH16_STAMP(0)
+
+        // ---- chunk loop.  Chunk c: [barrier] MFMAs over V[c & 1]: 9 slots = the wave's 9 positions, each 3 MFMAs + three
+        // slices of the transform of raw (= chunk c + 1) -> V[(c + 1) & 1] + the refill of the weight ring slot freed by the
+        // previous slot; behind slot APZH16_RAW_SLOT (the vertical pass long done) raw <- chunk c + 2.
+        f16x8 bfr[2];
+        auto chunk = [&](int c, auto PAR, auto XF, auto LD) {
+            constexpr int par = decltype(PAR)::value;
+            constexpr bool xf = decltype(XF)::value, ld = decltype(LD)::value;
+            __syncthreads();                          // V[par] complete; V[1 - par] free
+            APZH16_STAMP(1)
+            ub_cur = ub_nxt;
+            ub_nxt = c + 1 < T::NCHUNK ? ub_cur + 18u * T::UNIT : (t + 1 < nitems ? unit_base(t + 1, 0) : ub_cur + 18u * T::UNIT);
+            const char* vp = vbase + par * T::V_BYTES;
+            // per-lane fragment offset from an opaque copy of the lane id (see trunk15_wino3h.h)
+            int le = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(le));
+            const int fcol = le & 31;
+            const int b_hi = wpos0 * T::VPOS + fcol * 32 + ((((le >> 5) & 1) ^ ((fcol >> 3) & 1)) * 16);   // B = Vhi, 16 channels
+            const int b_lo = b_hi + T::VTERM;                                                                // B = Vlo
+            bfr[0] = *reinterpret_cast<const f16x8*>(vp + b_hi);
+            bfr[1] = *reinterpret_cast<const f16x8*>(vp + b_lo);
+#define APZH16_SLOT(k)                                                                                                   \
+            {                                                                                                            \
+                constexpr int p9 = (k), slot = (par * 9 + (k)) % RING;                                                   \
+                /* the small products first: H . Vlo, L . Vhi, then H . Vhi; every V fragment is re-read for the next    \
+                   position right behind the last MFMA that uses it */                                                   \
+                acc[p9] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[slot], bfr[1], acc[p9], 0, 0, 0);                    \
+                if (p9 + 1 < 9) bfr[1] = *reinterpret_cast<const f16x8*>(vp + b_lo + pos_off(p9 + 1));                   \
+                acc[p9] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[slot], bfr[0], acc[p9], 0, 0, 0);                    \
+                acc[p9] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[slot], bfr[0], acc[p9], 0, 0, 0);                    \
+                if (p9 + 1 < 9) bfr[0] = *reinterpret_cast<const f16x8*>(vp + b_hi + pos_off(p9 + 1));                   \
+                if (xf) {                                                                                                \
+                    tslice(1 - par, std::integral_constant<int, 3 * (k)>{});                                             \
+                    tslice(1 - par, std::integral_constant<int, 3 * (k) + 1>{});                                         \
+                    tslice(1 - par, std::integral_constant<int, 3 * (k) + 2>{});                                         \
+                }                                                                                                        \
+                if ((k) == APZH16_RAW_SLOT && ld) raw_load(t, c + 2);                                                    \
+                /* position k + RING - 1 goes into the ring slot of position k - 1, whose MFMAs are done */             \
+                unit_load((k) + RING - 1, (par * 9 + (k) + RING - 1) % RING);                                            \
+                __builtin_amdgcn_sched_barrier(0);                                                                       \
+            }
+            APZH16_SLOT(0) APZH16_SLOT(1) APZH16_SLOT(2) APZH16_SLOT(3) APZH16_SLOT(4) APZH16_SLOT(5) APZH16_SLOT(6) APZH16_SLOT(7) APZH16_SLOT(8)
+#undef APZH16_SLOT
+            APZH16_STAMP(2)
+        };
+        using P0 = std::integral_constant<int, 0>;
+        using P1 = std::integral_constant<int, 1>;
+        using Y = std::true_type;
+        using N = std::false_type;
+        for (int c = 0; c < T::NCHUNK - 2; c += 2) {
+            chunk(c, P0{}, Y{}, Y{});
+            chunk(c + 1, P1{}, Y{}, Y{});
+        }
+        chunk(T::NCHUNK - 2, P0{}, Y{}, N{});         // transforms the last chunk; nothing left to load
+        chunk(T::NCHUNK - 1, P1{}, N{}, N{});         // MFMAs only
+
+        // ---- epilogue: as trunk15_wino3h_kernel.  Four steps of 16 output channels = channels 8 s .. 8 s + 7 of BOTH 32-channel
+        // halves.  Layout of the 32 x 32 tile: lane (col = lane & 31, hh = lane >> 5), register v: channel (v & 3) + 8 (v >> 2) +
+        // 4 hh.  M row (of 16) = 8 cc + channel - 8 s.
+        const int cosel = lane >> 5;               // gather role: M row 2 wave + cosel of the step's 16, column lane & 31
+        const int col = lane & 31, gbd = col >> 4, gtile = col & 15;
+        const int gty = gtile >> 2, gtx = gtile & 3;
+        float* sw = stg + wave * (4 * T::SPLANE);
+        const int s_lin = (lane >> 2) * T::SROW + (lane & 3) * 4;
+        const unsigned ep_vo = lane < 60 ? lane * 16 : 0x80000000u;
+        auto row_chan = [&](int s, int row) { return (2 * h + (row >> 3)) * 32 + 8 * s + (row & 7); };
+        f32x4 rs[4];
+        auto resid_request = [&](int s) {
+#pragma unroll
+            for (int pl = 0; pl < 4; pl++) {
+                const int bdp = bd0 + (pl & 1);
+                const int bd = bdp < n ? bdp : n - 1;
+                rs[pl] = bload(r_res, ep_vo, (unsigned)(bd * T::C + row_chan(s, 2 * wave + (pl >> 1))) * plane_b);
+            }
+        };
+        if (RESID) resid_request(0);
+        auto ep_step = [&](auto S_) {
+            constexpr int s = decltype(S_)::value;
+            __syncthreads();                       // MFMAs over V done (s = 0) / M and staging of the previous step consumed
+            APZH16_STAMP(4)
+            {
+                float* mw = mq + wpos0 * 512 + (8 * cc + 4 * hh) * 32 + r31;
+#pragma unroll
+                for (int p9 = 0; p9 < 9; p9++)
+#pragma unroll
+                    for (int e4 = 0; e4 < 4; e4++) mw[(6 * (p9 / 3) + p9 % 3) * 512 + e4 * 32] = acc[p9][4 * s + e4];
+            }
+            if (RESID) {
+#pragma unroll
+                for (int pl = 0; pl < 4; pl++) *reinterpret_cast<f32x4*>(sw + pl * T::SPLANE + s_lin) = rs[pl];
+            }
+            // the accumulators are spent: the next item's first raw tiles
+            if (s == 3 && t + 1 < nitems) raw_load(t + 1, 0);
+            APZH16_STAMP(8)
+            __syncthreads();                       // M complete
+            APZH16_STAMP(10)
+            {
+                const int co16 = 2 * wave + cosel;
+                const float* mp = mq + co16 * 32 + col;
+                float hrow[6][4];                   // the k-direction transform of every row
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    float m[6];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 512];
+                    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
+                    hrow[i][0] = (m[0] + s12) + s34;
+                    hrow[i][1] = __builtin_fmaf(2.f, d34, d12);
+                    hrow[i][2] = __builtin_fmaf(4.f, s34, s12);
+                    hrow[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+                }
+                if (RESID && s + 1 < 4) resid_request(s + 1);
+                const int ch = row_chan(s, co16);
+                const float bv = bias[ch];
+                const float is = bias[128 + ch];                     // 1 / S of the channel (a power of two)
+                float* sp = sw + (cosel * 2 + gbd) * T::SPLANE + (4 * gty) * T::SROW + 4 * gtx;
+                f32x4 y[4];
+#pragma unroll
+                for (int ee = 0; ee < 4; ee++) {
+                    const float s12 = hrow[1][ee] + hrow[2][ee], d12 = hrow[1][ee] - hrow[2][ee];
+                    const float s34 = hrow[3][ee] + hrow[4][ee], d34 = hrow[3][ee] - hrow[4][ee];
+                    y[0][ee] = (hrow[0][ee] + s12) + s34;
+                    y[1][ee] = __builtin_fmaf(2.f, d34, d12);
+                    y[2][ee] = __builtin_fmaf(4.f, s34, s12);
+                    y[3][ee] = __builtin_fmaf(8.f, d34, d12) + hrow[5][ee];
+                }
+                float chk = 0.f;
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    f32x4 v;
+#pragma unroll
+                    for (int ee = 0; ee < 4; ee++) v[ee] = __builtin_fmaf(y[a][ee], is, bv);
+                    if (RESID) v += *reinterpret_cast<const f32x4*>(sp + a * T::SROW);   // (wave-private: written above by this wave)
+                    chk += (v[0] + v[1]) + (v[2] + v[3]);   // an overflow of the fp16 split shows as +-inf / NaN here
+#pragma unroll
+                    for (int ee = 0; ee < 4; ee++) v[ee] = RELU ? fmaxf(v[ee], 0.f) : v[ee];
+                    if (gtx == 3) v[3] = 0.f;      // column 15 is the halo column of the rows16 layout
+                    *reinterpret_cast<f32x4*>(sp + a * T::SROW) = v;
+                }
+                nonfinite |= ((chk - chk) != 0.f) ? 1u : 0u;         // 0 for every finite sum; NaN != 0 is true
+            }
+            APZH16_STAMP(9)
+            wave_lds_fence();
+#pragma unroll
+            for (int pl = 0; pl < 4; pl++) {
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(sw + pl * T::SPLANE + s_lin);
+                const unsigned vo = ((pl & 1) == 0 || two) ? ep_vo : 0x80000000u;   // the missing second board of an odd batch
+                bstore(r_out, vo, (unsigned)((bd0 + (pl & 1)) * T::C + row_chan(s, 2 * wave + (pl >> 1))) * plane_b, pv);
+            }
+            APZH16_STAMP(3)
+        };
+        ep_step(std::integral_constant<int, 0>{});
+        ep_step(std::integral_constant<int, 1>{});
+        ep_step(std::integral_constant<int, 2>{});
+        ep_step(std::integral_constant<int, 3>{});
+    }
+    // (a plain store: every writer writes the same 1, and the word may live in pinned host memory)
+    if (nonfinite && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
+#ifdef APZ_WINO3H_STAMPS
+    st_acc[7] = __builtin_readcyclecounter() - st_t0;
+    st_acc[6] = __builtin_amdgcn_s_memrealtime() - st_r0;
+    if (lane == 0 && blockIdx.x < 4)
+        for (int i = 0; i < 12; i++) apz_wino3h16_stamps[(blockIdx.x * 8 + wave) * 12 + i] = st_acc[i];
+#endif
+#undef APZH16_STAMP
+}
+
+}  // namespace apz

@@ -6,6 +6,7 @@
 #pragma once
 #include "trunk15_wino3b.h"
 #include "trunk15_wino3h.h"
+#include "trunk15_wino3h16.h"
 #include "wino_common.h"
 #include <hip/hip_runtime.h>
 
@@ -107,7 +108,9 @@ __global__ void pack_wino3b_folded_kernel(const float* __restrict__ w, const dou
 
 // The same U for trunk15_wino3h.h: one workgroup per output channel (thread = input channel) finds max |U| of the channel,
 // S = Wino3H::scale_for(max), and writes U S as two fp16 terms (both round to nearest even, the remainder in double) at
-// Wino3H::upk_offset; bias3h = [128 folded biases][128 x 1 / S].  Launch: grid 128, block 128.
+// L::upk_offset (L = Wino3H, or Wino3H16 of trunk15_wino3h16.h); bias3h = [128 folded biases][128 x 1 / S].  Launch: grid
+// 128, block 128.
+template <class L>
 __global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const double* __restrict__ scale, const double* __restrict__ shift,
                                           unsigned short* __restrict__ up, float* __restrict__ bias3h) {
     const int co = blockIdx.x, ci = threadIdx.x;
@@ -147,8 +150,8 @@ __global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const dou
         const double x = u[pos] * (double)S;
         const _Float16 hi = (_Float16)(float)x;
         const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
-        up[Wino3H::upk_offset(co, ci, pos, 0) / 2] = __builtin_bit_cast(unsigned short, hi);
-        up[Wino3H::upk_offset(co, ci, pos, 1) / 2] = __builtin_bit_cast(unsigned short, lo);
+        up[L::upk_offset(co, ci, pos, 0) / 2] = __builtin_bit_cast(unsigned short, hi);
+        up[L::upk_offset(co, ci, pos, 1) / 2] = __builtin_bit_cast(unsigned short, lo);
     }
 }
 

@@ -31,7 +31,7 @@ class PolicyValueNet(object):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
-          "f16x2"  every fp32 operand as two fp16 terms on the fp16 matrix pipe, fp32 accumulation (csrc/trunk15_wino3h.h):
+          "f16x2"  every fp32 operand as two fp16 terms on the fp16 matrix pipe, fp32 accumulation (csrc/trunk15_wino3h16.h):
                    the same accuracy class (<= 1e-4 on the logits against the float64 oracle, tests/test_gpu_winograd_
                    numerics.py), different low-order bits, 1.5x faster; an activation beyond the fp16 range makes the
                    engine repeat that forward on the exact kernel (never a silently wrong result);
