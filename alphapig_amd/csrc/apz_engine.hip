@@ -129,7 +129,7 @@ struct apz_engine {
     bool small8 = false;    // 8x8 boards: conv8_kernel / head8_kernel (conv8_small.h)
     float* wfc_raw = nullptr;   // head8_kernel: the policy FullyConnected weight as stored, [hw][4 hw]
     int act_ps = 0, act_rs = 0;
-    bool lds_attr_set[40] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
+    bool lds_attr_set[44] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
     int conv_lds_set[16] = {0};
     // persistent sampler staging (apz_sample_moves_host)
     int32_t* smp_vis = nullptr;
@@ -467,18 +467,22 @@ int launch_wino3b_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
 template <bool RESID, bool K16>
 int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = typename std::conditional<K16, apz::Wino3H16, apz::Wino3H>::type;
-    const auto kern = K16 ? apz::trunk15_wino3h16_kernel<RESID, true> : apz::trunk15_wino3h_kernel<RESID, true>;
+    const void* kern = K16 ? (const void*)apz::trunk15_wino3h16_kernel<RESID, true> : (const void*)apz::trunk15_wino3h_kernel<RESID, true>;
     bool& configured = e->lds_attr_set[attr_slot];
     if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
         configured = true;
     }
     for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS) {
         const int nb = std::min(n - b0, WINO3_MAX_BOARDS);
         const size_t off = (size_t)b0 * T::C * T::GPLANE;
         const int grid = apz::wino3_grid(nb, e->num_cu);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
-                           (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
+        if constexpr (K16)
+            hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
+                               (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur, nullptr, 0);
+        else
+            hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
+                               (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
     }
     HIP_TRY(hipGetLastError());
     return APZ_OK;
@@ -1657,6 +1661,64 @@ int apz_wino_conv(apz_engine* e, const void* x_dev, const void* upk_dev, const v
     return apz_wino_conv_add(e, x_dev, upk_dev, bias_dev, nullptr, y_dev, n, relu, layout, stream);
 }
 
+// ---- the training step's trunk on the f16x2 kernel (csrc/trunk15_wino3h16.h, trunk15_wino3h16_train_kernel)
+int64_t apz_wino3h_packed_size(void) { return (int64_t)(apz::Wino3H16::UPK_BYTES / 4); }
+
+int apz_wino3h_pack_many(apz_engine* e, const void* w_dev, const void* b_dev, int count, void* upk_dev, void* bias_dev,
+                         void* flag_dev, void* stream) {
+    if (!e || !w_dev || !upk_dev || !bias_dev || count < 1 || count > 16384) return fail(APZ_E_ARG, "bad argument");
+    EngineLock guard(e->submit_lock);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    StreamScope sc(e, stream);
+    hipLaunchKernelGGL(apz::pack_wino3h16_many_kernel, dim3(128, 2 * count), dim3(128), 0, e->stream, (const float*)w_dev,
+                       (const float*)b_dev, (unsigned short*)upk_dev, (float*)bias_dev, (unsigned*)flag_dev);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+extern "C++" {
+namespace {
+template <int FORM, bool RESID>
+int launch_wino3h16_train(apz_engine* e, int attr_slot, const void* x_dev, const void* upk_dev, const void* bias_dev,
+                          const void* resid_dev, void* y_dev, int n, void* flag_dev, void* aux, int aux_n, void* stream) {
+    if (!e || !x_dev || !upk_dev || !bias_dev || !y_dev || !aux || n < 1) return fail(APZ_E_ARG, "bad argument");
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wino3h: 15x15 boards only");
+    if (n > WINO3_MAX_BOARDS) return fail(APZ_E_UNSUPPORTED, "wino3h: one launch (<= 16384 boards)");
+    using T = apz::Wino3H16;
+    const auto kern = apz::trunk15_wino3h16_kernel<RESID, false, FORM>;
+    EngineLock guard(e->submit_lock);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    StreamScope sc(e, stream);
+    bool& configured = e->lds_attr_set[attr_slot];
+    if (!configured) {
+        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
+        configured = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(apz::wino3_grid(n, e->num_cu)), dim3(512), T::LDS_BYTES, e->stream, (const float*)x_dev, upk_dev,
+                       (const float*)bias_dev, (const float*)resid_dev, (float*)y_dev, n, (unsigned*)flag_dev, aux, aux_n);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int apz_wino3h_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev, void* y_dev,
+                          void* stats_dev, int n, void* flag_dev, void* stream) {
+    return launch_wino3h16_train<apz::WINO3H16_STATS, false>(e, 40, x_dev, upk_dev, bias_dev, nullptr, y_dev, n, flag_dev,
+                                                             stats_dev, 0, stream);
+}
+
+int apz_wino3h_conv_dgrad(apz_engine* e, const void* dy_dev, const void* upk_dev, const void* bias_dev, const void* add_dev,
+                          void* dx_dev, int n, const void* dymax_dev, int dymax_count, void* flag_dev, void* stream) {
+    if (dymax_count < 1) return fail(APZ_E_ARG, "bad argument");
+    void* dm = const_cast<void*>(dymax_dev);
+    if (add_dev)
+        return launch_wino3h16_train<apz::WINO3H16_DGRAD, true>(e, 41, dy_dev, upk_dev, bias_dev, add_dev, dx_dev, n, flag_dev, dm,
+                                                                dymax_count, stream);
+    return launch_wino3h16_train<apz::WINO3H16_DGRAD, false>(e, 42, dy_dev, upk_dev, bias_dev, nullptr, dx_dev, n, flag_dev, dm,
+                                                             dymax_count, stream);
+}
+
 namespace {
 int wgrad_scratch(apz_engine* e, size_t floats) {   // per-slice partial weight gradients (both weight-gradient kernels)
     if (floats > e->wgw_floats) {
@@ -1800,9 +1862,18 @@ int apz_bn_bwd_splits(apz_engine* e, int n, int C, int layout) {
 int apz_bn_bwd(apz_engine* e, const void* dy_dev, const void* x_dev, const void* out_dev, const void* mask_dev,
                const void* gamma_dev, const void* mean_dev, const void* invstd_dev, void* dx_dev, void* dres_dev, void* dgamma_dev,
                void* dbeta_dev, void* dxsum_dev, int dxsum_ld, int n, int C, int layout, int relu, void* stream) {
+    return apz_bn_bwd_max(e, dy_dev, x_dev, out_dev, mask_dev, gamma_dev, mean_dev, invstd_dev, dx_dev, dres_dev, dgamma_dev,
+                          dbeta_dev, dxsum_dev, dxsum_ld, nullptr, n, C, layout, relu, stream);
+}
+
+int apz_bn_bwd_max(apz_engine* e, const void* dy_dev, const void* x_dev, const void* out_dev, const void* mask_dev,
+                   const void* gamma_dev, const void* mean_dev, const void* invstd_dev, void* dx_dev, void* dres_dev,
+                   void* dgamma_dev, void* dbeta_dev, void* dxsum_dev, int dxsum_ld, void* dxmax_dev, int n, int C, int layout,
+                   int relu, void* stream) {
     if (!e || !dy_dev || !x_dev || !mean_dev || !invstd_dev || !dx_dev || n < 1 || C < 1 || C > 256 ||
         (relu && !out_dev && !mask_dev) || (dxsum_dev && dxsum_ld < C) || (mask_dev && layout != APZ_LAYOUT_ROWS16))
         return fail(APZ_E_ARG, "bad argument");
+    if (dxmax_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_max: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
     EngineLock guard(e->submit_lock);
@@ -1819,7 +1890,7 @@ int apz_bn_bwd(apz_engine* e, const void* dy_dev, const void* x_dev, const void*
                            (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
                            (const float*)invstd_dev, (const double*)e->bn_part, splits, (float*)dx_dev, (float*)dres_dev,
                            (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C,
-                           relu, (double)n * H * W);
+                           relu, (double)n * H * W, (float*)dxmax_dev);
     } else {
         hipLaunchKernelGGL(apz::bn_bwd_reduce_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
                            (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
@@ -1881,6 +1952,11 @@ int apz_wgrad_wino(apz_engine* e, const void* x_dev, const void* dy_dev, void* d
 
 int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
                   float rescale, void* stream) {
+    return apz_adam_step_unless(e, table_host, ntensors, lr_t, b1, b2, eps, rescale, nullptr, stream);
+}
+
+int apz_adam_step_unless(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
+                         float rescale, const void* skip_dev, void* stream) {
     if (!e || !table_host || ntensors < 1 || ntensors > 4096) return fail(APZ_E_ARG, "bad argument");
     static_assert(sizeof(apz::AdamTensor) == 48, "apz_adam_tensor layout");
     EngineLock guard(e->submit_lock);
@@ -1897,8 +1973,12 @@ int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_
     // for pageable host memory hipMemcpyAsync returns once the 6 KB have been staged, so the caller's buffer need
     // not outlive the call.  (No stream synchronisation: the optimiser step no longer drains the GPU.)
     HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(apz::adam_step_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
-                       (const apz::AdamTensor*)e->adam_tab, lr_t, b1, b2, eps, rescale);
+    if (skip_dev)
+        hipLaunchKernelGGL(apz::adam_step_unless_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
+                           (const apz::AdamTensor*)e->adam_tab, lr_t, b1, b2, eps, rescale, (const unsigned*)skip_dev);
+    else
+        hipLaunchKernelGGL(apz::adam_step_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
+                           (const apz::AdamTensor*)e->adam_tab, lr_t, b1, b2, eps, rescale);
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }

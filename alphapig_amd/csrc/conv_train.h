@@ -166,6 +166,15 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
     __syncthreads();
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
+__device__ __forceinline__ float block_max_256(float v, float* sh) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
 // the two sums of channel c over its `splits` partials, to every thread: thread k loads split k (k + 256, ...), then
 // the shuffle tree -- a fixed order
 __device__ __forceinline__ void channel_sums(const double* __restrict__ part, int c, int splits, double* sh, double& s1,
@@ -321,8 +330,8 @@ struct AdamTensor {
     float wd;
     int pad_;
 };
-__global__ __launch_bounds__(256) void adam_step_kernel(const AdamTensor* __restrict__ tab, float lr_t, float b1, float b2,
-                                                        float eps, float rescale) {
+__device__ __forceinline__ void adam_step_body(const AdamTensor* __restrict__ tab, float lr_t, float b1, float b2, float eps,
+                                               float rescale) {
     const AdamTensor T = tab[blockIdx.y];
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < T.n; i += (long long)gridDim.x * blockDim.x) {
         const float w = T.w[i];
@@ -333,6 +342,17 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamTensor* __rest
         T.v[i] = v;
         T.w[i] = w - lr_t * m / (sqrtf(v) + eps);
     }
+}
+__global__ __launch_bounds__(256) void adam_step_kernel(const AdamTensor* __restrict__ tab, float lr_t, float b1, float b2,
+                                                        float eps, float rescale) {
+    adam_step_body(tab, lr_t, b1, b2, eps, rescale);
+}
+// ... unless *skip != 0 (the overflow word of the step's f16x2 launches: the trainer repeats the step on the exact kernels,
+// and these gradients must not reach the moments)
+__global__ __launch_bounds__(256) void adam_step_unless_kernel(const AdamTensor* __restrict__ tab, float lr_t, float b1, float b2,
+                                                               float eps, float rescale, const unsigned* __restrict__ skip) {
+    if (*reinterpret_cast<const volatile unsigned*>(skip)) return;
+    adam_step_body(tab, lr_t, b1, b2, eps, rescale);
 }
 
 // ---- the same four kernels for the padded-row layout (plane = 60 float4; pad elements are zero on input, so
@@ -431,7 +451,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_r16_kernel(const float* __re
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                float* __restrict__ dxsum, int dxsum_ld,
                                                                const unsigned char* __restrict__ mask, int n, int C, int relu,
-                                                               double M) {
+                                                               double M, float* __restrict__ dxmax) {
     __shared__ double sh[4];
     const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
     double s1, s2;
@@ -443,6 +463,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_r16_kernel(const float* __re
     const float m = mean[c], is = invstd[c], k0 = (float)(s1 / M), k1 = (float)(s2 / M);
     const float gi = (gamma ? gamma[c] : 1.f) * is;
     double ds = 0.0;
+    float dm = 0.f;
     if (sub < 4)
         for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
             const size_t o = ((size_t)b * C + c) * 60 + k;
@@ -464,10 +485,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_r16_kernel(const float* __re
             reinterpret_cast<f32x4*>(dx)[o] = r;
             if (dres) reinterpret_cast<f32x4*>(dres)[o] = g;
             ds += (double)((r[0] + r[1]) + (r[2] + r[3]));
+            if (dxmax) dm = fmaxf(dm, fmaxf(fmaxf(fabsf(r[0]), fabsf(r[1])), fmaxf(fabsf(r[2]), fabsf(r[3]))));
         }
     if (dxsum) {
         ds = block_sum_256(ds, sh);
         if (t == 0) dxsum[(size_t)blockIdx.y * dxsum_ld + c] = (float)ds;
+    }
+    if (dxmax) {   // [split][C]: max |dx| of this workgroup (the input scale of trunk15_wino3h16_train_kernel's data gradient)
+        dm = block_max_256(dm, reinterpret_cast<float*>(sh));
+        if (t == 0) dxmax[(size_t)blockIdx.y * C + c] = dm;
     }
 }
 

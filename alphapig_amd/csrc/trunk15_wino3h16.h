@@ -72,11 +72,40 @@ __device__ unsigned long long apz_wino3h16_stamps[4 * 8 * 12];   // [workgroup 4
 #define APZH16_RAW_SLOT 4    /* the MFMA slot whose end requests the raw tiles of the chunk after next */
 #endif
 
-template <bool RESID, bool RELU = true>
+// FORM: WINO3H16_PLAIN is the self-play kernel (aux unused).  The training step's two forms, RELU false for both:
+//   WINO3H16_STATS  the forward in front of a BatchNorm: bias only, no residual; `aux` receives per (output channel, board)
+//                   the sum and the sum of squares of the board's 225 outputs as double [128][n][2], the contract of
+//                   trunk15_wino3_kernel<..., STATS = true> (bn_fwd(stats=...) consumes either).  A board's 225 values: the
+//                   lane's 4x4 tile row by row, its four rows, then the 16 tiles of the board (one DPP row) -- a fixed fp32
+//                   tree whatever the launch shape or the board's place in the batch.
+//   WINO3H16_DGRAD  the data gradient (flipped, transposed weights; bias zero; RESID adds the skip gradient).  Its input is
+//                   not O(1): the gradients of a mean loss sit far below the fp16 normal range, where the lo term of the
+//                   split is subnormal and carries an ABSOLUTE error of up to 2^-25.  So the launch
+//                   scales its input by 2^a, chosen on the device: `aux` holds `aux_n` partial maxima of |input| (bn_bwd's
+//                   dxmax, one per channel and batch split), every workgroup folds them (max: exact, any order), and a puts
+//                   the maximum into [2^7, 2^8) -- |V| <= 100 max <= 25 600 stays below the fp16 limit, and 22 binades
+//                   below the maximum are still normal fp16.  The raw tile values are multiplied by 2^a before the
+//                   transform, 2^-a goes into the 1 / S of the bias FMA: both exact (powers of two, no over- or underflow
+//                   for |a| <= 64).
+enum { WINO3H16_PLAIN = 0, WINO3H16_STATS = 1, WINO3H16_DGRAD = 2 };
+
+// a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as Wino3H::scale_for(0)); clamped to [-64, 64]
+__device__ __forceinline__ int wino3h16_dgrad_exponent(float m) {
+    if (!(m > 0.f)) return 0;
+    const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u);   // m in [2^(e-127), 2^(e-126)) (e = 0: subnormal)
+    const int a = 134 - e;
+    return a < -64 ? -64 : (a > 64 ? 64 : a);
+}
+
+template <bool RESID, bool RELU = true, int FORM = WINO3H16_PLAIN>
 __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __restrict__ in, const void* __restrict__ upk,
                                                                const float* __restrict__ bias, const float* __restrict__ resid,
-                                                               float* __restrict__ out, int n, unsigned* __restrict__ flag) {
+                                                               float* __restrict__ out, int n, unsigned* __restrict__ flag,
+                                                               void* __restrict__ aux, int aux_n) {
     using T = Wino3H16;
+    constexpr bool STATS = FORM == WINO3H16_STATS, DGRAD = FORM == WINO3H16_DGRAD;
+    static_assert(FORM == WINO3H16_PLAIN || !RELU, "the training forms have no ReLU");
+    static_assert(!STATS || !RESID, "STATS: bias only");
 #ifdef APZ_WINO3H_STAMPS
     // phases as trunk15_wino3h.h: 0 item prologue, 1 chunk barrier waits, 2 chunk bodies, 3 staging + stores, 4 epilogue first
     // barriers, 5 item start, 6 s_memrealtime ticks, 7 total, 8 M write + residual, 9 gather + output transform, 10 second barriers
@@ -112,6 +141,24 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     auto item_pair = [&](int t) { return pair0 + (duo ? t : (t >> 1)) * pstride; };
     auto item_half = [&](int t) { return duo ? h_fix : (t & 1); };
 
+    // DGRAD: the input scale 2^a and 2^-a from the partial maxima (the eight wave maxima pass through V[0], which the first
+    // item's transform writes only behind its barrier)
+    float xsc = 1.f, xisc = 1.f;
+    if constexpr (DGRAD) {
+        const float* pm = static_cast<const float*>(aux);
+        float m = 0.f;
+        for (int i = tid; i < aux_n; i += 512) m = fmaxf(m, fabsf(pm[i]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        if (lane == 0) lds[wave] = m;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 8; w++) m = fmaxf(m, lds[w]);
+        const int a = __builtin_amdgcn_readfirstlane(wino3h16_dgrad_exponent(m));
+        xsc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
+        xisc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
+    }
+
     const unsigned plane_b = T::GPLANE * 4;
     const unsigned act_bytes = (unsigned)n * T::C * plane_b;
     const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, act_bytes, 0x00020000);
@@ -120,6 +167,8 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_u =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)T::UPK_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_st =
+        __builtin_amdgcn_make_buffer_rsrc(STATS ? aux : out, 0, STATS ? (unsigned)n * T::C * 16u : 0u, 0x00020000);
     auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
     };
@@ -218,6 +267,10 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     auto tslice = [&](int vpar, auto KK) {
         constexpr int K = decltype(KK)::value;
         char* vp = vbase + vpar * T::V_BYTES + tv_off;
+        if constexpr (DGRAD && K == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) raw[r] *= xsc;      // exact: a power of two
+        }
         if constexpr (K < 2) vpass(K);
         else if constexpr (K >= 3) {
             constexpr int j = (K - 3) / 4, part = (K - 3) % 4;
@@ -407,7 +460,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                 if (RESID && s + 1 < 4) resid_request(s + 1);
                 const int ch = row_chan(s, co16);
                 const float bv = bias[ch];
-                const float is = bias[128 + ch];                     // 1 / S of the channel (a power of two)
+                const float is = DGRAD ? bias[128 + ch] * xisc : bias[128 + ch];   // 1 / S of the channel (a power of two)
                 float* sp = sw + (cosel * 2 + gbd) * T::SPLANE + (4 * gty) * T::SROW + 4 * gtx;
                 f32x4 y[4];
 #pragma unroll
@@ -420,6 +473,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                     y[3][ee] = __builtin_fmaf(8.f, d34, d12) + hrow[5][ee];
                 }
                 float chk = 0.f;
+                float r1[4], r2[4];                  // STATS: the row sums of the tile
 #pragma unroll
                 for (int a = 0; a < 4; a++) {
                     f32x4 v;
@@ -431,8 +485,22 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                     for (int ee = 0; ee < 4; ee++) v[ee] = RELU ? fmaxf(v[ee], 0.f) : v[ee];
                     if (gtx == 3) v[3] = 0.f;      // column 15 is the halo column of the rows16 layout
                     *reinterpret_cast<f32x4*>(sp + a * T::SROW) = v;
+                    if constexpr (STATS) {
+                        r1[a] = (v[0] + v[1]) + (v[2] + v[3]);
+                        r2[a] = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+                    }
                 }
                 nonfinite |= ((chk - chk) != 0.f) ? 1u : 0u;         // 0 for every finite sum; NaN != 0 is true
+                if constexpr (STATS) {
+                    if (gty == 3) r1[3] = 0.f, r2[3] = 0.f;          // board row 15 does not exist
+                    // the 16 tiles of this (channel, board) are one DPP row: lanes 16 (2 cosel + gbd) .. + 15
+                    const double d1 = (double)wino3_row16_sum((r1[0] + r1[1]) + (r1[2] + r1[3]));
+                    const double d2 = (double)wino3_row16_sum((r2[0] + r2[1]) + (r2[2] + r2[3]));
+                    const bool mine = gtile == 0 && (gbd == 0 || two);
+                    typedef double f64x2 __attribute__((ext_vector_type(2)));
+                    const unsigned so = (unsigned)(ch * n + bd0 + gbd) * 16u;
+                    bstore(r_st, mine ? so : 0x80000000u, 0u, __builtin_bit_cast(f32x4, f64x2{d1, d2}));
+                }
             }
             APZH16_STAMP(9)
             wave_lds_fence();

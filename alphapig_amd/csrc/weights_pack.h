@@ -106,21 +106,15 @@ __global__ void pack_wino3b_folded_kernel(const float* __restrict__ w, const dou
         }
 }
 
-// The same U for trunk15_wino3h.h: one workgroup per output channel (thread = input channel) finds max |U| of the channel,
-// S = Wino3H::scale_for(max), and writes U S as two fp16 terms (both round to nearest even, the remainder in double) at
-// L::upk_offset (L = Wino3H, or Wino3H16 of trunk15_wino3h16.h); bias3h = [128 folded biases][128 x 1 / S].  Launch: grid
-// 128, block 128.
+// The U of kernel g (one output channel co, thread = input channel ci of a 128-thread workgroup) for the fp16 x 2 kernels:
+// max |U| of the channel over the workgroup, S = Wino3H::scale_for(max), U S as two fp16 terms (both round to nearest even,
+// the remainder in double) at L::upk_offset; bias3h[co] = bias, bias3h[128 + co] = 1 / S
 template <class L>
-__global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const double* __restrict__ scale, const double* __restrict__ shift,
-                                          unsigned short* __restrict__ up, float* __restrict__ bias3h) {
-    const int co = blockIdx.x, ci = threadIdx.x;
+__device__ __forceinline__ void pack_wino3h_channel(const double (&g)[3][3], int co, int ci, double bias, unsigned short* __restrict__ up,
+                                                    float* __restrict__ bias3h) {
     const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    double g[3][3], t[6][3], u[36];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
+    double t[6][3], u[36];
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -142,7 +136,7 @@ __global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const dou
     }
     const float S = Wino3H::scale_for(red[0]);
     if (ci == 0) {
-        bias3h[co] = (float)shift[co];
+        bias3h[co] = (float)bias;
         bias3h[128 + co] = 1.f / S;
     }
 #pragma unroll
@@ -153,6 +147,41 @@ __global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const dou
         up[L::upk_offset(co, ci, pos, 0) / 2] = __builtin_bit_cast(unsigned short, hi);
         up[L::upk_offset(co, ci, pos, 1) / 2] = __builtin_bit_cast(unsigned short, lo);
     }
+}
+
+// The same U for trunk15_wino3h.h: one workgroup per output channel (thread = input channel), the BatchNorm folded in
+// (L = Wino3H, or Wino3H16 of trunk15_wino3h16.h); bias3h = [128 folded biases][128 x 1 / S].  Launch: grid 128, block 128.
+template <class L>
+__global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const double* __restrict__ scale, const double* __restrict__ shift,
+                                          unsigned short* __restrict__ up, float* __restrict__ bias3h) {
+    const int co = blockIdx.x, ci = threadIdx.x;
+    double g[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
+    pack_wino3h_channel<L>(g, co, ci, shift[co], up, bias3h);
+}
+
+// The training step's weights for trunk15_wino3h16_train_kernel, no BatchNorm fold: `count` layers whose fp32 weights sit
+// back to back ([count][128][128][3][3]), each for the forward (bias b[layer], may be NULL: zero) and the data gradient
+// (W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], bias zero; S per output channel of W', i.e. per input channel of the forward),
+// in one launch: up [count][2][UPK_BYTES], bias3h [count][2][256].  flag (may be NULL) is zeroed: the overflow word of the
+// step these weights serve.  Launch: grid (128, 2 count), block 128.
+__global__ void pack_wino3h16_many_kernel(const float* __restrict__ w, const float* __restrict__ b, unsigned short* __restrict__ up,
+                                          float* __restrict__ bias3h, unsigned* __restrict__ flag) {
+    const int co = blockIdx.x, ci = threadIdx.x, layer = blockIdx.y >> 1, flip = blockIdx.y & 1;
+    const float* wl = w + (size_t)layer * (128 * 128 * 9);
+    double g[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            g[a][c] = flip ? (double)wl[((size_t)ci * 128 + co) * 9 + (2 - a) * 3 + (2 - c)] : (double)wl[((size_t)co * 128 + ci) * 9 + a * 3 + c];
+    const double bias = (!flip && b) ? (double)b[(size_t)layer * 128 + co] : 0.0;
+    pack_wino3h_channel<Wino3H16>(g, co, ci, bias, up + (size_t)blockIdx.y * (Wino3H16::UPK_BYTES / 2),
+                                  bias3h + (size_t)blockIdx.y * Wino3H16::BIAS_FLOATS);
+    if (flag && blockIdx.x == 0 && blockIdx.y == 0 && ci == 0) *flag = 0u;
 }
 
 // heads: rows [row0, row0 + rows) of the [6][C] matrix of both 1x1 convolutions, and their folded biases

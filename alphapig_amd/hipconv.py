@@ -86,6 +86,56 @@ def wino_pack_many(weights, out=None):
     return out
 
 
+def wino3h_pack_many(weights, biases=None, out=None, flag=None):
+    """The training step's trunk weights for the f16x2 kernel: weights [count][128][128][3][3] and biases [count][128] (None:
+    zero), one contiguous float32 device tensor each -> (upk [count][2][apz_wino3h_packed_size()], bias [count][2][256])
+    for the forward ([:, 0]) and the data gradient ([:, 1]), one launch.  out: such a pair to fill again; flag: a device
+    int32 word the launch zeroes (the overflow word of the step that follows)."""
+    torch = _torch()
+    if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and
+            tuple(weights.shape[1:]) == (128, 128, 3, 3)):
+        raise ValueError("wino3h_pack_many takes a contiguous float32 device tensor [count][128][128][3][3]")
+    count = int(weights.shape[0])
+    if biases is not None and not (biases.is_contiguous() and biases.dtype == torch.float32 and tuple(biases.shape) == (count, 128)):
+        raise ValueError("biases: a contiguous float32 [count][128] tensor")
+    L = _native.hip()
+    hnd = _engine(15, 15, weights.device.index or 0)
+    if out is None:
+        out = (_empty((count, 2, L.apz_wino3h_packed_size()), weights), _empty((count, 2, 256), weights))
+    stream = C.c_void_p(torch.cuda.current_stream(weights.device).cuda_stream)
+    _ck(L, L.apz_wino3h_pack_many(hnd, weights.data_ptr(), _ptr(biases), count, out[0].data_ptr(), out[1].data_ptr(), _ptr(flag),
+                                  stream))
+    return out
+
+
+def conv3x3_fwd_stats_f16x2(x, upk, bias, flag):
+    """conv3x3_fwd_stats on the f16x2 kernel: upk / bias = one layer's forward pair of wino3h_pack_many.  -> (y, stats);
+    a non-finite output sets the int32 device word `flag` to 1."""
+    torch = _torch()
+    L, hnd, stream = _ctx(x, ROWS16)
+    if tuple(x.shape[1:]) != (128, 15, 16):
+        raise ValueError("conv3x3_fwd_stats_f16x2: the 128-channel trunk in the padded-row layout")
+    n = int(x.shape[0])
+    y = _empty(tuple(x.shape), x)
+    stats = torch.empty((128, n, 2), dtype=torch.float64, device=x.device)
+    _ck(L, L.apz_wino3h_conv_stats(hnd, x.data_ptr(), upk.data_ptr(), bias.data_ptr(), y.data_ptr(), stats.data_ptr(), n,
+                                   flag.data_ptr(), stream))
+    return y, stats
+
+
+def conv3x3_dgrad_f16x2(dy, upk, bias, dymax, flag, add=None):
+    """conv3x3_dgrad on the f16x2 kernel (padded rows): upk / bias = one layer's data-gradient pair of wino3h_pack_many;
+    dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two input scale); (+ add)."""
+    L, hnd, stream = _ctx(dy, ROWS16)
+    if tuple(dy.shape[1:]) != (128, 15, 16) or (add is not None and add.shape != dy.shape):
+        raise ValueError("conv3x3_dgrad_f16x2: the 128-channel trunk in the padded-row layout")
+    n = int(dy.shape[0])
+    dx = _empty(tuple(dy.shape), dy)
+    _ck(L, L.apz_wino3h_conv_dgrad(hnd, dy.data_ptr(), upk.data_ptr(), bias.data_ptr(), _ptr(add), dx.data_ptr(), n,
+                                   dymax.data_ptr(), int(dymax.numel()), flag.data_ptr(), stream))
+    return dx
+
+
 def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     """conv(x, W) (flip: the data-gradient convolution with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]) + bias + resid.
     upk: the layer's transformed weights in that orientation when the caller packed them already (wino_pack_many)."""
@@ -205,11 +255,13 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, resid=None, relu=True, layout=DENS
     return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
 
 
-def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DENSE, dxsum=None, mask=None):
+def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DENSE, dxsum=None, mask=None, dxmax=None):
     """-> (dx, dres or None, dgamma, dbeta); y is the forward output (the ReLU mask) -- or None when mask (bn_fwd's
     want_mask result) carries the ReLU decisions.
     dxsum: a [bn_bwd_splits(x, layout)][C] view (row stride >= C) of a float32 matrix that receives the per-split column
-    sums of dx -- colsum() of it is the bias gradient of the convolution in front (bias_parts() hands such views out)."""
+    sums of dx -- colsum() of it is the bias gradient of the convolution in front (bias_parts() hands such views out).
+    dxmax (padded rows): a contiguous float32 [bn_bwd_splits(x, layout)][C] tensor that receives max |dx| per split and
+    channel (conv3x3_dgrad_f16x2's dymax)."""
     L, hnd, stream = _ctx(x, layout)
     n, c = int(x.shape[0]), int(x.shape[1])
     dx = _empty(tuple(x.shape), x)
@@ -222,9 +274,16 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
         ld = int(dxsum.stride(0))
     if mask is not None and (tuple(mask.shape) != (n, c, 60) or mask.dtype != _torch().uint8 or not mask.is_contiguous()):
         raise ValueError("mask: contiguous uint8 [n][C][60]")
-    _ck(L, L.apz_bn_bwd(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
-                        dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, n, c, layout, int(relu),
-                        stream))
+    if dxmax is None:
+        _ck(L, L.apz_bn_bwd(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
+                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, n, c, layout, int(relu),
+                            stream))
+        return dx, dres, dgamma, dbeta
+    if tuple(dxmax.shape) != (bn_bwd_splits(x, layout), c) or not dxmax.is_contiguous() or dxmax.dtype != _torch().float32:
+        raise ValueError("dxmax: a contiguous float32 [splits][C] tensor")
+    _ck(L, L.apz_bn_bwd_max(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
+                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, dxmax.data_ptr(), n, c,
+                            layout, int(relu), stream))
     return dx, dres, dgamma, dbeta
 
 
@@ -328,17 +387,17 @@ def dropout(x, keep, seed, step):
     return y
 
 
-def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False):
+def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=None):
     """The reference's loss head (policy_value_net_mxnet.py:180-193) on [n][H*W] logits and [n] value logits.
     -> dict with loss3 = (value loss, policy loss, entropy) [device, 3 floats], dlogits, dvlogit (grads),
-    probs, values (outputs)."""
+    probs, values (outputs).  loss3: a contiguous float32 device tensor of 3 to write the losses into."""
     L, _, stream = _ctx2(logits)
     n, hw = int(logits.shape[0]), int(logits.shape[1])
     side = int(round(hw ** 0.5))
     hnd = _engine(side, side, logits.device.index or 0)
     out = {}
     if pi is not None:
-        out["loss3"] = _empty((3,), logits)
+        out["loss3"] = _empty((3,), logits) if loss3 is None else loss3
         if grads:
             out["dlogits"], out["dvlogit"] = _empty((n, hw), logits), _empty((n,), logits)
     if outputs:
@@ -366,8 +425,9 @@ def from_rows16(x):
 
 
 # ---- Adam -----------------------------------------------------------------------------------------------------------
-def adam_step(entries, lr_t, b1, b2, eps, rescale, device):
-    """One launch over all tensors.  entries: [(w, grad, m, v, wd)] of float32 device tensors (apz_adam_step)."""
+def adam_step(entries, lr_t, b1, b2, eps, rescale, device, skip=None):
+    """One launch over all tensors.  entries: [(w, grad, m, v, wd)] of float32 device tensors (apz_adam_step).  skip: a
+    device int32 word; when it is not zero at the time the launch runs, nothing is updated (apz_adam_step_unless)."""
     import numpy as np
     torch = _torch()
     tab = np.zeros(len(entries), dtype=[("w", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("n", "i8"), ("wd", "f4"),
@@ -379,4 +439,8 @@ def adam_step(entries, lr_t, b1, b2, eps, rescale, device):
     L = _native.hip()
     hnd = _any_engine(device.index or 0)
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    _ck(L, L.apz_adam_step(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, stream))
+    if skip is None:
+        _ck(L, L.apz_adam_step(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, stream))
+    else:
+        _ck(L, L.apz_adam_step_unless(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, skip.data_ptr(),
+                                      stream))

@@ -131,6 +131,10 @@ class TrainPipeline(object):
         # 12 % of the wall clock and ends at 277 k leaf evaluations/s against 305 k interleaved: interleaving wins on
         # throughput; the switch is for jobs that want the shortest update latency.
         self.exclusive_updates = bool(conf.get("exclusive_updates", False))
+        # train_arith: the trainer's trunk arithmetic (HipTrainer's trunk_arith): "f32" (default) or "f16x2"
+        self.train_arith = conf.get("train_arith", "f32")
+        if self.train_arith not in ("f32", "f16x2"):
+            raise ValueError("train_arith must be 'f32' or 'f16x2', not %r" % (self.train_arith,))
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -233,8 +237,14 @@ class TrainPipeline(object):
         if getattr(net, "_trainer", None) is None:
             # a re-created trainer (set_params dropped the old one) continues the dropout mask sequence instead of replaying it
             net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
-                                      device_index=net._device, seed=self._seed, dropout_step0=self._train_steps)
+                                      device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
+                                      trunk_arith=self.train_arith)
         return net._trainer
+
+    def _note_overflows(self, rec, trainer):
+        """train_arith f16x2: the update record carries the trainer's count of steps repeated on the exact kernels"""
+        if self.train_arith == "f16x2":
+            rec["trunk_overflows"] = int(getattr(trainer, "trunk_overflows", 0))
 
     def policy_update(self, trainer=None, kl_net=None):
         """train_mxnet.py:194-240 (rank 0 of a multi-rank run; see `_exchange_update` / `_trainer_main`).  Lock step: the
@@ -260,11 +270,13 @@ class TrainPipeline(object):
         if not self.distributed:
             if do:
                 rec["loss"], rec["entropy"], rec["kl"] = self.policy_update()
+                self._note_overflows(rec, self._trainer())
             return
         head = [0.0, 0.0, 0.0, 0.0, self.lr_multiplier]
         if do:
             loss, entropy, kl = self.policy_update()
             head = [1.0, loss, entropy, kl, self.lr_multiplier]
+            self._note_overflows(rec, self._trainer())
         head = dist.broadcast_floats(head, src=0)
         if head[0] == 0.0:
             return
@@ -382,7 +394,7 @@ class TrainPipeline(object):
             with ctx:
                 if trainer is None:
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
-                                         device_index=net._device, seed=self._seed)
+                                         device_index=net._device, seed=self._seed, trunk_arith=self.train_arith)
                 self._async_trainer = trainer
                 games_recv = 0
                 busy_until = 0.0
@@ -410,6 +422,7 @@ class TrainPipeline(object):
                             self._last = (loss, entropy, kl)
                             self._fresh = (self.updates_done, snap)
                         rec.update(loss=loss, entropy=entropy, kl=kl)
+                        self._note_overflows(rec, trainer)
                     self._schedule_after_batch(i, rec, kl_net)
                     with self._lock:
                         self.trainer_history.append(rec)
@@ -458,6 +471,7 @@ class TrainPipeline(object):
                             self._last = (loss, entropy, kl)
                             self._fresh = (self.updates_done, snap)
                         rec.update(loss=loss, entropy=entropy, kl=kl)
+                        self._note_overflows(rec, trainer)
                     self._schedule_after_batch(batches_done - 1, rec, kl_net, first=first)
                     with self._lock:
                         self.trainer_history.append(rec)

@@ -36,11 +36,21 @@ DeviceBatch = collections.namedtuple("DeviceBatch", "states pis zs")     # HipTr
 
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
-                 seed=0, height=None, width=None, dropout_step0=0):
+                 seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32"):
         """params: name -> array, in any order.  height / width: the board (default: square, from the policy head's size).
         seed / dropout_step0: the dropout masks are a stateless hash of (seed, dropout_step0 + step, element) -- a trainer
         that is re-created (set_params, a resumed checkpoint) or one of several ranks passes its own seed / the steps
-        already taken, or it replays the mask sequence of a fresh trainer."""
+        already taken, or it replays the mask sequence of a fresh trainer.
+        trunk_arith: "f32" (default) runs the padded-row trunk's forward and data gradient on the exact fp32 Winograd
+        kernel; "f16x2" on the two-term fp16 kernel of the self-play path (trunk15_wino3h16.h: the forward with the
+        BatchNorm statistics in its epilogue, the data gradient with a power-of-two input scale chosen on the device),
+        at every batch size -- the weight gradient, the stem and the heads stay as they are.  A step in which an f16x2
+        launch leaves the fp16 range is taken again on the exact kernels (trunk_overflows counts them) and ends
+        bit-identical to the "f32" trainer's step.  Only the 15x15, 128-filter residual trunk has the f16x2 form:
+        other nets raise ValueError.  (profiles/r07_train_f16x2.md: 0.86 of the "f32" step time at batch 512, but
+        only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)"""
+        if trunk_arith not in ("f32", "f16x2"):
+            raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
         import torch
         from . import _native, hipconv
         if not torch.cuda.is_available():
@@ -92,6 +102,32 @@ class HipTrainer(object):
             for j, k in enumerate(self._trunk_names):
                 self._trunk_w[j].copy_(self.p[k])
                 self.p[k] = self._trunk_w[j]
+        self.trunk_arith = trunk_arith
+        self.trunk_overflows = 0       # f16x2: steps (and loss_and_grads calls) repeated on the exact kernels
+        self._fast = False             # the pass being queued runs its trunk on the f16x2 kernel
+        if trunk_arith == "f16x2":
+            if not self.rows16:
+                raise ValueError("trunk_arith='f16x2' needs the 15x15 residual trunk of 128 filters (net_kind %r, %dx%d)" %
+                                 (net_kind, self.side, self.side))
+            # the trunk biases back to back as well (wino3h_pack_many packs them with the weights), the moving statistics in
+            # one buffer (one copy snapshots them at the start of a step: a repeated step must not move them twice), and
+            # a word after the step's three losses: the overflow word, read with the losses in ONE device -> host copy
+            self._trunk_b = torch.empty((len(self._trunk_names), 128), dtype=torch.float32, device=self.device)
+            for j, k in enumerate(self._trunk_names):
+                kb = k[:-len("_weight")] + "_bias"
+                self._trunk_b[j].copy_(self.p[kb])
+                self.p[kb] = self._trunk_b[j]
+            self._stat_buf = torch.empty((sum(self.p[k].numel() for k in self.stat_names),), dtype=torch.float32, device=self.device)
+            off = 0
+            for k in self.stat_names:
+                v = self._stat_buf[off:off + self.p[k].numel()].view(self.p[k].shape)
+                v.copy_(self.p[k])
+                self.p[k] = v
+                off += v.numel()
+            self._stat_snap = torch.empty_like(self._stat_buf)
+            self._word = torch.zeros((4,), dtype=torch.float32, device=self.device)   # [loss3][overflow word]
+            self._flag = self._word[3:]
+            self._u16 = None
         self._eval = None
         self._eval_t = -1
         self.tape = None
@@ -131,17 +167,22 @@ class HipTrainer(object):
             x, rec = self._conv_act_fwd(states, "res_conv1", o.DENSE)
             tape["stem"] = rec
             lay = o.ROWS16 if self.rows16 else o.DENSE
-            upk = None
+            upk = u16 = None
             if self.rows16:
                 x = o.to_rows16(x)
-                self._upk = upk = o.wino_pack_many(self._trunk_w, self._upk)
-            tape["upk"] = upk
+                if self._fast:          # (the pack launch zeroes the step's overflow word)
+                    self._u16 = u16 = o.wino3h_pack_many(self._trunk_w, self._trunk_b, self._u16, self._flag)
+                else:
+                    self._upk = upk = o.wino_pack_many(self._trunk_w, self._upk)
+            tape["upk"], tape["u16"] = upk, u16
             for i in range(1, self.n_blocks + 1):
                 A, B = "A%d" % i, "B%d" % i
                 ua, ub = (upk[2 * i - 2, 0], upk[2 * i - 1, 0]) if upk is not None else (None, None)
                 sa = sb = None
                 fused = upk is not None and int(x.shape[0]) <= 16384       # (apz_wino_conv_stats: one launch)
-                if fused:               # the Winograd kernel's epilogue leaves the BatchNorm's per-board sums: no statistics pass
+                if u16 is not None:     # the same contract on the f16x2 kernel
+                    ya, sa = o.conv3x3_fwd_stats_f16x2(x, u16[0][2 * i - 2, 0], u16[1][2 * i - 2, 0], self._flag)
+                elif fused:             # the Winograd kernel's epilogue leaves the BatchNorm's per-board sums: no statistics pass
                     ya, sa = o.conv3x3_fwd_stats(x, p["conv" + A + "_weight"], p["conv" + A + "_bias"], upk=ua)
                 else:
                     ya = o.conv3x3_fwd(x, p["conv" + A + "_weight"], p["conv" + A + "_bias"], lay, upk=ua)
@@ -149,7 +190,9 @@ class HipTrainer(object):
                 ha, ma, ia, *ka = o.bn_fwd(ya, p["bn" + A + "_gamma"], p["bn" + A + "_beta"], p["bn" + A + "_moving_mean"],
                                            p["bn" + A + "_moving_var"], None, True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sa,
                                            want_mask=wm)
-                if fused:
+                if u16 is not None:
+                    yb, sb = o.conv3x3_fwd_stats_f16x2(ha, u16[0][2 * i - 1, 0], u16[1][2 * i - 1, 0], self._flag)
+                elif fused:
                     yb, sb = o.conv3x3_fwd_stats(ha, p["conv" + B + "_weight"], p["conv" + B + "_bias"], upk=ub)
                 else:
                     yb = o.conv3x3_fwd(ha, p["conv" + B + "_weight"], p["conv" + B + "_bias"], lay, upk=ub)
@@ -199,25 +242,36 @@ class HipTrainer(object):
         dx, g["conv3_1_1_weight"], g["conv3_1_1_bias"], g["conv3_2_1_weight"], g["conv3_2_1_bias"] = o.conv1x1_bwd_pair(
             xh, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"][6])
         if self.kind == "resnet":
-            upk = tape.get("upk")
+            upk, u16 = tape.get("upk"), tape.get("u16")
             # the trunk convolutions' bias gradients = column sums of the dx their BatchNorms hand back: every bn_bwd
             # leaves its per-split sums in its own columns of ONE matrix, added after the loop in one launch
             nb = self.n_blocks
             nf = int(tape["blocks"][0][1].shape[1]) if nb else 0
             parts = o._empty((o.bn_bwd_splits(tape["blocks"][0][1], lay), 2 * nb * nf), dx) if nb else None
+            # f16x2: each bn_bwd also leaves max |dx| per split and channel, which the data-gradient launch right behind it
+            # folds into its input scale (one buffer: every pair runs in stream order)
+            dmax = o._empty((parts.shape[0], nf), dx) if (u16 is not None and nb) else None
             for i in range(nb, 0, -1):
                 A, B = "A%d" % i, "B%d" % i
                 x, ya, ha, ma, ia, yb, out, mb, ib, ka, kb = tape["blocks"][i - 1]
                 ua, ub = (upk[2 * i - 2, 1], upk[2 * i - 1, 1]) if upk is not None else (None, None)
                 ca, cb = (2 * i - 2) * nf, (2 * i - 1) * nf
                 dyb, dskip, g["bn" + B + "_gamma"], g["bn" + B + "_beta"] = o.bn_bwd(dx, yb, out, p["bn" + B + "_gamma"], mb, ib,
-                                                                                    True, True, lay, dxsum=parts[:, cb:cb + nf], mask=kb)
+                                                                                    True, True, lay, dxsum=parts[:, cb:cb + nf], mask=kb,
+                                                                                    dxmax=dmax)
                 g["conv" + B + "_weight"] = o.conv3x3_wgrad(ha, dyb, lay)
-                dha = o.conv3x3_dgrad(dyb, p["conv" + B + "_weight"], lay, upk=ub)
+                if u16 is not None:
+                    dha = o.conv3x3_dgrad_f16x2(dyb, u16[0][2 * i - 1, 1], u16[1][2 * i - 1, 1], dmax, self._flag)
+                else:
+                    dha = o.conv3x3_dgrad(dyb, p["conv" + B + "_weight"], lay, upk=ub)
                 dya, _, g["bn" + A + "_gamma"], g["bn" + A + "_beta"] = o.bn_bwd(dha, ya, ha, p["bn" + A + "_gamma"], ma, ia,
-                                                                                True, False, lay, dxsum=parts[:, ca:ca + nf], mask=ka)
+                                                                                True, False, lay, dxsum=parts[:, ca:ca + nf], mask=ka,
+                                                                                dxmax=dmax)
                 g["conv" + A + "_weight"] = o.conv3x3_wgrad(x, dya, lay)
-                dx = o.conv3x3_dgrad(dya, p["conv" + A + "_weight"], lay, add=dskip, upk=ua)   # trunk + skip gradients meet
+                if u16 is not None:
+                    dx = o.conv3x3_dgrad_f16x2(dya, u16[0][2 * i - 2, 1], u16[1][2 * i - 2, 1], dmax, self._flag, add=dskip)
+                else:
+                    dx = o.conv3x3_dgrad(dya, p["conv" + A + "_weight"], lay, add=dskip, upk=ua)   # trunk + skip gradients meet
             db = o.colsum(parts) if nb else None
             for i in range(1, nb + 1):
                 g["convA%d_bias" % i] = db[(2 * i - 2) * nf:(2 * i - 1) * nf]
@@ -244,18 +298,42 @@ class HipTrainer(object):
     def loss_and_grads(self, state_batch, mcts_probs=None, winner_batch=None, keep_tape=False):
         """Forward + backward in training mode (moving statistics are updated).  -> (loss3 device tensor =
         (value loss, policy loss, entropy)); the gradients of the MEAN loss land in self.grad.  keep_tape: hold on to
-        the saved activations afterwards (relu_masks(); tests).  state_batch: host array, or upload()'s DeviceBatch."""
+        the saved activations afterwards (relu_masks(); tests).  state_batch: host array, or upload()'s DeviceBatch.
+        trunk_arith "f16x2": the call reads the overflow word (a synchronisation) and repeats itself on the exact kernels
+        when it is set (train_step does the same without the extra synchronisation)."""
+        if self.trunk_arith == "f32":
+            return self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
+        if not isinstance(state_batch, DeviceBatch):
+            state_batch = self.upload(state_batch, mcts_probs, winner_batch)
+        self._stat_snap.copy_(self._stat_buf)
+        loss3 = self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True)
+        if int(self._flag.view(self.torch.int32).item()) == 0:
+            return loss3
+        self._repeat_exact()
+        return self._loss_and_grads(state_batch, keep_tape=keep_tape)
+
+    def _loss_and_grads(self, state_batch, mcts_probs=None, winner_batch=None, keep_tape=False, fast=False, loss3=None):
         if isinstance(state_batch, DeviceBatch):
             states, pis, zs = state_batch
         else:
             states, pis, zs = self.upload(state_batch, mcts_probs, winner_batch)
         self.grad = {}
-        logits, vlogit, tape = self._forward(states, self.t)
-        tape["step"] = self.t
-        out = self.ops.pv_loss(logits, vlogit, pis, zs, grads=True)
-        self._backward(tape, out["dlogits"], out["dvlogit"])
+        self._fast = fast
+        try:
+            logits, vlogit, tape = self._forward(states, self.t)
+            tape["step"] = self.t
+            out = self.ops.pv_loss(logits, vlogit, pis, zs, grads=True, loss3=loss3)
+            self._backward(tape, out["dlogits"], out["dvlogit"])
+        finally:
+            self._fast = False
         self.tape = tape if keep_tape else None
         return out["loss3"]
+
+    def _repeat_exact(self):
+        """An f16x2 launch of the pass just queued left the fp16 range: its gradients never reached Adam; the moving
+        statistics go back to their values at the start of the step, which is then taken again on the exact kernels."""
+        self.trunk_overflows += 1
+        self._stat_buf.copy_(self._stat_snap)
 
     def relu_masks(self):
         """{layer: [n][C][H][W] bool} -- which activations of the kept forward pass were positive.  (A comparator that
@@ -274,15 +352,30 @@ class HipTrainer(object):
     def train_step(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape=False):
         """One optimiser step -> (loss, entropy).  state_batch may be upload()'s DeviceBatch (mcts_probs / winner_batch are
         then ignored)."""
-        loss3 = self.loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
+        if self.trunk_arith == "f16x2":
+            if not isinstance(state_batch, DeviceBatch):
+                state_batch = self.upload(state_batch, mcts_probs, winner_batch)
+            self._stat_snap.copy_(self._stat_buf)
+            self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True, loss3=self._word[:3])
+            self.t += 1
+            self._adam(learning_rate, skip=self._flag)      # skipped on the device when the overflow word is set
+            w4 = self._word.cpu().numpy()      # the losses and the overflow word: still the step's only synchronisation
+            if w4[3:].view(np.uint32)[0] == 0:
+                return float(w4[0] + w4[1]), float(w4[2])
+            self.t -= 1
+            self._repeat_exact()
+        loss3 = self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
         self.t += 1
+        self._adam(learning_rate)
+        l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
+        return float(l3[0] + l3[1]), float(l3[2])
+
+    def _adam(self, learning_rate, skip=None):
         b1, b2, eps = 0.9, 0.999, 1e-8
         lr_t = learning_rate * (1.0 - b2 ** self.t) ** 0.5 / (1.0 - b1 ** self.t)
         entries = [(self.p[k], self.grad[k], self.m[k], self.v[k], self.wd if k.endswith(("_weight", "_gamma")) else 0.0)
                    for k in self.train_names]
-        self.ops.adam_step(entries, lr_t, b1, b2, eps, 1.0 / self.batch_size, self.device)
-        l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
-        return float(l3[0] + l3[1]), float(l3[2])
+        self.ops.adam_step(entries, lr_t, b1, b2, eps, 1.0 / self.batch_size, self.device, skip=skip)
 
     def sync_evaluator(self, net):
         """Give `net` (a PolicyValueNet of the same architecture) this trainer's current weights, device to device:

@@ -175,6 +175,28 @@ int apz_wino_conv_add(apz_engine *e, const void *x_dev, const void *upk_dev, con
  * ReLU decisions from it instead of from the 16-times-larger y. */
 int apz_wino_conv_stats(apz_engine *e, const void *x_dev, const void *upk_dev, const void *bias_dev, void *y_dev,
                         void *stats_dev, int n, void *stream);
+/* The training step's trunk on the f16x2 kernel (trunk15_wino3h16.h; HipTrainer(trunk_arith="f16x2")).
+ *   apz_wino3h_pack_many   w_dev [count][128][128][3][3] fp32, b_dev [count][128] (NULL: zero) -> upk_dev
+ *                          [count][2][apz_wino3h_packed_size() floats] and bias_dev [count][2][256] floats (forward, data
+ *                          gradient), U in double, no BatchNorm fold: per output channel S = 2^k, U S as two fp16 terms,
+ *                          bias = [128 biases (the data gradient's: 0)][128 x 1 / S].  flag_dev (NULL: none): a 32-bit
+ *                          word zeroed by this launch.
+ *   apz_wino3h_conv_stats  apz_wino_conv_stats' contract (y [n][128][15][16] = conv + bias, stats_dev double [128][n][2])
+ *                          on the f16x2 kernel; a non-finite output sets *flag_dev = 1 (the step is then repeated on the
+ *                          exact kernels).
+ *   apz_wino3h_conv_dgrad  dx = conv(dy, W') (+ add_dev; NULL: none), every tensor [n][128][15][16]; dymax_dev: dymax_count
+ *                          partial maxima of |dy| (apz_bn_bwd_max's dxmax) -- the launch scales dy by 2^a with the maximum
+ *                          in [2^7, 2^8) before the fp16 split; flag_dev as above.
+ *   apz_bn_bwd_max         apz_bn_bwd (padded-row layout) + dxmax_dev [apz_bn_bwd_splits(n, C, layout)][C] floats: max |dx|
+ *                          per batch split and channel.
+ *   apz_adam_step_unless   apz_adam_step, skipped on the device when the 32-bit word at skip_dev is not zero. */
+int64_t apz_wino3h_packed_size(void);
+int apz_wino3h_pack_many(apz_engine *e, const void *w_dev, const void *b_dev, int count, void *upk_dev, void *bias_dev,
+                         void *flag_dev, void *stream);
+int apz_wino3h_conv_stats(apz_engine *e, const void *x_dev, const void *upk_dev, const void *bias_dev, void *y_dev,
+                          void *stats_dev, int n, void *flag_dev, void *stream);
+int apz_wino3h_conv_dgrad(apz_engine *e, const void *dy_dev, const void *upk_dev, const void *bias_dev, const void *add_dev,
+                          void *dx_dev, int n, const void *dymax_dev, int dymax_count, void *flag_dev, void *stream);
 int apz_bn_fwd_stats(apz_engine *e, const void *x_dev, const void *resid_dev, const void *gamma_dev,
                      const void *beta_dev, void *run_mean_dev, void *run_var_dev, void *y_dev, void *mean_dev,
                      void *invstd_dev, const void *stats_dev, void *mask_dev, int n, int C, int layout, int relu,
@@ -214,6 +236,12 @@ int apz_bn_bwd(apz_engine *e, const void *dy_dev, const void *x_dev, const void 
                const void *gamma_dev, const void *mean_dev, const void *invstd_dev, void *dx_dev,
                void *dres_dev, void *dgamma_dev, void *dbeta_dev, void *dxsum_dev, int dxsum_ld, int n, int C,
                int layout, int relu, void *stream);
+int apz_bn_bwd_max(apz_engine *e, const void *dy_dev, const void *x_dev, const void *out_dev, const void *mask_dev,
+                   const void *gamma_dev, const void *mean_dev, const void *invstd_dev, void *dx_dev, void *dres_dev,
+                   void *dgamma_dev, void *dbeta_dev, void *dxsum_dev, int dxsum_ld, void *dxmax_dev, int n, int C,
+                   int layout, int relu, void *stream);
+int apz_adam_step_unless(apz_engine *e, const void *table_host, int ntensors, float lr_t, float b1, float b2,
+                         float eps, float rescale, const void *skip_dev, void *stream);
 int apz_bn_bwd_splits(apz_engine *e, int n, int C, int layout);
 int apz_colsum(apz_engine *e, const void *in_dev, void *out_dev, int rows, int cols, float scale, void *stream);
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training-step timing on the GPU box: the product trainer (alphapig_amd/train.py, every operator a HIP kernel of
 this repository) beside the same graph in PyTorch (MIOpen convolutions; tests/torch_trainer.py, the comparator the
-trainer is tested against), 10-block net, 15x15."""
+trainer is tested against), 10-block net, 15x15.  --arith f32,f16x2: the product trainer with each trunk arithmetic
+(HipTrainer trunk_arith), the two alternating --reps times on the same box, step times side by side."""
 import argparse
 import json
 import os
@@ -24,10 +25,14 @@ def main():
     ap.add_argument("--batches", default="128,512")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--arith", default=None, help="comma list of HipTrainer trunk arithmetics (f32,f16x2): alternating runs")
+    ap.add_argument("--reps", type=int, default=3, help="--arith: alternating repetitions")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
     out = {}
+    if args.arith:
+        return arith_ab(args, prm, rs)
     for B in [int(x) for x in args.batches.split(",")]:
         states = (rs.rand(B, 9, 15, 15) > 0.7).astype(np.float32)
         pis = rs.dirichlet(np.ones(225), size=B).astype(np.float32)
@@ -61,6 +66,42 @@ def main():
                 out["B%d_hip_resident_batch" % B] = {"ms_per_step": ms}
                 print("batch %4d  hip     %.2f ms/step on an uploaded mini-batch (HipTrainer.upload: policy_update's epochs share one)" %
                       (B, ms), flush=True)
+    print(json.dumps(out))
+
+
+def arith_ab(args, prm, rs):
+    """Both trunk arithmetics per batch size, alternating: one trainer each, `--reps` rounds of (warm-up step, `--steps`
+    timed steps on an uploaded mini-batch) per arithmetic in turn; the median step time per arithmetic and their ratio."""
+    import torch
+    ariths = args.arith.split(",")
+    out = {}
+    for B in [int(x) for x in args.batches.split(",")]:
+        states = (rs.rand(B, 9, 15, 15) > 0.7).astype(np.float32)
+        pis = rs.dirichlet(np.ones(225), size=B).astype(np.float32)
+        zs = rs.choice([-1.0, 1.0], size=B).astype(np.float32)
+        trs = {a: HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a) for a in ariths}
+        batches = {a: trs[a].upload(states, pis, zs) for a in ariths}
+        times = {a: [] for a in ariths}
+        for _ in range(args.reps):
+            for a in ariths:
+                tr = trs[a]
+                tr.train_step(batches[a], None, None, 1e-3)
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(args.steps):
+                    tr.train_step(batches[a], None, None, 1e-3)
+                torch.cuda.synchronize()
+                times[a].append(1e3 * (time.perf_counter() - t) / args.steps)
+        med = {a: float(np.median(times[a])) for a in ariths}
+        for a in ariths:
+            out["B%d_%s" % (B, a)] = {"ms_per_step": med[a], "runs_ms": [round(x, 3) for x in times[a]],
+                                      "trunk_overflows": getattr(trs[a], "trunk_overflows", 0)}
+        print("batch %4d  " % B + "   ".join("%s %.3f ms/step (runs %s)" % (a, med[a], ", ".join("%.3f" % x for x in times[a]))
+                                           for a in ariths) +
+              ("   ratio %s/%s %.3f" % (ariths[1], ariths[0], med[ariths[1]] / med[ariths[0]]) if len(ariths) > 1 else ""),
+              flush=True)
+        for tr in trs.values():
+            tr.close()
     print(json.dumps(out))
 
 

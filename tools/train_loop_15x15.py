@@ -24,13 +24,14 @@ def main():
     ap.add_argument("--exclusive", action="store_true", help="no new self-play round while the trainer is inside a policy update (default: interleaved)")
     ap.add_argument("--eval-games", type=int, default=10)
     ap.add_argument("--pure-playouts", type=int, default=1000)
+    ap.add_argument("--train-arith", default="f32", choices=("f32", "f16x2"), help="the trainer's trunk arithmetic (HipTrainer trunk_arith)")
     args = ap.parse_args()
     conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
                 n_playout=400, c_puct=5, buffer_size=2198800, batch_size=128, epochs=8, kl_targ=0.02,
                 check_freq=10 ** 9, pure_mcts_playout_num=args.pure_playouts, game_batch_num=args.games,
                 play_batch_size=1, concurrent_games=1024, n_blocks=10, n_filter=128, eval_games=args.eval_games,
                 model_dir="/tmp/apz_models_15", async_update=not args.lock_step, round_seconds=0.25,
-                max_update_share=args.max_update_share, exclusive_updates=args.exclusive)
+                max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith)
     tp = TrainPipeline(conf, seed=1)
     t0 = time.time()
     if args.lock_step:
@@ -61,6 +62,8 @@ def main():
             ups = [h for h in getattr(tp, "trainer_history", []) if "loss" in h]
             if ups:
                 rec.update(loss=round(ups[-1]["loss"], 4), entropy=round(ups[-1]["entropy"], 4), kl=round(ups[-1]["kl"], 5))
+                if "trunk_overflows" in ups[-1]:
+                    rec["trunk_overflows"] = ups[-1]["trunk_overflows"]
             print(json.dumps(rec), flush=True)
             last_t, last_leaf, last_busy, last_upd, last_games = now, leaf, busy, len(iv), games
 
@@ -74,7 +77,10 @@ def main():
                       "leaf_evals_per_s_whole_run": round(tp.engine.stats["leaf_evals"] / dt),
                       "update_share_of_wall_whole_run": round(sum(b - a for a, b in tp.update_intervals) / dt, 3),
                       "exclusive_updates": tp.exclusive_updates,
-                      "self_play_held_s": round(tp.engine.timers.get("gate_s", 0.0), 2)}), flush=True)
+                      "self_play_held_s": round(tp.engine.timers.get("gate_s", 0.0), 2), "train_arith": tp.train_arith,
+                      "policy_update_ms_whole_run": round(1e3 * sum(b - a for a, b in tp.update_intervals) /
+                                                          max(1, len(tp.update_intervals)), 1),
+                      "trunk_overflows": getattr(getattr(tp, "_async_trainer", None), "trunk_overflows", None)}), flush=True)
     tp.close()
 
 

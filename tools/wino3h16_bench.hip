@@ -146,8 +146,8 @@ int main(int argc, char** argv) {
     // kern: 0 = fp16 x 2 with 16-channel chunks, 1 = fp16 x 2 with 8-channel chunks, 2 = exact fp32
     auto launch = [&](int kern, int resid, int grid, int n, float* o) {
         if (kern == 0) {
-            if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<true>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag);
-            else hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<false>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag);
+            if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<true>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, 0);
+            else hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<false>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, 0);
         } else if (kern == 1) {
             if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<true>), dim3(grid), dim3(512), TH::LDS_BYTES, 0, in, upkh, biash, res, o, n, flag);
             else hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<false>), dim3(grid), dim3(512), TH::LDS_BYTES, 0, in, upkh, biash, res, o, n, flag);
