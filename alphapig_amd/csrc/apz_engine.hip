@@ -25,6 +25,7 @@
 #include "conv8_split.h"
 #include "conv8_small.h"
 #include "wgrad_wino3.h"
+#include "wgrad_wino3h.h"
 #include "sampler.h"
 #include "conv_train.h"
 #include "heads_train.h"
@@ -129,7 +130,7 @@ struct apz_engine {
     bool small8 = false;    // 8x8 boards: conv8_kernel / head8_kernel (conv8_small.h)
     float* wfc_raw = nullptr;   // head8_kernel: the policy FullyConnected weight as stored, [hw][4 hw]
     int act_ps = 0, act_rs = 0;
-    bool lds_attr_set[44] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
+    bool lds_attr_set[45] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
     int conv_lds_set[16] = {0};
     // persistent sampler staging (apz_sample_moves_host)
     int32_t* smp_vis = nullptr;
@@ -1944,6 +1945,40 @@ int apz_wgrad_wino(apz_engine* e, const void* x_dev, const void* dy_dev, void* d
     else
         hipLaunchKernelGGL(apz::wgrad_wino3_kernel<false>, dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES, e->stream,
                            (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx);
+    hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
+                       (const float*)e->wgw_scratch, slices, (float*)dw_dev);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, const void* dymax_dev,
+                         int dymax_count, void* flag_dev, void* stream) {
+    if (!e || !x_dev || !dy_dev || !dw_dev || !dymax_dev || dymax_count < 1 || n < 1) return fail(APZ_E_ARG, "bad argument");
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
+    if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
+    using T = apz::WgradWino;
+    using T3 = apz::WgradWino3H;
+    EngineLock guard(e->submit_lock);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    StreamScope sc(e, stream);
+    // the decomposition of apz_wgrad_wino
+    const int spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * T3::BLOCKS)));
+    const int slices = 8 * spx;
+    if (int rc = wgrad_scratch(e, (size_t)slices * T::SCRATCH_FLOATS_PER_SLICE)) return rc;
+    bool& attr = e->lds_attr_set[44];
+    if (!attr) {
+        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
+        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3h_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
+        attr = true;
+    }
+    if (n >= 256)                                     // buffer loads from 256 boards on, as apz_wgrad_wino
+        hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<true>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
+                           e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
+                           dymax_count, (unsigned*)flag_dev);
+    else
+        hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<false>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
+                           e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
+                           dymax_count, (unsigned*)flag_dev);
     hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
                        (const float*)e->wgw_scratch, slices, (float*)dw_dev);
     HIP_TRY(hipGetLastError());

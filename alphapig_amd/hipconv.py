@@ -136,6 +136,21 @@ def conv3x3_dgrad_f16x2(dy, upk, bias, dymax, flag, add=None):
     return dx
 
 
+def conv3x3_wgrad_f16x2(x, dy, dymax, flag):
+    """conv3x3_wgrad of the trunk shape on the f16x2 kernel (csrc/wgrad_wino3h.h; padded rows [n][128][15][16] only):
+    dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two scale of dy); flag = the int32
+    overflow word, set -- never cleared -- when the transformed activations leave the fp16 range."""
+    L, hnd, stream = _ctx(x, ROWS16)
+    if x.dim() != 4 or tuple(x.shape[1:]) != (128, 15, 16) or dy.shape != x.shape:
+        raise ValueError("conv3x3_wgrad_f16x2: the 128 -> 128 trunk shape in the padded-row layout")
+    if int(dymax.numel()) < 1:
+        raise ValueError("conv3x3_wgrad_f16x2: dymax is empty")
+    dw = _empty((128, 128, 3, 3), x)
+    _ck(L, L.apz_wgrad_wino_f16x2(hnd, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(x.shape[0]), dymax.data_ptr(),
+                                  int(dymax.numel()), flag.data_ptr(), stream))
+    return dw
+
+
 def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     """conv(x, W) (flip: the data-gradient convolution with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]) + bias + resid.
     upk: the layer's transformed weights in that orientation when the caller packed them already (wino_pack_many)."""

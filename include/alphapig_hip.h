@@ -225,6 +225,18 @@ int apz_bn_fwd(apz_engine *e, const void *x_dev, const void *resid_dev, const vo
  * MFMAs than apz_conv3x3_wgrad): x_dev / dy_dev in the padded-row layout [n][128][15][16], dw_dev [128][128][3][3]
  * overwritten. */
 int apz_wgrad_wino(apz_engine *e, const void *x_dev, const void *dy_dev, void *dw_dev, int n, void *stream);
+/* The same weight gradient with the per-position products on the fp16 matrix pipe (csrc/wgrad_wino3h.h): both
+ * transformed operands as two fp16 terms (hi + lo, round to nearest even), fp32 accumulation, the same slice scratch
+ * and finish kernel as apz_wgrad_wino, the same bits on every run.
+ *   scale     dymax_dev: dymax_count >= 1 floats whose largest magnitude is max |dy| (what apz_bn_bwd_max leaves in
+ *             dxmax_dev; as apz_wino3h_conv_dgrad).  The launch multiplies dy by 2^a, a chosen on the device so that
+ *             max |dy| 2^a lies in [2^6, 2^7): the transformed gradient stays below 225 * 2^7 = 28 800 < 65 504 and
+ *             cannot overflow on finite input; a = 0 for an all-zero dy, |a| <= 64; 2^-a is applied to the result.
+ *   overflow  the transformed activations are not scaled (|V| <= 100 max |x|).  The 32-bit word at flag_dev (may be
+ *             NULL) is set to 1 when a partial result is not finite or an activation exceeds 655 (where that bound
+ *             leaves the fp16 range); the call never clears it, and dw_dev of a call that sets it is unspecified. */
+int apz_wgrad_wino_f16x2(apz_engine *e, const void *x_dev, const void *dy_dev, void *dw_dev, int n,
+                         const void *dymax_dev, int dymax_count, void *flag_dev, void *stream);
 /* One optimiser step of the reference's Adam (policy_value_net_mxnet.py:198-205: rescale_grad = 1/batch_size,
  * wd on *_weight / *_gamma) over ntensors device tensors in ONE launch.  table_host: ntensors entries
  * { float *w; const float *g; float *m; float *v; int64 n; float wd; int32 pad; } (48 bytes) in HOST memory;
