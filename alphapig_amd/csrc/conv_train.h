@@ -365,8 +365,11 @@ __global__ __launch_bounds__(256) void bn_stats_r16_kernel(const float* __restri
     if (sub < 4)
         for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
             const f32x4 v = reinterpret_cast<const f32x4*>(x + ((size_t)b * C + c) * 240)[k];
-            s1 += (double)((v[0] + v[1]) + (v[2] + v[3]));
-            s2 += (double)((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
+            // squares and sums in double, as bn_stats_kernel: an fp32 (v0^2 + v1^2) + ... loses (1 + mean^2 / var) ulps of the
+            // variance to the cancellation in sum x^2 / M - mean^2 (the kernel is bound by its loads)
+            const double d0 = v[0], d1 = v[1], d2 = v[2], d3 = v[3];
+            s1 += (d0 + d1) + (d2 + d3);
+            s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
     s1 = block_sum_256(s1, sh);
     s2 = block_sum_256(s2, sh);

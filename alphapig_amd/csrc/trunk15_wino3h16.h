@@ -85,16 +85,22 @@ __device__ unsigned long long apz_wino3h16_stamps[4 * 8 * 12];   // [workgroup 4
 //                   dxmax, one per channel and batch split), every workgroup folds them (max: exact, any order), and a puts
 //                   the maximum into [2^7, 2^8) -- |V| <= 100 max <= 25 600 stays below the fp16 limit, and 22 binades
 //                   below the maximum are still normal fp16.  The raw tile values are multiplied by 2^a before the
-//                   transform, 2^-a goes into the 1 / S of the bias FMA: both exact (powers of two, no over- or underflow
-//                   for |a| <= 64).
+//                   transform, 2^-a goes into the 1 / S of the bias FMA.  2^a and 2^-a are normal floats for
+//                   -64 <= a <= 110; the product 2^-a / S = 2^-(a + k) (S = 2^k from Wino3H::scale_for, k about 18 for
+//                   weights of this net, clamped to 100) is an fp32 subnormal from a + k = 127 on, and exact there only
+//                   because this library is built with fp32 denormals enabled (the compiler's default for gfx950;
+//                   no flush-to-zero flag in build.py) and while a + k <= 149.  A maximum of 1e-30 has a = 107: 2^-125
+//                   at k = 18.  A partial maximum of +inf sets the overflow word.
 enum { WINO3H16_PLAIN = 0, WINO3H16_STATS = 1, WINO3H16_DGRAD = 2 };
 
-// a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as Wino3H::scale_for(0)); clamped to [-64, 64]
+// a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as Wino3H::scale_for(0)); clamped to [-64, 110]: 2^110 and 2^-110 are
+// normal floats, and maxima down to 2^-103 (1e-31) still reach the window.  (A maximum of +inf -- the launch sets the
+// overflow word for it -- gives -64.)
 __device__ __forceinline__ int wino3h16_dgrad_exponent(float m) {
     if (!(m > 0.f)) return 0;
     const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u);   // m in [2^(e-127), 2^(e-126)) (e = 0: subnormal)
     const int a = 134 - e;
-    return a < -64 ? -64 : (a > 64 ? 64 : a);
+    return a < -64 ? -64 : (a > 110 ? 110 : a);
 }
 
 template <bool RESID, bool RELU = true, int FORM = WINO3H16_PLAIN>
@@ -144,6 +150,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     // DGRAD: the input scale 2^a and 2^-a from the partial maxima (the eight wave maxima pass through V[0], which the first
     // item's transform writes only behind its barrier)
     float xsc = 1.f, xisc = 1.f;
+    bool aux_inf = false;                             // DGRAD: a partial maximum is +inf -- no scale fits, the result is void
     if constexpr (DGRAD) {
         const float* pm = static_cast<const float*>(aux);
         float m = 0.f;
@@ -155,6 +162,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
 #pragma unroll
         for (int w = 0; w < 8; w++) m = fmaxf(m, lds[w]);
         const int a = __builtin_amdgcn_readfirstlane(wino3h16_dgrad_exponent(m));
+        aux_inf = !(m <= 3.4028234664e38f);
         xsc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
         xisc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
     }
@@ -321,7 +329,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
         else unit_pair_at(ub_nxt, p9 - 9, slot);
     };
 
-    unsigned nonfinite = 0;                           // any pre-ReLU output of this thread that is not a finite number
+    unsigned nonfinite = aux_inf ? 1u : 0u;           // any pre-ReLU output of this thread that is not a finite number
 
     ub_cur = ub_nxt = unit_base(0, 0);
 #pragma unroll

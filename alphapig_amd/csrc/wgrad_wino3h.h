@@ -38,8 +38,8 @@
 // fp16 normal range, so dy is multiplied by 2^a on the way in, a chosen on the device from `dymax` (`dymax_n` partial
 // maxima of |dy|, what apz_bn_bwd_max leaves; every workgroup folds them: max is exact in any order, no atomics) such that
 // max |dy| 2^a lies in [2^6, 2^7): 225 * 128 = 28 800 < 65 504 -- the dM side cannot overflow on finite input whose maxima
-// are true -- and 21 binades below the maximum are still normal fp16.  a = 0 for an all-zero dy, |a| <= 64; 2^-a is applied
-// to the partial dg in the epilogue (exact: a power of two).  V: |V| <= 100 max |x|, not scaled, as in the forward.  The
+// are true -- and 21 binades below the maximum are still normal fp16.  a = 0 for an all-zero dy, -64 <= a <= 110; 2^-a is
+// applied to the partial dg in the epilogue (exact: a power of two).  V: |V| <= 100 max |x|, not scaled, as in the forward.  The
 // 32-bit word at `flag` is set (a plain vector store; never cleared here) when a partial dg is not finite -- an fp16 term that
 // is +-inf makes every accumulator it feeds +-inf or NaN -- and also when an activation exceeds 65 504 / 100, where the
 // bound above no longer keeps V inside fp16 (sufficient, not necessary: a single outlier only reaches 25 |x|).  The result
@@ -69,12 +69,13 @@ struct WgradWino3H {
 };
 static_assert(WgradWino3H::LDS_BYTES <= 160 * 1024, "LDS");
 
-// a with m 2^a in [2^6, 2^7); 0 for m = 0; clamped to [-64, 64]
+// a with m 2^a in [2^6, 2^7); 0 for m = 0; clamped to [-64, 110] (as wino3h16_dgrad_exponent: maxima down to 1e-31 reach
+// the window; m = +inf sets the overflow word)
 __device__ __forceinline__ int wgw3h_exponent(float m) {
     if (!(m > 0.f)) return 0;
     const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u);   // m in [2^(e-127), 2^(e-126)) (e = 0: subnormal)
     const int a = 133 - e;
-    return a < -64 ? -64 : (a > 64 ? 64 : a);
+    return a < -64 ? -64 : (a > 110 ? 110 : a);
 }
 
 // the two terms of v0 (position p) and v1 (position p + 1) of this thread's (channel, tile): dst points at the hi term of
@@ -120,6 +121,7 @@ __global__ __launch_bounds__(512) void wgrad_wino3h_kernel(const float* __restri
 
     // ---- the scale of dy: 2^a from the partial maxima (the eight wave maxima meet behind the operand sets)
     float sc, isc;
+    bool max_inf;                                     // a partial maximum is +inf: no scale fits, the result is void
     {
         float m = 0.f;
         for (int i = tid; i < dymax_n; i += T::THREADS) m = fmaxf(m, fabsf(dymax[i]));
@@ -132,6 +134,7 @@ __global__ __launch_bounds__(512) void wgrad_wino3h_kernel(const float* __restri
         for (int w = 0; w < 8; w++) m = fmaxf(m, wm[w]);
         __syncthreads();                              // (the epilogue's staging area covers wm)
         const int a = __builtin_amdgcn_readfirstlane(wgw3h_exponent(m));
+        max_inf = !(m <= 3.4028234664e38f);
         sc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
         isc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
     }
@@ -350,7 +353,7 @@ __global__ __launch_bounds__(512) void wgrad_wino3h_kernel(const float* __restri
                 chk = __builtin_fmaf(v, 0.f, chk);
             }
     }
-    if ((chk != chk || xmax > T::X_LIMIT) && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
+    if ((chk != chk || xmax > T::X_LIMIT || max_inf) && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
 #ifdef APZ_WGW3_STAMPS
     WGW3_STAMP(5)
     if (blockIdx.x == 0 && lane == 0)

@@ -125,7 +125,8 @@ def conv3x3_fwd_stats_f16x2(x, upk, bias, flag):
 
 def conv3x3_dgrad_f16x2(dy, upk, bias, dymax, flag, add=None):
     """conv3x3_dgrad on the f16x2 kernel (padded rows): upk / bias = one layer's data-gradient pair of wino3h_pack_many;
-    dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two input scale); (+ add)."""
+    dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two input scale; NaN entries are
+    ignored, a +inf entry sets `flag`); (+ add)."""
     L, hnd, stream = _ctx(dy, ROWS16)
     if tuple(dy.shape[1:]) != (128, 15, 16) or (add is not None and add.shape != dy.shape):
         raise ValueError("conv3x3_dgrad_f16x2: the 128-channel trunk in the padded-row layout")
@@ -139,7 +140,8 @@ def conv3x3_dgrad_f16x2(dy, upk, bias, dymax, flag, add=None):
 def conv3x3_wgrad_f16x2(x, dy, dymax, flag):
     """conv3x3_wgrad of the trunk shape on the f16x2 kernel (csrc/wgrad_wino3h.h; padded rows [n][128][15][16] only):
     dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two scale of dy); flag = the int32
-    overflow word, set -- never cleared -- when the transformed activations leave the fp16 range."""
+    overflow word, set -- never cleared -- when the transformed activations leave the fp16 range, a partial result is not
+    finite or dymax holds +inf."""
     L, hnd, stream = _ctx(x, ROWS16)
     if x.dim() != 4 or tuple(x.shape[1:]) != (128, 15, 16) or dy.shape != x.shape:
         raise ValueError("conv3x3_wgrad_f16x2: the 128 -> 128 trunk shape in the padded-row layout")

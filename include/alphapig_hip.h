@@ -186,7 +186,9 @@ int apz_wino_conv_stats(apz_engine *e, const void *x_dev, const void *upk_dev, c
  *                          exact kernels).
  *   apz_wino3h_conv_dgrad  dx = conv(dy, W') (+ add_dev; NULL: none), every tensor [n][128][15][16]; dymax_dev: dymax_count
  *                          partial maxima of |dy| (apz_bn_bwd_max's dxmax) -- the launch scales dy by 2^a with the maximum
- *                          in [2^7, 2^8) before the fp16 split; flag_dev as above.
+ *                          in [2^7, 2^8) before the fp16 split (-64 <= a <= 110: maxima down to 1e-31 reach that
+ *                          window; NaN entries are ignored); flag_dev as above, also set when an entry of dymax_dev
+ *                          is +inf.
  *   apz_bn_bwd_max         apz_bn_bwd (padded-row layout) + dxmax_dev [apz_bn_bwd_splits(n, C, layout)][C] floats: max |dx|
  *                          per batch split and channel.
  *   apz_adam_step_unless   apz_adam_step, skipped on the device when the 32-bit word at skip_dev is not zero. */
@@ -231,10 +233,11 @@ int apz_wgrad_wino(apz_engine *e, const void *x_dev, const void *dy_dev, void *d
  *   scale     dymax_dev: dymax_count >= 1 floats whose largest magnitude is max |dy| (what apz_bn_bwd_max leaves in
  *             dxmax_dev; as apz_wino3h_conv_dgrad).  The launch multiplies dy by 2^a, a chosen on the device so that
  *             max |dy| 2^a lies in [2^6, 2^7): the transformed gradient stays below 225 * 2^7 = 28 800 < 65 504 and
- *             cannot overflow on finite input; a = 0 for an all-zero dy, |a| <= 64; 2^-a is applied to the result.
+ *             cannot overflow on finite input; a = 0 for an all-zero dy, -64 <= a <= 110; 2^-a is applied to the result.
  *   overflow  the transformed activations are not scaled (|V| <= 100 max |x|).  The 32-bit word at flag_dev (may be
- *             NULL) is set to 1 when a partial result is not finite or an activation exceeds 655 (where that bound
- *             leaves the fp16 range); the call never clears it, and dw_dev of a call that sets it is unspecified. */
+ *             NULL) is set to 1 when a partial result is not finite, an activation exceeds 655 (where that bound
+ *             leaves the fp16 range) or an entry of dymax_dev is +inf; the call never clears it, and dw_dev of a
+ *             call that sets it is unspecified. */
 int apz_wgrad_wino_f16x2(apz_engine *e, const void *x_dev, const void *dy_dev, void *dw_dev, int n,
                          const void *dymax_dev, int dymax_count, void *flag_dev, void *stream);
 /* One optimiser step of the reference's Adam (policy_value_net_mxnet.py:198-205: rescale_grad = 1/batch_size,

@@ -288,8 +288,8 @@ def test_head_conv1x1_forward_backward(n, c, co, hw, layout):
     assert err(db, b64.grad) < 5 * tol(b64.grad)
 
 
-@pytest.mark.parametrize("n,k,nn", [(37, 900, 225), (5, 450, 1), (130, 256, 64), (512, 900, 225), (1, 128, 1), (64, 67, 19)])
-def test_fully_connected_forward_backward(n, k, nn):
+def _fully_connected_against_float64(n, k, nn):
+    """fc_fwd and fc_bwd on x [n][k], W [nn][k] against float64 autograd"""
     from alphapig_amd import hipconv
     g = torch.Generator().manual_seed(n + k + nn)
     x = torch.randn(n, k, generator=g)
@@ -307,6 +307,24 @@ def test_fully_connected_forward_backward(n, k, nn):
     assert err(dx, x64.grad) < tol(x64.grad)
     assert err(dw, w64.grad) < 5 * tol(w64.grad)
     assert err(db, b64.grad) < 5 * tol(b64.grad)
+
+
+@pytest.mark.parametrize("n,k,nn", [(37, 900, 225), (5, 450, 1), (130, 256, 64), (512, 900, 225), (1, 128, 1), (64, 67, 19)])
+def test_fully_connected_forward_backward(n, k, nn):
+    _fully_connected_against_float64(n, k, nn)
+
+
+@pytest.mark.parametrize("n,k,nn,product", [(2049, 131, 227, "forward"), (600, 900, 225, "dx"), (5, 900, 577, "dw")])
+def test_fully_connected_on_the_64x64_tile_kernel(n, k, nn, product):
+    """launch_sgemm takes sgemm_mfma_kernel<4> when the output's 64 x 64 tiles number at least half the CUs; the shapes
+    above put the named product across that threshold on 256 CUs (132, 150 and 150 tiles; the forward one with K no
+    multiple of 4 and ragged M and N).  The predicate is restated here: on another CU count the case fails instead of
+    testing the other kernel."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tiles = lambda M, N: ((N + 63) // 64) * ((M + 63) // 64)
+    count = {"forward": tiles(n, nn), "dx": tiles(n, k), "dw": tiles(nn, k)}[product]      # C[M][N] of the three products
+    assert count >= cus // 2, (product, count, cus)
+    _fully_connected_against_float64(n, k, nn)
 
 
 def test_dropout_mask_is_a_stateless_hash():
