@@ -124,7 +124,9 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_layout_convert", "apz_bias_grad", "apz_add", "apz_load_weights_dev",
                "apz_sync", "apz_stream", "apz_set_forward_graphs",
                "apz_device_alloc", "apz_device_free", "apz_memcpy_h2d", "apz_memcpy_d2h",
-               "apz_conv3x3_bench", "apz_layer_io", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows"]
+               "apz_conv3x3_bench", "apz_layer_io", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows",
+               "apz_set_trunk_act_exponents", "apz_get_trunk_act_exponents", "apz_calibrate_trunk_planes", "apz_calibrate_trunk_codes",
+               "apz_set_act_scale_auto"]
 
 
 def _one_hip_runtime():
@@ -286,6 +288,11 @@ def hip():
         "apz_test_select_trunk": (C.c_int, [vp, C.c_int]),
         "apz_set_trunk_arith": (C.c_int, [vp, C.c_int]),
         "apz_trunk_overflows": (C.c_long, [vp]),
+        "apz_set_trunk_act_exponents": (C.c_int, [vp, i32p, C.c_int]),
+        "apz_get_trunk_act_exponents": (C.c_int, [vp, i32p, C.c_int]),
+        "apz_calibrate_trunk_planes": (C.c_int, [vp, f32p, C.c_int, f32p, C.c_int]),
+        "apz_calibrate_trunk_codes": (C.c_int, [vp, u8p, C.c_int, f32p, C.c_int]),
+        "apz_set_act_scale_auto": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -30,6 +30,7 @@
 #include "conv_train.h"
 #include "heads_train.h"
 #include "weights_pack.h"
+#include "act_max.h"
 
 namespace {
 
@@ -73,6 +74,9 @@ struct ConvLayer {
     void* wpk8h = nullptr;  // conv8h_kernel (8x8 boards, APZ_ARITH_F16X2, C_in a multiple of 64): w S[co] as two fp16 terms (Conv8H)
     float* bias8h = nullptr;   // ... and its [cout biases][cout x 1 / S[co]]
     float* bias = nullptr;
+    // APZ_ARITH_F16X2, 15x15 trunk layers: the static exponent a of the layer's input scale 2^a (trunk15_wino3h16.h,
+    // WINO3H16_PLAIN_SCALED); 0 = the unscaled kernel.  Engine state: weight loads do not touch it.
+    int act_exp = 0;
 };
 
 struct Pending {
@@ -169,6 +173,12 @@ struct apz_engine {
     // environment at engine creation selects its predecessor trunk15_wino3h_kernel instead (A/B measurements)
     bool f16x2_k8 = false;
     long ovf_repeats = 0;                    // forwards repeated so far (apz_trunk_overflows)
+    // static activation exponents (apz_set_trunk_act_exponents ...): max |input| of every trunk convolution, measured by
+    // act_absmax_kernel during a calibration forward or the exact repeat of an overflowed one
+    bool act_auto = false;                   // apz_set_act_scale_auto: an overflow lowers the exponents
+    bool measure_max = false;                // run_trunk: measure (set around exact-fp32 forwards only)
+    float* amax_dev = nullptr;               // [trunk layer][ActMax::MAX_PARTS] partial maxima
+    float* amax_host = nullptr;              // ... pinned copy, valid after the stream synchronisation behind the forward
     int trunk_kernel = APZ_TRUNK_WINOGRAD;   // or APZ_TRUNK_DIRECT (trunk15_ring_kernel): apz_test_select_trunk, tests only
     // profiling
     bool profiling = false;
@@ -465,10 +475,14 @@ int launch_wino3b_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
 }
 
 // The 2 x fp16 split kernels (K16: trunk15_wino3h16_kernel, else trunk15_wino3h_kernel): same layouts, same grids, 512 threads
-template <bool RESID, bool K16>
+// (SCALED, K16 only: the form with the layer's static input exponent, launched for L.act_exp != 0 and never otherwise --
+// an engine without exponents runs the same code objects as before they existed)
+template <bool RESID, bool K16, bool SCALED = false>
 int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    static_assert(K16 || !SCALED, "only the 16-channel kernel has a scaled form");
     using T = typename std::conditional<K16, apz::Wino3H16, apz::Wino3H>::type;
-    const void* kern = K16 ? (const void*)apz::trunk15_wino3h16_kernel<RESID, true> : (const void*)apz::trunk15_wino3h_kernel<RESID, true>;
+    constexpr int FORM = SCALED ? apz::WINO3H16_PLAIN_SCALED : apz::WINO3H16_PLAIN;
+    const void* kern = K16 ? (const void*)apz::trunk15_wino3h16_kernel<RESID, true, FORM> : (const void*)apz::trunk15_wino3h_kernel<RESID, true>;
     bool& configured = e->lds_attr_set[attr_slot];
     if (!configured) {
         HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
@@ -479,8 +493,9 @@ int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
         const size_t off = (size_t)b0 * T::C * T::GPLANE;
         const int grid = apz::wino3_grid(nb, e->num_cu);
         if constexpr (K16)
-            hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
-                               (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur, nullptr, 0);
+            hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<RESID, true, FORM>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
+                               in + off, (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur,
+                               nullptr, SCALED ? L.act_exp : 0);
         else
             hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
                                (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
@@ -495,6 +510,10 @@ int launch_trunk_wino3(apz_engine* e, const ConvLayer& L, const float* in, const
         if (e->f16x2_k8) {
             if (resid) return launch_wino3h_t<true, false>(e, 32, L, in, resid, out, n);
             return launch_wino3h_t<false, false>(e, 33, L, in, resid, out, n);
+        }
+        if (L.act_exp != 0) {
+            if (resid) return launch_wino3h_t<true, true, true>(e, 43, L, in, resid, out, n);
+            return launch_wino3h_t<false, true, true>(e, 44, L, in, resid, out, n);
         }
         if (resid) return launch_wino3h_t<true, true>(e, 36, L, in, resid, out, n);
         return launch_wino3h_t<false, true>(e, 37, L, in, resid, out, n);
@@ -605,6 +624,17 @@ int launch_conv(apz_engine* e, const ConvLayer& L, const float* in, const float*
     return fail(APZ_E_UNSUPPORTED, "conv3x3: unsupported board size / channel count");
 }
 
+// e->measure_max: max |x| of the rows16 tensor `in` (n boards, 128 channels), the input of trunk layer li >= 1, as
+// partials in row li - 1 of e->amax_dev
+int launch_act_max(apz_engine* e, int li, const float* in, int n) {
+    const long n4 = (long)n * 128 * (apz::Trunk15::GPLANE / 4);
+    float* part = e->amax_dev + (size_t)(li - 1) * apz::ActMax::MAX_PARTS;
+    hipLaunchKernelGGL(apz::act_absmax_kernel, dim3(apz::ActMax::grid_for(n4)), dim3(apz::ActMax::THREADS), 0, e->stream, in, n4,
+                       part);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
 // runs conv layers [0, upto] on e->planes; returns the buffer holding layer `upto`'s output
 int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** result, const unsigned char* codes = nullptr) {
     float *x = e->act[0], *t = e->act[1], *y = e->act[2];
@@ -628,6 +658,10 @@ int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** resul
         tm.launches = last;
         for (int li = 1; li <= last; li++) {
             const ConvLayer& L = e->convs[li];
+            if (e->measure_max) {
+                int rc = launch_act_max(e, li, L.residual ? t : x, n);
+                if (rc) return rc;
+            }
             if (e->cfg.net_kind == APZ_NET_RESNET) {
                 if (!L.residual) {          // convA: x -> t
                     int rc = launch_conv(e, L, x, nullptr, t, n);
@@ -647,6 +681,9 @@ int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** resul
             }
         }
     }
+    if (e->measure_max && last >= 1)
+        HIP_TRY(hipMemcpyAsync(e->amax_host, e->amax_dev, (size_t)last * apz::ActMax::MAX_PARTS * sizeof(float), hipMemcpyDeviceToHost,
+                               e->stream));
     *result = const_cast<float*>(cur);
     return APZ_OK;
 }
@@ -728,11 +765,160 @@ struct ArmOverflowWord {
     ~ArmOverflowWord() { e->ovf_cur = nullptr; }
 };
 
+// ---- static activation exponents of the f16x2 trunk kernel
+// APZ_OK where they exist: the 15x15 / 128-filter residual net, APZ_ARITH_F16X2, the 16-channel kernel
+int act_scale_supported(apz_engine* e) {
+    if (e->small8)
+        return fail(APZ_E_UNSUPPORTED, "activation exponents: the 8x8 kernels have none (conv8_split.h is in range up to 65 504)");
+    if (!e->ring || e->trunk_arith != APZ_ARITH_F16X2)
+        return fail(APZ_E_UNSUPPORTED, "activation exponents exist for the 15x15 / 128-filter residual net with APZ_ARITH_F16X2 only");
+    if (e->f16x2_k8)
+        return fail(APZ_E_UNSUPPORTED, "activation exponents: the engine was created with APZ_F16X2_K8=1, and the old kernel has no scaled form");
+    return APZ_OK;
+}
+
+int act_scale_buffers(apz_engine* e) {
+    const size_t bytes = (size_t)std::max<size_t>(e->convs.size() - 1, 1) * apz::ActMax::MAX_PARTS * sizeof(float);
+    if (!e->amax_dev) HIP_TRY(hipMalloc((void**)&e->amax_dev, bytes));
+    if (!e->amax_host) HIP_TRY(hipHostMalloc((void**)&e->amax_host, bytes));
+    return APZ_OK;
+}
+
+// The largest |a| the layer's weights allow: 2^-a goes into 1 / S[co] = 2^-k of the bias FMA, and 2^-(a + k) must be a
+// normal float for every output channel (the subnormal case is exact only while fp32 denormals are enabled: see the DGRAD
+// comment in trunk15_wino3h16.h).  Reads the layer's 1 / S from the device: the device-side weight refresh computes them
+// there.  Synchronous.
+int clamp_act_exponent(apz_engine* e, const ConvLayer& L, int a, int* out) {
+    a = std::max(-apz::ACT_EXP_MAX, std::min(apz::ACT_EXP_MAX, a));
+    if (a != 0 && L.bias3h) {
+        float inv_s[128];
+        HIP_TRY(hipMemcpyAsync(inv_s, L.bias3h + 128, sizeof(inv_s), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        int kmin = 1000, kmax = -1000;
+        for (float v : inv_s) {
+            int ex;
+            std::frexp((double)v, &ex);               // 1 / S = 2^-k = 0.5 x 2^(1 - k)
+            kmin = std::min(kmin, 1 - ex);
+            kmax = std::max(kmax, 1 - ex);
+        }
+        a = std::max(-126 - kmin, std::min(126 - kmax, a));   // -126 <= a + k <= 126 for every channel
+    }
+    *out = a;
+    return APZ_OK;
+}
+
+// after the stream synchronisation behind a measuring forward: the maxima of the `count` trunk inputs
+void fold_act_maxima(apz_engine* e, int n, int count, float* m) {
+    const int parts = apz::ActMax::grid_for((long)n * 128 * (apz::Trunk15::GPLANE / 4));
+    for (int l = 0; l < count; l++) {
+        float v = 0.f;
+        for (int i = 0; i < parts; i++) v = std::fmax(v, e->amax_host[(size_t)l * apz::ActMax::MAX_PARTS + i]);
+        m[l] = v;
+    }
+}
+
+// apz_set_act_scale_auto: behind the exact repeat of an overflowed forward of n boards (stream drained).  Only ever lowers
+// an exponent; a non-finite maximum (the exact forward overflowed too) leaves all of them alone.
+int lower_act_exponents(apz_engine* e, int n) {
+    const int count = (int)e->convs.size() - 1;
+    std::vector<float> m(count);
+    fold_act_maxima(e, n, count, m.data());
+    for (float v : m)
+        if (!std::isfinite(v)) return APZ_OK;
+    bool changed = false;
+    for (int l = 0; l < count; l++) {
+        ConvLayer& L = e->convs[l + 1];
+        int a = std::min(L.act_exp, apz::act_exponent_for(m[l]));
+        if (int rc = clamp_act_exponent(e, L, a, &a)) return rc;
+        if (a < L.act_exp) {
+            L.act_exp = a;
+            changed = true;
+        }
+    }
+    if (changed) drop_forward_graphs(e);          // a captured launch sequence holds the old exponents
+    return APZ_OK;
+}
+
+// The exact-fp32 repeat of an overflowed forward of n boards; with apz_set_act_scale_auto on it measures the trunk inputs
+// on the way and lowers the exponents behind it.  Returns with the stream drained.
+template <class F>
+int repeat_exact(apz_engine* e, int n, F run) {
+    const bool measure = e->act_auto && e->amax_dev && n > 0;
+    e->force_f32 = true;
+    e->measure_max = measure;
+    int rc = run();
+    e->measure_max = false;
+    e->force_f32 = false;
+    e->ovf_repeats++;
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return measure ? lower_act_exponents(e, n) : APZ_OK;
+}
+
+// one measuring forward of n boards on the exact-fp32 kernels (`run` queues it), then the exponents from the maxima
+template <class F>
+int calibrate_trunk(apz_engine* e, int n, float* layer_max_out, int count, F run) {
+    if (int rc = act_scale_supported(e)) return rc;
+    if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
+    const int layers = (int)e->convs.size() - 1;
+    if (count != layers) return fail(APZ_E_ARG, "calibration: count must be 2 * n_blocks = " + std::to_string(layers));
+    if (n < 1 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "calibration: batch must be in [1, max_batch]");
+    if (count == 0) return APZ_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (int rc = act_scale_buffers(e)) return rc;
+    e->force_f32 = true;                          // (no overflow word armed either: nothing here counts as an overflow)
+    e->measure_max = true;
+    int rc = run();
+    e->measure_max = false;
+    e->force_f32 = false;
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    resolve_pending(e);
+    std::vector<float> m(count);
+    fold_act_maxima(e, n, count, m.data());
+    if (layer_max_out) std::memcpy(layer_max_out, m.data(), count * sizeof(float));
+    for (int l = 0; l < count; l++)
+        if (!std::isfinite(m[l]))
+            return fail(APZ_E_STATE, "calibration: the input of trunk convolution " + std::to_string(l) +
+                                         " is not finite in exact fp32; the exponents are unchanged");
+    std::vector<int> eff(count);
+    for (int l = 0; l < count; l++)
+        if (int rc2 = clamp_act_exponent(e, e->convs[l + 1], apz::act_exponent_for(m[l]), &eff[l])) return rc2;
+    drop_forward_graphs(e);
+    std::vector<int> old(count);
+    for (int l = 0; l < count; l++) {
+        old[l] = e->convs[l + 1].act_exp;
+        e->convs[l + 1].act_exp = eff[l];
+    }
+    // The maxima are taken behind the ReLU, which turns a NaN into 0: a layer whose exact-fp32 sums are inf - inf shows a
+    // maximum of 0, not a non-finite one.  So the new exponents prove themselves on their own batch: the same forward on
+    // the f16x2 kernel (whatever the batch size), whose non-finite check sits in front of the ReLU, must not raise the word.
+    const bool small_was = e->no_small_trunk;
+    e->no_small_trunk = true;
+    e->ovf_host[APZ_MAX_SLOTS] = 0;
+    e->ovf_cur = e->ovf_dev + APZ_MAX_SLOTS;
+    rc = run();
+    e->ovf_cur = nullptr;
+    e->no_small_trunk = small_was;
+    hipError_t he = hipStreamSynchronize(e->stream);
+    resolve_pending(e);
+    const bool raised = e->ovf_host[APZ_MAX_SLOTS] != 0;
+    e->ovf_host[APZ_MAX_SLOTS] = 0;
+    if (rc || he != hipSuccess || raised) {
+        for (int l = 0; l < count; l++) e->convs[l + 1].act_exp = old[l];
+        if (rc) return rc;
+        if (he != hipSuccess) return fail(APZ_E_HIP, std::string("calibration: ") + hipGetErrorString(he));
+        return fail(APZ_E_STATE, "calibration: the batch is not finite on the f16x2 kernel with its own exponents (a layer "
+                                 "overflows in exact fp32 too); the exponents are unchanged");
+    }
+    return APZ_OK;
+}
+
 // APZ_ARITH_F16X2: forward_dev with the overflow word `idx` armed.  `again` != nullptr: the forward is collected here --
 // wait for the stream, look at the word and, if an activation left the fp16 range, run `again` (the same forward, which
 // then takes the exact-fp32 trunk kernel).  Other arithmetics: plain forward_dev.
 template <class F>
-int forward_guarded(apz_engine* e, int idx, F run, bool collect) {
+int forward_guarded(apz_engine* e, int idx, int n, F run, bool collect) {
     if (e->trunk_arith != APZ_ARITH_F16X2 || !e->ovf_host) return run();
     e->ovf_host[idx] = 0;
     e->ovf_cur = e->ovf_dev + idx;
@@ -742,12 +928,7 @@ int forward_guarded(apz_engine* e, int idx, F run, bool collect) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->ovf_host[idx]) {
         e->ovf_host[idx] = 0;
-        e->force_f32 = true;
-        rc = run();
-        e->force_f32 = false;
-        e->ovf_repeats++;
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        return repeat_exact(e, n, run);
     }
     return APZ_OK;
 }
@@ -810,10 +991,11 @@ void apz_destroy(apz_engine* e) {
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
                    e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
-                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets};
+                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->amax_dev};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->ovf_host) hipHostFree(e->ovf_host);
+    if (e->amax_host) hipHostFree(e->amax_host);
     for (auto& sl : e->slots) {
         if (sl.h_codes) hipHostFree(sl.h_codes);
         if (sl.h_probs) hipHostFree(sl.h_probs);
@@ -1096,6 +1278,10 @@ int apz_load_weights(apz_engine* e, const char* const* names, const float* const
             return rc;
     }
     e->loaded = true;
+    // the activation exponents are engine state and survive the load; the new 1 / S may only narrow their range
+    for (auto& L : e->convs)
+        if (L.act_exp != 0)
+            if (int rc = clamp_act_exponent(e, L, L.act_exp, &L.act_exp)) return rc;
     return APZ_OK;
 }
 
@@ -1105,7 +1291,7 @@ int apz_forward(apz_engine* e, const void* planes_dev, int n, void* probs_dev, v
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     // (APZ_ARITH_F16X2: returns with the stream drained -- the overflow word has to be read before the results are used)
-    return forward_guarded(e, APZ_MAX_SLOTS, [&]() {
+    return forward_guarded(e, APZ_MAX_SLOTS, n, [&]() {
         return forward_dev(e, (const float*)planes_dev, n, (float*)probs_dev, (float*)values_dev, (float*)logits_dev,
                            (float*)vlogits_dev);
     }, true);
@@ -1120,7 +1306,7 @@ int apz_forward_host(apz_engine* e, const float* planes_host, int n, float* prob
     const size_t hw = e->hw, pin = (size_t)n * e->cfg.c_in * hw * sizeof(float);
     std::memcpy(e->h_planes, planes_host, pin);
     HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, pin, hipMemcpyHostToDevice, e->stream));
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, [&]() { return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr); }, true);
+    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() { return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr); }, true);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(e->h_probs, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(e->h_values, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1142,7 +1328,7 @@ int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, f
     const size_t hw = e->hw;
     HIP_TRY(hipMemcpyAsync(e->codes, codes_pinned, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
     // (APZ_ARITH_F16X2: the forward is collected here, see forward_guarded -- the copies below are queued behind it)
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, [&]() -> int {
+    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() -> int {
         if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, e->probs, e->values, nullptr, nullptr, e->codes);
         if (int r = apz_encode_planes(e, e->codes, n, e->cfg.c_in, e->planes)) return r;
         return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
@@ -1260,18 +1446,12 @@ int apz_wait(apz_engine* e, int slot, float* probs_host, float* values_host) {
         // an activation of this batch left the fp16 range (trunk15_wino3h.h): the same batch again on the exact-fp32 kernel
         EngineLock guard(e->submit_lock);
         e->ovf_host[slot] = 0;
-        e->force_f32 = true;
-        int rc;
-        if (stem_takes_codes(e)) {
-            rc = forward_dev(e, nullptr, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr, sl.d_codes);
-        } else {
-            rc = apz_encode_planes(e, sl.d_codes, sl.n, e->cfg.c_in, e->planes);
-            if (!rc) rc = forward_dev(e, e->planes, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr);
-        }
-        e->force_f32 = false;
-        e->ovf_repeats++;
+        int rc = repeat_exact(e, sl.n, [&]() -> int {
+            if (stem_takes_codes(e)) return forward_dev(e, nullptr, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr, sl.d_codes);
+            if (int r = apz_encode_planes(e, sl.d_codes, sl.n, e->cfg.c_in, e->planes)) return r;
+            return forward_dev(e, e->planes, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr);
+        });
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
     }
     std::memcpy(probs_host, sl.h_probs, (size_t)sl.n * e->hw * sizeof(float));
     std::memcpy(values_host, sl.h_values, (size_t)sl.n * sizeof(float));
@@ -2362,6 +2542,69 @@ int apz_set_trunk_arith(apz_engine* e, int arith) {
 }
 
 long apz_trunk_overflows(apz_engine* e) { return e ? e->ovf_repeats : -1; }
+
+int apz_set_trunk_act_exponents(apz_engine* e, const int* a, int count) {
+    if (!e || !a) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    if (int rc = act_scale_supported(e)) return rc;
+    if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
+    const int layers = (int)e->convs.size() - 1;
+    if (count != layers) return fail(APZ_E_ARG, "activation exponents: count must be 2 * n_blocks = " + std::to_string(layers));
+    for (int l = 0; l < count; l++)
+        if (a[l] < -apz::ACT_EXP_MAX || a[l] > apz::ACT_EXP_MAX)
+            return fail(APZ_E_ARG, "activation exponents must lie in [-100, 100]");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    std::vector<int> eff(count);
+    for (int l = 0; l < count; l++)
+        if (int rc = clamp_act_exponent(e, e->convs[l + 1], a[l], &eff[l])) return rc;
+    drop_forward_graphs(e);                       // a captured launch sequence holds the old exponents
+    for (int l = 0; l < count; l++) e->convs[l + 1].act_exp = eff[l];
+    return APZ_OK;
+}
+
+int apz_get_trunk_act_exponents(apz_engine* e, int* a, int count) {
+    if (!e || !a) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    if (int rc = act_scale_supported(e)) return rc;
+    const int layers = (int)e->convs.size() - 1;
+    if (count != layers) return fail(APZ_E_ARG, "activation exponents: count must be 2 * n_blocks = " + std::to_string(layers));
+    for (int l = 0; l < count; l++) a[l] = e->convs[l + 1].act_exp;
+    return APZ_OK;
+}
+
+int apz_set_act_scale_auto(apz_engine* e, int on) {
+    if (!e) return fail(APZ_E_ARG, "null engine");
+    EngineLock guard(e->submit_lock);
+    if (int rc = act_scale_supported(e)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (on)
+        if (int rc = act_scale_buffers(e)) return rc;
+    e->act_auto = on != 0;
+    return APZ_OK;
+}
+
+int apz_calibrate_trunk_planes(apz_engine* e, const float* planes_host, int n, float* layer_max_out, int count) {
+    if (!e || !planes_host) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    return calibrate_trunk(e, n, layer_max_out, count, [&]() -> int {
+        const size_t pin = (size_t)n * e->cfg.c_in * e->hw * sizeof(float);
+        std::memcpy(e->h_planes, planes_host, pin);
+        HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, pin, hipMemcpyHostToDevice, e->stream));
+        return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
+    });
+}
+
+int apz_calibrate_trunk_codes(apz_engine* e, const uint8_t* codes_host, int n, float* layer_max_out, int count) {
+    if (!e || !codes_host) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    return calibrate_trunk(e, n, layer_max_out, count, [&]() -> int {
+        std::memcpy(e->h_codes, codes_host, (size_t)n * e->code_stride);
+        HIP_TRY(hipMemcpyAsync(e->codes, e->h_codes, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
+        if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, e->probs, e->values, nullptr, nullptr, e->codes);
+        if (int r = apz_encode_planes(e, e->codes, n, e->cfg.c_in, e->planes)) return r;
+        return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
+    });
+}
 
 int apz_test_select_trunk(apz_engine* e, int kind) {
     if (e) {

@@ -91,7 +91,34 @@ __device__ unsigned long long apz_wino3h16_stamps[4 * 8 * 12];   // [workgroup 4
 //                   because this library is built with fp32 denormals enabled (the compiler's default for gfx950;
 //                   no flush-to-zero flag in build.py) and while a + k <= 149.  A maximum of 1e-30 has a = 107: 2^-125
 //                   at k = 18.  A partial maximum of +inf sets the overflow word.
-enum { WINO3H16_PLAIN = 0, WINO3H16_STATS = 1, WINO3H16_DGRAD = 2 };
+//   WINO3H16_PLAIN_SCALED  the self-play kernel with a STATIC input scale (RELU true): `aux_n` is not a count but the
+//                   layer's exponent a, |a| <= ACT_EXP_MAX, chosen on the host (a calibration forward, or the response to
+//                   an overflow) and the same for every launch until the host changes it -- so a board's bits depend on a,
+//                   never on the other boards of its batch.  As in DGRAD the raw tiles are multiplied by 2^a before the
+//                   transform and 2^-a goes into the 1 / S of the bias FMA (both exact); no `aux` folding, no barrier in
+//                   front of the first item.  Bias, residual, ReLU, the non-finite check and the overflow word are
+//                   WINO3H16_PLAIN's.  The host keeps 2^-a / S a normal float (apz_set_trunk_act_exponents clamps a), and it
+//                   launches WINO3H16_PLAIN itself for a = 0.
+enum { WINO3H16_PLAIN = 0, WINO3H16_STATS = 1, WINO3H16_DGRAD = 2, WINO3H16_PLAIN_SCALED = 3 };
+
+// WINO3H16_PLAIN_SCALED: where the host puts a layer's calibration maximum m = max |input|, and why.  The split is proven
+// for max |x| 2^a < 655 (|V| <= 100 max |x| must stay below the fp16 limit 65 504).  DGRAD's window [2^7, 2^8) fits a scale
+// taken from the EXACT maximum of the tensor the launch reads.  A static exponent is taken from one calibration batch and
+// then meets positions that were not in it, so the window sits three binades lower: a = ACT_WINDOW_LOG2 - floor(log2 m)
+// puts m 2^a into [2^4, 2^5) -- at least 655 / 32 = 20 times headroom above the calibration maximum, and the lo term of
+// the split stays a normal fp16 number (full 22-bit operands) for inputs down to 2^4 2^-7 = 2^-3 after scaling, 7 binades
+// below the maximum (unscaled, that floor of 2^-3 is absolute: DESIGN.md section 4).
+constexpr int ACT_WINDOW_LOG2 = 4;
+constexpr int ACT_EXP_MAX = 100;          // |a| <= 100: 2^a and 2^-a are normal floats
+
+// a with m 2^a in [2^ACT_WINDOW_LOG2, 2^(ACT_WINDOW_LOG2 + 1)); 0 for m == 0; clamped to |a| <= ACT_EXP_MAX.  m finite, >= 0.
+inline int act_exponent_for(float m) {
+    if (!(m > 0.f)) return 0;
+    int ex;
+    std::frexp((double)m, &ex);           // m = f 2^ex, f in [0.5, 1): floor(log2 m) = ex - 1 (subnormal floats included)
+    const int a = ACT_WINDOW_LOG2 - (ex - 1);
+    return a < -ACT_EXP_MAX ? -ACT_EXP_MAX : (a > ACT_EXP_MAX ? ACT_EXP_MAX : a);
+}
 
 // a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as Wino3H::scale_for(0)); clamped to [-64, 110]: 2^110 and 2^-110 are
 // normal floats, and maxima down to 2^-103 (1e-31) still reach the window.  (A maximum of +inf -- the launch sets the
@@ -109,8 +136,9 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                                                                float* __restrict__ out, int n, unsigned* __restrict__ flag,
                                                                void* __restrict__ aux, int aux_n) {
     using T = Wino3H16;
-    constexpr bool STATS = FORM == WINO3H16_STATS, DGRAD = FORM == WINO3H16_DGRAD;
-    static_assert(FORM == WINO3H16_PLAIN || !RELU, "the training forms have no ReLU");
+    constexpr bool STATS = FORM == WINO3H16_STATS, DGRAD = FORM == WINO3H16_DGRAD, SCALED = FORM == WINO3H16_PLAIN_SCALED;
+    static_assert(FORM == WINO3H16_PLAIN || SCALED || !RELU, "the training forms have no ReLU");
+    static_assert(!SCALED || RELU, "the scaled form is a self-play form");
     static_assert(!STATS || !RESID, "STATS: bias only");
 #ifdef APZ_WINO3H_STAMPS
     // phases as trunk15_wino3h.h: 0 item prologue, 1 chunk barrier waits, 2 chunk bodies, 3 staging + stores, 4 epilogue first
@@ -165,6 +193,10 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
         aux_inf = !(m <= 3.4028234664e38f);
         xsc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
         xisc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
+    }
+    if constexpr (SCALED) {                           // the host's exponent: a kernel argument, the same in every wave
+        xsc = __builtin_bit_cast(float, (unsigned)(127 + aux_n) << 23);
+        xisc = __builtin_bit_cast(float, (unsigned)(127 - aux_n) << 23);
     }
 
     const unsigned plane_b = T::GPLANE * 4;
@@ -275,7 +307,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     auto tslice = [&](int vpar, auto KK) {
         constexpr int K = decltype(KK)::value;
         char* vp = vbase + vpar * T::V_BYTES + tv_off;
-        if constexpr (DGRAD && K == 0) {
+        if constexpr ((DGRAD || SCALED) && K == 0) {
 #pragma unroll
             for (int r = 0; r < 4; r++) raw[r] *= xsc;      // exact: a power of two
         }
@@ -468,7 +500,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                 if (RESID && s + 1 < 4) resid_request(s + 1);
                 const int ch = row_chan(s, co16);
                 const float bv = bias[ch];
-                const float is = DGRAD ? bias[128 + ch] * xisc : bias[128 + ch];   // 1 / S of the channel (a power of two)
+                const float is = (DGRAD || SCALED) ? bias[128 + ch] * xisc : bias[128 + ch];   // 1 / S of the channel (a power of two)
                 float* sp = sw + (cosel * 2 + gbd) * T::SPLANE + (4 * gty) * T::SROW + 4 * gtx;
                 f32x4 y[4];
 #pragma unroll

@@ -135,6 +135,12 @@ class TrainPipeline(object):
         self.train_arith = conf.get("train_arith", "f32")
         if self.train_arith not in ("f32", "f16x2"):
             raise ValueError("train_arith must be 'f32' or 'f16x2', not %r" % (self.train_arith,))
+        # act_scale: the static activation exponents of the self-play evaluator's f16x2 trunk kernel (PolicyValueNet.
+        # calibrate_trunk).  "off" (default): untouched, all 0.  "auto": the evaluators lower their exponents when a forward
+        # overflows, and the self-play evaluator is calibrated on its most recent code batch after every weight installation.
+        self.act_scale = conf.get("act_scale", "off")
+        if self.act_scale not in ("off", "auto"):
+            raise ValueError("act_scale must be 'off' or 'auto', not %r" % (self.act_scale,))
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -176,6 +182,10 @@ class TrainPipeline(object):
                                      temp=self.temp, base_seed=seed, pipeline=2,
                                      forced_opening=(self.board_width == 15 and self.board_height == 15),
                                      index_offset=self.rank, index_stride=self.world)
+        if self.act_scale == "auto":
+            self.policy_value_net.set_act_scale_auto(True)
+            if eval_net is not None and eval_net is not self.policy_value_net:
+                eval_net.set_act_scale_auto(True)
         self.keep_replica_buffers = bool(conf.get("replica_buffers", False))    # every rank keeps the replay buffer (host RAM x world)
         self._taken = 0
         self._rng = random.Random(seed)
@@ -245,6 +255,26 @@ class TrainPipeline(object):
         """train_arith f16x2: the update record carries the trainer's count of steps repeated on the exact kernels"""
         if self.train_arith == "f16x2":
             rec["trunk_overflows"] = int(getattr(trainer, "trunk_overflows", 0))
+
+    def _note_act_scale(self, rec):
+        """Every round / batch record carries the self-play evaluator's count of forwards repeated on the exact kernel
+        (evaluators without such a count: left out); act_scale "auto": its current activation exponents too."""
+        net = self.policy_value_net
+        if hasattr(net, "trunk_overflows"):
+            rec["eval_trunk_overflows"] = int(net.trunk_overflows())
+        if self.act_scale == "auto":
+            rec["act_exponents"] = [int(a) for a in net.trunk_act_exponents()]
+
+    def _calibrate_after_install(self):
+        """act_scale "auto": new weights move the activation ranges -- calibrate the self-play evaluator on the most
+        recent self-play code batch (none yet: skipped; the overflow response still holds)."""
+        if self.act_scale != "auto":
+            return
+        codes = getattr(self.engine, "last_codes", None)
+        if codes is None or not len(codes):
+            return
+        cap = int(getattr(self.policy_value_net, "batchsize", len(codes)))
+        self.policy_value_net.calibrate_trunk(codes=codes[:cap])
 
     def policy_update(self, trainer=None, kl_net=None):
         """train_mxnet.py:194-240 (rank 0 of a multi-rank run; see `_exchange_update` / `_trainer_main`).  Lock step: the
@@ -324,6 +354,9 @@ class TrainPipeline(object):
                 self.collect_selfplay_data_ai(self.play_batch_size)
             rec = {"batch": i + 1, "episode_len": self.episode_len, "buffer": len(self.data_buffer)}
             self._exchange_update(rec)
+            if "loss" in rec:                          # the evaluator holds new weights
+                self._calibrate_after_install()
+            self._note_act_scale(rec)
             if lead and (i + 1) % 50 == 0:
                 os.makedirs(self.model_dir, exist_ok=True)
                 self.policy_value_net.save_model(os.path.join(self.model_dir, "current_policy.model"))
@@ -389,6 +422,8 @@ class TrainPipeline(object):
                         self.board_width, self.board_height, self.batch_size, n_blocks=net._n_blocks,
                         n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, device=net._device)
                     self._own_eval_net = True
+                    if self.act_scale == "auto":
+                        kl_net.set_act_scale_auto(True)
             elif kl_net is None:
                 kl_net = self._eval_net = net
             with ctx:
@@ -504,6 +539,7 @@ class TrainPipeline(object):
         else:
             net.set_params({k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in got.items()},
                            **({"_keep_trainer": True} if self._custom_net else {}))
+        self._calibrate_after_install()
         self.weights_version = version
         self.weight_broadcasts += 1
 
@@ -593,6 +629,7 @@ class TrainPipeline(object):
             if version > self.weights_version:
                 self._install_weights(version, fresh[1] if fresh else None)
                 rec.update(loss=head[3], entropy=head[4], kl=head[5], lr_multiplier=head[6])
+            self._note_act_scale(rec)
             self.round_log.append((time.time(), int(self.engine.stats["leaf_evals"])))
             self.history.append(rec)
             stop = head[0] == 1.0

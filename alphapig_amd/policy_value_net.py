@@ -25,6 +25,31 @@ class EvaluatorError(RuntimeError):
     pass
 
 
+# The rule of the f16x2 trunk kernel's static activation exponents, restated from csrc/trunk15_wino3h16.h (ACT_WINDOW_LOG2,
+# ACT_EXP_MAX, act_exponent_for) and apz_engine.hip (clamp_act_exponent): what apz_calibrate_trunk_* computes from a
+# layer's maximum.  For documentation, tools and tests -- the engine does not call it.
+ACT_WINDOW_LOG2 = 4
+ACT_EXP_MAX = 100
+
+
+def act_exponent_for(m, k_min=None, k_max=None):
+    """The exponent a for a layer whose input maximum is m: a = 4 - floor(log2 m), so that m 2^a lies in [2^4, 2^5); 0 for
+    m == 0; |a| <= 100.  k_min / k_max: the smallest / largest k of the layer's weight scales S[co] = 2^k -- a is then
+    also clamped to -126 <= a + k <= 126, where 2^-a / S[co] is a normal float.  inf / NaN: ValueError (the engine
+    refuses such a calibration and leaves its exponents alone)."""
+    m = float(m)
+    if not np.isfinite(m) or m < 0.0:
+        raise ValueError("a layer maximum must be finite and >= 0, not %r" % (m,))
+    if m == 0.0:
+        a = 0
+    else:
+        a = ACT_WINDOW_LOG2 - (int(np.frexp(m)[1]) - 1)        # m = f 2^e, f in [0.5, 1): floor(log2 m) = e - 1
+    a = max(-ACT_EXP_MAX, min(ACT_EXP_MAX, a))
+    if a != 0 and k_min is not None and k_max is not None:
+        a = max(-126 - int(k_min), min(126 - int(k_max), a))
+    return a
+
+
 class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto"):
@@ -347,6 +372,46 @@ class PolicyValueNet(object):
         (trunk_arith "f16x2"; always 0 for the other arithmetics)."""
         return int(self.L.apz_trunk_overflows(self._h))
 
+    # ---- static activation exponents of the f16x2 trunk kernel (15x15 / 128-filter residual net; apz_set_trunk_act_exponents)
+    def _n_trunk_convs(self):
+        return 2 * self._n_blocks if self.net_kind == "resnet" else 0
+
+    def calibrate_trunk(self, planes=None, codes=None):
+        """One forward of the batch (planes [n, C, H, W] or codes uint8 [n, code_stride], at most batch_size boards) on the
+        exact-fp32 kernels; sets the exponent of every trunk convolution from the maximum of its input, a = 4 -
+        floor(log2 max) -> the maxima, float32 [2 * n_blocks].  Raises EvaluatorError, exponents unchanged, if a maximum is
+        not finite or the engine has no such exponents (another arithmetic than "f16x2", 8x8 boards, APZ_F16X2_K8=1)."""
+        if (planes is None) == (codes is None):
+            raise ValueError("calibrate_trunk takes planes or codes")
+        m = np.zeros(max(self._n_trunk_convs(), 1), dtype=np.float32)
+        cnt = self._n_trunk_convs()
+        if planes is not None:
+            x = np.ascontiguousarray(planes, dtype=np.float32)
+            if x.ndim != 4 or x.shape[1:] != (self.channelnum, self.board_height, self.board_width):
+                raise ValueError("planes must be [n, %d, %d, %d]" % (self.channelnum, self.board_height, self.board_width))
+            self._ck(self.L.apz_calibrate_trunk_planes(self._h, as_ptr(x, C.c_float), x.shape[0], as_ptr(m, C.c_float), cnt))
+        else:
+            c = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, self.code_stride)
+            self._ck(self.L.apz_calibrate_trunk_codes(self._h, as_ptr(c, C.c_uint8), c.shape[0], as_ptr(m, C.c_float), cnt))
+        return m[:cnt]
+
+    def trunk_act_exponents(self):
+        """The exponents in force, graph order (convA1, convB1, convA2, ...); all 0 until set or calibrated."""
+        cnt = self._n_trunk_convs()
+        a = np.zeros(max(cnt, 1), dtype=np.int32)
+        self._ck(self.L.apz_get_trunk_act_exponents(self._h, as_ptr(a, C.c_int32), cnt))
+        return [int(v) for v in a[:cnt]]
+
+    def set_trunk_act_exponents(self, seq):
+        a = np.ascontiguousarray(list(seq), dtype=np.int32)
+        self._ck(self.L.apz_set_trunk_act_exponents(self._h, as_ptr(a if a.size else np.zeros(1, np.int32), C.c_int32),
+                                                    int(a.size)))
+
+    def set_act_scale_auto(self, on):
+        """on: a forward that overflows the fp16 range lowers the exponents from its exact repeat, so that the next one of
+        the same kind does not repeat (default off)."""
+        self._ck(self.L.apz_set_act_scale_auto(self._h, int(bool(on))))
+
     def prewarm(self, n, iters):
         """Enqueue `iters` forwards of n empty boards on the engine stream, without waiting (GPU-only warm-up of a
         measurement: clocks, runtime pools; results are never read)."""
@@ -424,6 +489,26 @@ class LanedEvaluator(object):
 
     def trunk_overflows(self):
         return sum(ln.trunk_overflows() for ln in self.lanes)
+
+    def calibrate_trunk(self, planes=None, codes=None):
+        """Calibrates lane 0 and gives every other lane its exponents (same weights, same kernels: same bits on any lane)."""
+        m = self.lanes[0].calibrate_trunk(planes=planes, codes=codes)
+        exps = self.lanes[0].trunk_act_exponents()
+        for ln in self.lanes[1:]:
+            ln.set_trunk_act_exponents(exps)
+        return m
+
+    def trunk_act_exponents(self):
+        return self.lanes[0].trunk_act_exponents()
+
+    def set_trunk_act_exponents(self, seq):
+        seq = list(seq)
+        for ln in self.lanes:
+            ln.set_trunk_act_exponents(seq)
+
+    def set_act_scale_auto(self, on):
+        for ln in self.lanes:
+            ln.set_act_scale_auto(on)
 
     def params(self):
         return self.lanes[0].params()

@@ -102,6 +102,9 @@ class SelfPlayEngine(object):
         # outputs are fed to the trees: which slot asked for which position and what the evaluator answered (the parity
         # tests record the games they replay through the sequential oracle with it; None costs nothing)
         self.tap = None
+        # the code batch of the most recent evaluation (a reference, no copy): what the training pipeline calibrates the
+        # evaluator's activation exponents on (pipeline.TrainPipeline, act_scale "auto")
+        self.last_codes = None
         self._limit = None
         # optional threading.Event: while it is CLEAR run_steps starts no new scheduler round (evaluations already in flight
         # finish; the next round begins when it is set again) -- the training pipeline's trainer thread holds it clear
@@ -307,6 +310,8 @@ class SelfPlayEngine(object):
 
     def _dispatch(self, gi, ids, codes):
         """Start the evaluation of one group's leaves -> a ticket for _collect."""
+        if len(ids):
+            self.last_codes = codes
         if self._async and len(ids) <= getattr(self.evaluator, "batchsize", len(ids)):
             slot = gi % self._n_slots
             t0 = time.perf_counter()

@@ -352,6 +352,38 @@ int apz_set_profiling(apz_engine *e, int on);
 #define APZ_ARITH_F16X2 2
 int apz_set_trunk_arith(apz_engine *e, int arith);
 long apz_trunk_overflows(apz_engine *e);
+/* Static per-layer activation exponents of the APZ_ARITH_F16X2 trunk kernel (15x15 / 128-filter residual net, batches of
+ * more than 32 boards; csrc/trunk15_wino3h16.h, WINO3H16_PLAIN_SCALED).  Unscaled, the two-term split holds activations
+ * between 2^-3 (below it the lo term is a subnormal fp16 number with an absolute 2^-25 error) and ~655 (above it the
+ * transformed tile overflows and the forward is repeated on the exact kernel -- every time).  With exponent a the kernel
+ * multiplies the input of trunk convolution l by 2^a before the transform and folds 2^-a into the channel's 1 / S: both
+ * exact, so the layer computes the same function with its window moved.  Activations in device memory stay unscaled fp32.
+ *   a[count], count = 2 * n_blocks, graph order (convA1, convB1, convA2, ...); all 0 by default, and a layer with
+ *   exponent 0 runs the unscaled kernel: an engine on which none of these calls is made behaves exactly as before.
+ * The exponents are engine state: apz_load_weights and apz_load_weights_dev keep them.  They are STATIC -- changed only by
+ * the calls below -- so a board's bits do not depend on its batch; a changed exponent changes the low-order bits of that
+ * layer (same accuracy class).  set: |a| <= 100, additionally clamped so that 2^-a / S[co] stays a normal float for every
+ * output channel of the layer as loaded (get returns the values in force; apz_load_weights clamps again, the device-side
+ * refresh does not look).  APZ_E_UNSUPPORTED, with the reason in apz_last_error, for another arithmetic than APZ_ARITH_F16X2,
+ * for an engine created under APZ_F16X2_K8=1 and for 8x8 boards (csrc/conv8_split.h is in range up to 65 504 already). */
+int apz_set_trunk_act_exponents(apz_engine *e, const int *a, int count);
+int apz_get_trunk_act_exponents(apz_engine *e, int *a, int count);
+/* Calibration: one forward of the given batch (planes_host as for apz_forward_host, codes_host as for
+ * apz_forward_codes_host) on the exact-fp32 kernels, measuring m_l = max |input of trunk convolution l| (csrc/act_max.h),
+ * then a_l = 4 - floor(log2 m_l): m_l 2^a in [2^4, 2^5), 20x headroom below the overflow bound for positions that were not in
+ * the batch (derivation: ACT_WINDOW_LOG2 in csrc/trunk15_wino3h16.h); a_l = 0 for m_l = 0.  layer_max_out (may be NULL)
+ * receives the `count` maxima.  A maximum that is not finite: error, all exponents unchanged.  The maxima are taken behind
+ * the ReLU, which hides a NaN, so the call then runs the batch once on the f16x2 kernel with the new exponents: if that
+ * raises the overflow word (a layer is not finite in exact fp32 either) the call fails and the exponents are unchanged.
+ * Synchronous; does not count as an overflow; the forwards' results are discarded. */
+int apz_calibrate_trunk_planes(apz_engine *e, const float *planes_host, int n, float *layer_max_out, int count);
+int apz_calibrate_trunk_codes(apz_engine *e, const uint8_t *codes_host, int n, float *layer_max_out, int count);
+/* on != 0 (default off): the exact repeat of an overflowed forward (in the collecting entry points listed above) also
+ * measures the maxima and sets a_l = min(a_l, 4 - floor(log2 m_l)) -- exponents only ever go down, and stay as they are if
+ * a maximum is not finite.  apz_trunk_overflows counts that forward; the next forward of the same batch runs on the f16x2
+ * kernel without a repeat.  apz_prewarm, apz_conv3x3_bench and apz_layer_io never adjust exponents (apz_conv3x3_bench on a
+ * trunk layer runs the form the layer's current exponent selects). */
+int apz_set_act_scale_auto(apz_engine *e, int on);
 #define APZ_TRUNK_DIRECT 0
 #define APZ_TRUNK_WINOGRAD 3            /* default: batches of <= 32 boards take the small-batch form (csrc/trunk15_wino3s.h) */
 #define APZ_TRUNK_WINOGRAD_BATCHED 4    /* ... the batched form for every batch size (the tests hold the two forms to bit equality) */

@@ -25,13 +25,16 @@ def main():
     ap.add_argument("--eval-games", type=int, default=10)
     ap.add_argument("--pure-playouts", type=int, default=1000)
     ap.add_argument("--train-arith", default="f32", choices=("f32", "f16x2"), help="the trainer's trunk arithmetic (HipTrainer trunk_arith)")
+    ap.add_argument("--act-scale", default="off", choices=("off", "auto"),
+                    help="the self-play evaluator's static activation exponents (TrainPipeline act_scale)")
     args = ap.parse_args()
     conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
                 n_playout=400, c_puct=5, buffer_size=2198800, batch_size=128, epochs=8, kl_targ=0.02,
                 check_freq=10 ** 9, pure_mcts_playout_num=args.pure_playouts, game_batch_num=args.games,
                 play_batch_size=1, concurrent_games=1024, n_blocks=10, n_filter=128, eval_games=args.eval_games,
                 model_dir="/tmp/apz_models_15", async_update=not args.lock_step, round_seconds=0.25,
-                max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith)
+                max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith,
+                act_scale=args.act_scale)
     tp = TrainPipeline(conf, seed=1)
     t0 = time.time()
     if args.lock_step:
@@ -64,6 +67,10 @@ def main():
                 rec.update(loss=round(ups[-1]["loss"], 4), entropy=round(ups[-1]["entropy"], 4), kl=round(ups[-1]["kl"], 5))
                 if "trunk_overflows" in ups[-1]:
                     rec["trunk_overflows"] = ups[-1]["trunk_overflows"]
+            if tp.history:                      # the self-play evaluator's repeats (and exponents with --act-scale auto)
+                for k in ("eval_trunk_overflows", "act_exponents"):
+                    if k in tp.history[-1]:
+                        rec[k] = tp.history[-1][k]
             print(json.dumps(rec), flush=True)
             last_t, last_leaf, last_busy, last_upd, last_games = now, leaf, busy, len(iv), games
 
@@ -80,7 +87,10 @@ def main():
                       "self_play_held_s": round(tp.engine.timers.get("gate_s", 0.0), 2), "train_arith": tp.train_arith,
                       "policy_update_ms_whole_run": round(1e3 * sum(b - a for a, b in tp.update_intervals) /
                                                           max(1, len(tp.update_intervals)), 1),
-                      "trunk_overflows": getattr(getattr(tp, "_async_trainer", None), "trunk_overflows", None)}), flush=True)
+                      "trunk_overflows": getattr(getattr(tp, "_async_trainer", None), "trunk_overflows", None),
+                      "act_scale": tp.act_scale, "eval_trunk_overflows": tp.policy_value_net.trunk_overflows(),
+                      "act_exponents": tp.policy_value_net.trunk_act_exponents() if tp.act_scale == "auto" else None}),
+          flush=True)
     tp.close()
 
 

@@ -2,6 +2,9 @@
 // its predecessor trunk15_wino3h_kernel (8-channel chunks, four products) and the exact-fp32 trunk15_wino3_kernel: random
 // data, HIP events, kernels interleaved round by round on the same box; outputs compared with a naive double-precision kernel
 // of the same Winograd-domain definition on the SAME fp32 weights U.  APZ_ACT_SCALE=<x> multiplies the activations.
+// Fourth column: the 16-channel kernel's form with a static input exponent (WINO3H16_PLAIN_SCALED), a = APZ_ACT_EXP or, by
+// default, what a calibration on this data would choose (its maximum is 1.4 x APZ_ACT_SCALE) -- the same-process A/B of the
+// scaled against the unscaled form.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Ialphapig_amd/csrc [-DAPZ_WINO3H_STAMPS] tools/wino3h16_bench.hip -o tools/_build/wino3h16_bench
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -85,6 +88,12 @@ int main(int argc, char** argv) {
     using TH = apz::Wino3H;
     const bool quick = getenv("APZ_NO_TIMING") != nullptr;
     const float act_scale = getenv("APZ_ACT_SCALE") ? (float)atof(getenv("APZ_ACT_SCALE")) : 1.f;
+    constexpr int NK = 4;
+    const int act_exp = getenv("APZ_ACT_EXP") ? atoi(getenv("APZ_ACT_EXP")) : apz::act_exponent_for(1.4f * act_scale);
+    if (act_exp < -apz::ACT_EXP_MAX || act_exp > apz::ACT_EXP_MAX) { printf("APZ_ACT_EXP out of range\n"); return 1; }
+    printf("scaled form: exponent %d\n", act_exp);
+    CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3h16_kernel<true, true, apz::WINO3H16_PLAIN_SCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, TK::LDS_BYTES));
+    CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3h16_kernel<false, true, apz::WINO3H16_PLAIN_SCALED>, hipFuncAttributeMaxDynamicSharedMemorySize, TK::LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3h16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TK::LDS_BYTES));
@@ -93,12 +102,12 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute((const void*)apz::trunk15_wino3h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TH::LDS_BYTES));
     const int nmax = 2048;
     const size_t act = (size_t)nmax * 128 * 240;
-    float *in, *res, *out[3], *upk, *bias, *biash, *probe;
+    float *in, *res, *out[4], *upk, *bias, *biash, *probe;
     double* outd;
     void *upkk, *upkh;
     unsigned* flag;
     CK(hipMalloc(&in, act * 4)); CK(hipMalloc(&res, act * 4));
-    for (int k = 0; k < 3; k++) CK(hipMalloc(&out[k], act * 4));
+    for (int k = 0; k < NK; k++) CK(hipMalloc(&out[k], act * 4));
     const int nref = 1030;
     CK(hipMalloc(&outd, (size_t)nref * 128 * 240 * 8));
     CK(hipMalloc(&upk, T2::UPK_FLOATS * 4)); CK(hipMalloc(&bias, 128 * 4)); CK(hipMalloc(&biash, 256 * 4));
@@ -143,11 +152,14 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(bias, hb.data(), 512, hipMemcpyHostToDevice));
     CK(hipMemcpy(biash, hb.data(), 1024, hipMemcpyHostToDevice));
 
-    // kern: 0 = fp16 x 2 with 16-channel chunks, 1 = fp16 x 2 with 8-channel chunks, 2 = exact fp32
+    // kern: 0 = fp16 x 2 with 16-channel chunks, 1 = fp16 x 2 with 8-channel chunks, 2 = exact fp32, 3 = 0 with the input exponent
     auto launch = [&](int kern, int resid, int grid, int n, float* o) {
         if (kern == 0) {
             if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<true>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, 0);
             else hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<false>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, 0);
+        } else if (kern == 3) {
+            if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<true, true, apz::WINO3H16_PLAIN_SCALED>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, act_exp);
+            else hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<false, true, apz::WINO3H16_PLAIN_SCALED>), dim3(grid), dim3(512), TK::LDS_BYTES, 0, in, upkk, biash, res, o, n, flag, nullptr, act_exp);
         } else if (kern == 1) {
             if (resid) hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<true>), dim3(grid), dim3(512), TH::LDS_BYTES, 0, in, upkh, biash, res, o, n, flag);
             else hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<false>), dim3(grid), dim3(512), TH::LDS_BYTES, 0, in, upkh, biash, res, o, n, flag);
@@ -156,11 +168,11 @@ int main(int argc, char** argv) {
             else hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false>), dim3(grid), dim3(512), T3::LDS_BYTES, 0, in, upk, bias, res, o, n);
         }
     };
-    const char* kname[3] = {"f16x2-k16", "f16x2-k8", "fp32"};
+    const char* kname[NK] = {"f16x2-k16", "f16x2-k8", "fp32", "f16x2-k16-scaled"};
 
     if (getenv("APZ_PROFILE")) {          // rocprofv3 runs: 12 launches of each variant at 512 boards, nothing else
         for (int it = 0; it < 12; it++)
-            for (int kern = 0; kern < 3; kern++)
+            for (int kern = 0; kern < NK; kern++)
                 for (int resid = 0; resid < 2; resid++) launch(kern, resid, 256, 512, out[kern]);
         CK(hipDeviceSynchronize());
         printf("RESULT PROFILE\n");
@@ -169,16 +181,16 @@ int main(int argc, char** argv) {
     // ---- cross-check against the naive double kernel at ragged sizes
     int bad = 0;
     const int check_sizes[7] = {1, 7, 64, 96, 512, 515, 1030};
-    std::vector<float> ha[3];
+    std::vector<float> ha[NK];
     std::vector<double> hd;
     for (int ci = 0; ci < (quick ? 3 : 7); ci++) {
         const int n = check_sizes[ci];
         const int grid = getenv("APZ_GRID") ? atoi(getenv("APZ_GRID")) : apz::wino3_grid(n, 256);
         for (int resid = 0; resid < 2; resid++) {
             const size_t cnt = (size_t)n * 128 * 240;
-            for (int k = 0; k < 3; k++) CK(hipMemset(out[k], 0xff, cnt * 4));
+            for (int k = 0; k < NK; k++) CK(hipMemset(out[k], 0xff, cnt * 4));
             hipLaunchKernelGGL(wino_ref_kernel, dim3((unsigned)((n * 128 * 16 + 255) / 256)), dim3(256), 0, 0, in, upk, bias, res, outd, n, resid);
-            for (int k = 0; k < 3; k++) launch(k, resid, grid, n, out[k]);
+            for (int k = 0; k < NK; k++) launch(k, resid, grid, n, out[k]);
             CK(hipGetLastError());
             CK(hipDeviceSynchronize());
             hd.resize(cnt);
@@ -186,25 +198,26 @@ int main(int argc, char** argv) {
             unsigned fl = 0;
             CK(hipMemcpy(&fl, flag, 4, hipMemcpyDeviceToHost));
             CK(hipMemset(flag, 0, 4));
-            double emax[3] = {0, 0, 0}, ss[3] = {0, 0, 0}, scale = 0;
+            double emax[NK] = {0, 0, 0, 0}, ss[NK] = {0, 0, 0, 0}, scale = 0;
             size_t worst = 0, nonfinite = 0;
-            for (int k = 0; k < 3; k++) {
+            for (int k = 0; k < NK; k++) {
                 ha[k].resize(cnt);
                 CK(hipMemcpy(ha[k].data(), out[k], cnt * 4, hipMemcpyDeviceToHost));
                 for (size_t i = 0; i < cnt; i++) {
                     if ((i % 240) / 16 >= 15) continue;
-                    if (!std::isfinite(ha[k][i])) { if (k == 0) nonfinite++; continue; }
+                    if (!std::isfinite(ha[k][i])) { if (k == 0 || k == 3) nonfinite++; continue; }
                     const double d = std::fabs((double)ha[k][i] - hd[i]);
                     if (d > emax[k]) { emax[k] = d; if (k == 0) worst = i; }
                     ss[k] += d * d;
                     if (k == 0) scale = std::max(scale, std::fabs(hd[i]));
                 }
             }
-            // (the flag word is shared by both split kernels: neither may raise it on ordinary data)
-            const bool ok = nonfinite == 0 && emax[0] < 2e-5 * std::max(1.0, scale) && emax[1] < 2e-5 * std::max(1.0, scale) && (fl == 0);
+            // (the flag word is shared by the split kernels: none may raise it on ordinary data)
+            const bool ok = nonfinite == 0 && emax[0] < 2e-5 * std::max(1.0, scale) && emax[1] < 2e-5 * std::max(1.0, scale) &&
+                            emax[3] < 2e-5 * std::max(1.0, scale) && (fl == 0);
             if (!ok) bad++;
-            printf("check n=%5d resid=%d grid=%d: f16x2-k16 max err %.3e rms %.3e | f16x2-k8 %.3e rms %.3e | fp32 wino3 %.3e rms %.3e | scale %.2f nonfinite %zu flag %u %s (worst at board %zu ch %zu row %zu col %zu: %.6f vs %.6f)\n",
-                   n, resid, grid, emax[0], std::sqrt(ss[0] / cnt), emax[1], std::sqrt(ss[1] / cnt), emax[2], std::sqrt(ss[2] / cnt), scale, nonfinite, fl,
+            printf("check n=%5d resid=%d grid=%d: f16x2-k16 max err %.3e rms %.3e | f16x2-k8 %.3e rms %.3e | fp32 wino3 %.3e rms %.3e | f16x2-k16-scaled %.3e rms %.3e | scale %.2f nonfinite %zu flag %u %s (worst at board %zu ch %zu row %zu col %zu: %.6f vs %.6f)\n",
+                   n, resid, grid, emax[0], std::sqrt(ss[0] / cnt), emax[1], std::sqrt(ss[1] / cnt), emax[2], std::sqrt(ss[2] / cnt), emax[3], std::sqrt(ss[3] / cnt), scale, nonfinite, fl,
                    ok ? "OK" : "MISMATCH", worst / (128 * 240), (worst / 240) % 128, (worst % 240) / 16, worst % 16, ha[0][worst], hd[worst]);
         }
     }
@@ -249,11 +262,11 @@ int main(int argc, char** argv) {
     for (int si = 0; si < 5; si++) {
         const int n = sizes[si];
         const int grid = getenv("APZ_GRID") ? atoi(getenv("APZ_GRID")) : apz::wino3_grid(n, 256);
-        float best[3][2], sum[3][2];
-        for (int k = 0; k < 3; k++) for (int r = 0; r < 2; r++) best[k][r] = 1e9f, sum[k][r] = 0;
+        float best[NK][2], sum[NK][2];
+        for (int k = 0; k < NK; k++) for (int r = 0; r < 2; r++) best[k][r] = 1e9f, sum[k][r] = 0;
         const int rounds = 6, iters = 20;
         for (int r = 0; r < rounds; r++)
-            for (int kern = 0; kern < 3; kern++)
+            for (int kern = 0; kern < NK; kern++)
                 for (int resid = 0; resid < 2; resid++) {
                     for (int it = -3; it < iters; it++) {
                         if (it == 0) CK(hipEventRecord(e0, 0));
@@ -267,8 +280,8 @@ int main(int argc, char** argv) {
                     sum[kern][resid] += ms / iters;
                 }
         printf("time n=%5d grid=%3d:", n, grid);
-        for (int k = 0; k < 3; k++)
-            printf(" %s %.1f / %.1f us (mean %.1f / %.1f)%s", kname[k], best[k][0] * 1e3, best[k][1] * 1e3, sum[k][0] / rounds * 1e3, sum[k][1] / rounds * 1e3, k < 2 ? " |" : "\n");
+        for (int k = 0; k < NK; k++)
+            printf(" %s %.1f / %.1f us (mean %.1f / %.1f)%s", kname[k], best[k][0] * 1e3, best[k][1] * 1e3, sum[k][0] / rounds * 1e3, sum[k][1] / rounds * 1e3, k < NK - 1 ? " |" : "\n");
     }
 #ifdef APZ_WINO3H_STAMPS
     {
