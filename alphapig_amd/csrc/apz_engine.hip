@@ -22,6 +22,7 @@
 #include "trunk15_wino3b.h"
 #include "trunk15_wino3h.h"
 #include "trunk15_wino3h16.h"
+#include "trunk15_wino3hs.h"
 #include "conv8_split.h"
 #include "conv8_small.h"
 #include "wgrad_wino3.h"
@@ -134,7 +135,7 @@ struct apz_engine {
     bool small8 = false;    // 8x8 boards: conv8_kernel / head8_kernel (conv8_small.h)
     float* wfc_raw = nullptr;   // head8_kernel: the policy FullyConnected weight as stored, [hw][4 hw]
     int act_ps = 0, act_rs = 0;
-    bool lds_attr_set[45] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
+    bool lds_attr_set[49] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
     int conv_lds_set[16] = {0};
     // persistent sampler staging (apz_sample_moves_host)
     int32_t* smp_vis = nullptr;
@@ -159,6 +160,11 @@ struct apz_engine {
     float* w3s_slabs = nullptr;              // trunk15_wino3s_kernel: row partials of the position halves
     unsigned* w3s_tickets = nullptr;         // ... and the pairs' ticket words (each launch exchanges its epoch in: trunk15_wino3s.h)
     unsigned w3s_epoch = 0;                  // last epoch handed out; never 0, never repeated between two memsets of the words
+    // apz_set_trunk_uniform: APZ_ARITH_F16X2 batches of <= 32 boards run trunk15_wino3hs_kernel (the batched kernel's bits)
+    bool uniform_trunk = false;
+    float* w3hs_slabs = nullptr;             // ... its row partials and ticket words (trunk15_wino3hs.h), allocated at the first launch
+    unsigned* w3hs_tickets = nullptr;
+    unsigned w3hs_epoch = 0;                 // as w3s_epoch
     bool no_small_trunk = false;             // apz_test_select_trunk(APZ_TRUNK_WINOGRAD_BATCHED): tests compare the two forms
     bool no_quarter_trunk = false;           // apz_test_select_trunk(APZ_TRUNK_WINOGRAD_NO_QUARTER): 64-channel items for every batch
     int trunk_arith = APZ_ARITH_F32;         // apz_set_trunk_arith: APZ_ARITH_BF16X3 / _F16X2 = the split kernels for batches > 32
@@ -504,7 +510,44 @@ int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
     return APZ_OK;
 }
 
+// The small-batch form of the 16-channel split kernel (apz_set_trunk_uniform): 1 .. 32 boards, eight workgroups per board,
+// the batched kernel's weights, bias, overflow word and exponent -- and its bits (csrc/trunk15_wino3hs.h)
+template <bool RESID, bool SCALED>
+int launch_wino3hs_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    using T = apz::Wino3HS;
+    bool& configured = e->lds_attr_set[attr_slot];
+    if (!configured) {
+        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3hs_kernel<RESID, SCALED>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
+        configured = true;
+    }
+    if (!e->w3hs_slabs) {
+        HIP_TRY(hipMalloc((void**)&e->w3hs_slabs, T::slab_floats() * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&e->w3hs_tickets, T::counters() * sizeof(unsigned)));
+        e->w3hs_epoch = 0;
+    }
+    if (++e->w3hs_epoch == 0 || e->w3hs_epoch == 1) {
+        // first launch, or the 32-bit epoch wrapped: zero the words ON THE LAUNCH STREAM (ordered before the kernel)
+        e->w3hs_epoch = 1;
+        HIP_TRY(hipMemsetAsync(e->w3hs_tickets, 0, T::counters() * sizeof(unsigned), e->stream));
+    }
+    hipLaunchKernelGGL((apz::trunk15_wino3hs_kernel<RESID, SCALED>), dim3(T::grid(n)), dim3(512), T::LDS_BYTES, e->stream, in,
+                       (const void*)L.upk3h, L.bias3h, RESID ? resid : nullptr, out, n, e->ovf_cur, SCALED ? L.act_exp : 0,
+                       e->w3hs_slabs, e->w3hs_tickets, e->w3hs_epoch);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
 int launch_trunk_wino3(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    if (e->uniform_trunk && e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur && !e->f16x2_k8 &&
+        n <= apz::Wino3S::MAX_BOARDS && !e->no_small_trunk) {
+        if (L.act_exp != 0) {
+            if (resid) return launch_wino3hs_t<true, true>(e, 45, L, in, resid, out, n);
+            return launch_wino3hs_t<false, true>(e, 46, L, in, resid, out, n);
+        }
+        if (resid) return launch_wino3hs_t<true, false>(e, 47, L, in, resid, out, n);
+        return launch_wino3hs_t<false, false>(e, 48, L, in, resid, out, n);
+    }
     if (e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur &&
         (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
         if (e->f16x2_k8) {
@@ -991,7 +1034,7 @@ void apz_destroy(apz_engine* e) {
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
                    e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
-                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->amax_dev};
+                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->w3hs_slabs, e->w3hs_tickets, e->amax_dev};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1401,7 +1444,7 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     if (it != e->fwd_graphs.end()) {
         HIP_TRY(hipGraphLaunch(it->second, e->stream));
         e->last_n = n;
-    } else if (graphable && ++e->fwd_seen[key] >= 3 && e->w3s_epoch < 0xFFFF0000u) {
+    } else if (graphable && ++e->fwd_seen[key] >= 3 && e->w3s_epoch < 0xFFFF0000u && e->w3hs_epoch < 0xFFFF0000u) {
         // (third use: every lazy allocation / attribute / ticket reset of this shape has happened outside the capture)
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
@@ -2619,6 +2662,22 @@ int apz_test_select_trunk(apz_engine* e, int kind) {
     e->trunk_kernel = kind == APZ_TRUNK_DIRECT ? APZ_TRUNK_DIRECT : APZ_TRUNK_WINOGRAD;
     e->no_small_trunk = kind == APZ_TRUNK_WINOGRAD_BATCHED || kind == APZ_TRUNK_WINOGRAD_NO_QUARTER;
     e->no_quarter_trunk = kind == APZ_TRUNK_WINOGRAD_NO_QUARTER;
+    return APZ_OK;
+}
+
+int apz_set_trunk_uniform(apz_engine* e, int on) {
+    if (!e) return fail(APZ_E_ARG, "null engine");
+    EngineLock guard(e->submit_lock);
+    if (e->trunk_arith == APZ_ARITH_F32 || e->small8 || !e->ring) return APZ_OK;   // already uniform: one kernel family for every batch
+    if (e->trunk_arith == APZ_ARITH_BF16X3)
+        return fail(APZ_E_UNSUPPORTED, "the bf16 x 3 trunk kernel has no small-batch form: batches of <= 32 boards run exact fp32");
+    if (e->f16x2_k8)
+        return fail(APZ_E_UNSUPPORTED, "the 8-channel f16x2 kernel (APZ_F16X2_K8=1) has no small-batch form");
+    if ((on != 0) != e->uniform_trunk) {
+        drop_forward_graphs(e);                   // a captured launch sequence holds the other kernels ...
+        e->fwd_seen.clear();                      // ... and the next capture waits until this route's lazy set-up has happened
+    }
+    e->uniform_trunk = on != 0;
     return APZ_OK;
 }
 

@@ -141,6 +141,10 @@ class TrainPipeline(object):
         self.act_scale = conf.get("act_scale", "off")
         if self.act_scale not in ("off", "auto"):
             raise ValueError("act_scale must be 'off' or 'auto', not %r" % (self.act_scale,))
+        # uniform_trunk (default False): the evaluators this pipeline builds itself run batches of <= 32 boards on the
+        # small-batch f16x2 kernel, so that a game's bits do not depend on how many games share a forward
+        # (PolicyValueNet's uniform_trunk).  The trainer's internal evaluator is not concerned.
+        self.uniform_trunk = bool(conf.get("uniform_trunk", False))
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -176,7 +180,7 @@ class TrainPipeline(object):
         self.policy_value_net = policy_value_net or PolicyValueNet(
             self.board_width, self.board_height, max(self.batch_size, (concurrent + 1) // 2),
             n_blocks=conf.get("n_blocks", 10), n_filter=conf.get("n_filter", 128), model_params=init_model,
-            device=device, seed=seed)
+            device=device, seed=seed, uniform_trunk=self.uniform_trunk)
         self.engine = SelfPlayEngine(self.policy_value_net, self.board_width, self.board_height, self.n_in_row,
                                      n_games=concurrent, n_playout=self.n_playout, c_puct=self.c_puct,
                                      temp=self.temp, base_seed=seed, pipeline=2,
@@ -420,7 +424,8 @@ class TrainPipeline(object):
                 if kl_net is None:
                     kl_net = self._eval_net = PolicyValueNet(
                         self.board_width, self.board_height, self.batch_size, n_blocks=net._n_blocks,
-                        n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, device=net._device)
+                        n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, device=net._device,
+                        uniform_trunk=self.uniform_trunk)
                     self._own_eval_net = True
                     if self.act_scale == "auto":
                         kl_net.set_act_scale_auto(True)

@@ -52,7 +52,8 @@ def act_exponent_for(m, k_min=None, k_max=None):
 
 class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
-                 model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto"):
+                 model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
+                 uniform_trunk=False):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -63,7 +64,12 @@ class PolicyValueNet(object):
           "bf16x3" three bf16 terms, six products (csrc/trunk15_wino3b.h): round 4's form, kept for comparison;
           "auto"   (default) "f16x2" where such kernels exist (15x15 / 128-filter residual net; 8x8 boards), else "f32".
         8x8 boards (round 6): "f16x2" runs every convolution with a multiple of 64 input channels on the fp16 matrix pipe with
-        split operands (csrc/conv8_split.h), for EVERY batch size: a board's bits do not depend on the batch there."""
+        split operands (csrc/conv8_split.h), for EVERY batch size: a board's bits do not depend on the batch there.
+        uniform_trunk (default False): with "f16x2" on the 15x15 / 128-filter net, batches of <= 32 boards run the small-batch
+        form of the f16x2 kernel (csrc/trunk15_wino3hs.h, bit-equal to the batched kernel) instead of the exact-fp32 one, so
+        a position's bits no longer depend on how many boards share its forward (apz_set_trunk_uniform; forwards that
+        overflow are repeated on the exact kernel for the whole batch).  No effect with "f32" and on 8x8 boards (already
+        uniform); EvaluatorError with "bf16x3"."""
         self.L = _native.hip()
         self.board_width, self.board_height = int(board_width), int(board_height)
         self.batchsize = int(batch_size)
@@ -89,6 +95,9 @@ class PolicyValueNet(object):
         self.trunk_arith = trunk_arith
         if trunk_arith != "f32":                                     # before the weights are loaded: they are packed for it
             self._ck(self.L.apz_set_trunk_arith(self._h, {"bf16x3": 1, "f16x2": 2}[trunk_arith]))
+        self.uniform_trunk = bool(uniform_trunk)
+        if self.uniform_trunk:
+            self._ck(self.L.apz_set_trunk_uniform(self._h, 1))
         if model_params is None:
             model_params = weights.init_params(net_kind, self.board_height, self.board_width, self.channelnum,
                                                self._n_blocks, self._n_filter, seed=seed, style=init_style)
@@ -444,6 +453,7 @@ class LanedEvaluator(object):
 
     @classmethod
     def like(cls, net, n_lanes, **kw):
+        kw.setdefault("uniform_trunk", net.uniform_trunk)      # the lanes compute the bits of the net they stand beside
         """`net` plus n_lanes - 1 more PolicyValueNet handles built from its parameters."""
         extra = [PolicyValueNet(net.board_width, net.board_height, net.batchsize, n_blocks=net._n_blocks,
                                 n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, c_in=net.channelnum, device=net._device,

@@ -351,6 +351,23 @@ int apz_set_profiling(apz_engine *e, int on);
 #define APZ_ARITH_BF16X3 1
 #define APZ_ARITH_F16X2 2
 int apz_set_trunk_arith(apz_engine *e, int arith);
+/* Batch-size independence of the APZ_ARITH_F16X2 trunk (15x15 / 128-filter residual net).  By default a batch of more than
+ * 32 boards runs the two-term fp16 kernel (csrc/trunk15_wino3h16.h) and a batch of <= 32 boards the exact-fp32 small-batch
+ * kernel (csrc/trunk15_wino3s.h): a position's low-order bits depend on how many boards share its forward.  on != 0
+ * (default off; takes effect from the next forward): batches of <= 32 boards run csrc/trunk15_wino3hs.h instead -- the
+ * small-batch form of the f16x2 kernel, held to BIT equality with the batched kernel for every board (tests/
+ * test_gpu_trunk_f16x2_small.py), with the same weights, overflow word and static exponents (a layer with exponent 0 runs
+ * the unscaled form, as in the batched dispatch).  A board's result then depends on its planes, the weights and the
+ * exponents only, whatever the batch.  A forward that raises the overflow word is repeated on the exact-fp32 kernel for the
+ * WHOLE batch (for batches of more than 32 boards that is so with or without this call): the independence holds for forwards
+ * that do not overflow.  The exact repeat, calibration, apz_prewarm, apz_conv3x3_bench and apz_layer_io follow the same
+ * route as a forward of that n; APZ_TRUNK_WINOGRAD_BATCHED (test hook) still forces the batched form.  HIP graphs
+ * (apz_set_forward_graphs) capture the new kernel like any other: every launch of a capture carries its own epoch.
+ * An engine on which this call is never made launches exactly the kernels it launched before the call existed.
+ * Returns APZ_OK and does nothing for APZ_ARITH_F32 and for 8x8 boards (already uniform: one kernel family for every batch
+ * size); APZ_E_UNSUPPORTED, with the reason in apz_last_error, for APZ_ARITH_BF16X3 and for an engine created under
+ * APZ_F16X2_K8=1 (no small-batch form of those kernels). */
+int apz_set_trunk_uniform(apz_engine *e, int on);
 long apz_trunk_overflows(apz_engine *e);
 /* Static per-layer activation exponents of the APZ_ARITH_F16X2 trunk kernel (15x15 / 128-filter residual net, batches of
  * more than 32 boards; csrc/trunk15_wino3h16.h, WINO3H16_PLAIN_SCALED).  Unscaled, the two-term split holds activations

@@ -3,18 +3,21 @@
 policy_value_net_mxnet.py:261-280) and one `MCTSPlayer.get_action` with n_playout = 400 (mcts_alphaZero.py:187-218),
 10-block net, 15x15 -- with the breakdown: GPU time per kernel class at one board (HIP events), the entry points
 (planes through apz_forward_host, codes through the zero-copy slot), the host-side pieces.
-Round 2: 1.0 ms per leaf, 0.43 s per move.  usage: latency_probe.py [out.json]"""
+Round 2: 1.0 ms per leaf, 0.43 s per move.  usage: latency_probe.py [--uniform] [out.json]
+--uniform: PolicyValueNet(uniform_trunk=True) -- one board runs the small-batch f16x2 trunk kernel (trunk15_wino3hs.h)."""
 import json, sys, time, numpy as np
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from alphapig_amd import weights
 from alphapig_amd.policy_value_net import PolicyValueNet
 from alphapig_amd.game import Board
 from alphapig_amd.mcts_alphaZero import MCTSPlayer
+uniform = "--uniform" in sys.argv
+if uniform: sys.argv.remove("--uniform")
 prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
-net = PolicyValueNet(15, 15, batch_size=16, n_blocks=10, n_filter=128, model_params=prm)
+net = PolicyValueNet(15, 15, batch_size=16, n_blocks=10, n_filter=128, model_params=prm, uniform_trunk=uniform)
 b = Board(width=15, height=15, n_in_row=5); b.init_board(0)
 for m in (112, 113, 97): b.do_move(m)
-res = {}
+res = {"uniform_trunk": uniform}
 def timeit(fn, reps=300, warm=20):
     for _ in range(warm): fn()
     t = time.perf_counter()
