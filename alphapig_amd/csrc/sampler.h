@@ -9,9 +9,18 @@
 // from a stateless counter hash (splitmix64 of (seed, row key, lane, draw)).  The row key is supplied by the
 // caller -- the self-play engine passes (global game index, ply), so a game's draws depend on nothing but the
 // seed, the game and the ply: not on the batch row, the rank or the step it happened to be sampled in (two ranks
-// with the same seed never share noise) -- or defaults to (step, row).  Validated statistically in
-// tests/test_gpu_sampler.py (pi to 1e-6 of the float64 host softmax; chi-square on move
-// frequencies; Dirichlet first and second moments).
+// with the same seed never share noise) -- or defaults to (step, row).
+//
+// pi is formed from the row's integer maximum: exp(1/temp * log(v / v_max)), the ratio taken as log1p((v - v_max) / v_max)
+// where it is above one half (v - v_max is exact in integers: no large intermediate is rounded; 1/temp * logf(v) is 5000 to
+// 14000 at temp 1e-3, where one ulp moved exp() by 1e-3 relative and two children one visit apart came out 4e-5 wrong),
+// and as log(v / v_max) below (where log1p's argument would cancel).  Visit counts below 2^24 convert exactly.  A child
+// without visits beside a visited one gets exp(1/temp * (log 1e-10 - log v_max)) as in the reference (< 1e-10); a row of
+// unvisited children only is uniform; a row without any child returns pi = 0 and move -1.
+// Tested in tests/test_gpu_sampler.py: pi within tests/test_head_loss_bounds.py's bar (<= 1e-6) of the float64 host
+// softmax, near ties at temp 1e-3 included; chi-square on the move frequencies with 6 and with 225 children; the mean of
+// the Dirichlet noise through the draw frequencies (its second moment is not observable through one draw per game);
+// determinism in (seed, key).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,22 +79,37 @@ __global__ __launch_bounds__(64) void root_sample_kernel(const int* __restrict__
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     const int* vrow = visits + (size_t)g * HW;
-    float x[4], p[4];
+    int v[4], vmax = -1;
+    float p[4];
     bool has[4];
-    float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int i = lane * 4 + k;
-        const int v = (i < HW) ? vrow[i] : -1;
-        has[k] = v >= 0;
-        x[k] = has[k] ? inv_temp * logf((float)v + 1e-10f) : -INFINITY;
-        m = fmaxf(m, x[k]);
+        v[k] = (i < HW) ? vrow[i] : -1;
+        has[k] = v[k] >= 0;
+        vmax = max(vmax, v[k]);
     }
-    m = wave_max(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) vmax = max(vmax, __shfl_xor(vmax, o));
+    if (vmax < 0) {                               // no child (wave-uniform): pi = 0, move -1
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (lane * 4 + k < HW) pi[(size_t)g * HW + lane * 4 + k] = 0.f;
+        if (lane == 0) moves[g] = -1;
+        return;
+    }
+    const float fmax_ = (float)vmax;
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        p[k] = has[k] ? expf(x[k] - m) : 0.f;
+        float xm = 0.f;                           // 1/temp * (log(v + 1e-10) - log(v_max + 1e-10)) <= 0
+        if (v[k] > 0 && v[k] < vmax) {
+            const float d = (float)(v[k] - vmax) / fmax_;
+            xm = inv_temp * (d >= -0.5f ? log1pf(d) : logf((float)v[k] / fmax_));
+        } else if (v[k] == 0 && vmax > 0) {
+            xm = inv_temp * (logf(1e-10f) - logf(fmax_));
+        }
+        p[k] = has[k] ? expf(xm) : 0.f;
         s += p[k];
     }
     s = wave_sum(s);

@@ -112,7 +112,12 @@ int apz_augment8(apz_engine *e, const void *planes_dev, const void *pi_dev, int 
 /* Root move sampling on the GPU (opt-in; NOT bit-compatible with the reference's NumPy stream):
  * visits_host [g][H*W] int32 with -1 where the root has no child; pi_host [g][H*W] gets
  * softmax(log(visits+1e-10)/temp) (mcts_alphaZero.py:152-155), moves_host[g] a draw from
- * (1-eps)*pi + eps*Dirichlet(alpha) (:198-201).  Deterministic in (seed, step, game index). */
+ * (1-eps)*pi + eps*Dirichlet(alpha) (:198-201).  Deterministic in (seed, step, game index).
+ * Accuracy of pi: within 1e-6 absolute of that softmax evaluated in float64, at every temperature and however close the
+ * leading children are (the kernel works from v / v_max with v - v_max taken in integers), on condition that every
+ * visit count is below 2^24 (counts convert to float exactly).  A child without visits beside a visited one gets the
+ * reference's weight (below 1e-10 at temp <= 1); a row whose children all have 0 visits is uniform over them.
+ * A row without any child (all -1): pi all zero, move -1, nothing non-finite; the other rows are unaffected. */
 int apz_sample_moves_host(apz_engine *e, const int32_t *visits_host, int g, float temp, float alpha,
                           float eps, uint64_t seed, uint64_t step, float *pi_host, int32_t *moves_host);
 /* The same with one caller-chosen 64-bit key per row instead of (step, row): the draw of row i depends on

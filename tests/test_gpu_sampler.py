@@ -1,7 +1,9 @@
-"""GPU root sampler (opt-in perf mode): exact pi, statistically correct draws, determinism."""
+"""GPU root sampler (opt-in perf mode): pi against the float64 host softmax (near ties, degenerate and empty rows
+included), statistically correct draws, determinism."""
 import numpy as np
 import pytest
 
+import test_head_loss_bounds as hb
 from alphapig_amd import weights
 
 pytestmark = pytest.mark.gpu
@@ -146,3 +148,91 @@ def test_keyed_draws_follow_the_game_not_the_row(net):
     # another seed: another stream
     _, c = net.sample_moves(v, temp=1.0, seed=100, step=1, keys=keys)
     assert (c != mv0).any()
+
+
+# ---- near ties, degenerate rows, every lane occupied (bars and rows: tests/test_head_loss_bounds.py) ------------------
+@pytest.fixture(scope="module")
+def net8():
+    from alphapig_amd.policy_value_net import PolicyValueNet
+    prm = weights.init_params("simple", 8, 8, 9, seed=1, style="bench")
+    n = PolicyValueNet(8, 8, batch_size=16, model_params=prm, net_kind="simple")
+    yield n
+    n.close()
+
+
+@pytest.mark.parametrize("temp", hb.SAMPLER_TEMPS)
+@pytest.mark.parametrize("side", [15, 8])
+def test_near_tie_and_degenerate_rows_match_host_softmax(net, net8, side, temp):
+    """Two leading children one visit apart at the cold temperature (an ordinary row with 1600 playouts; make_visits
+    never draws one), counts up to 1e6, unvisited children, a single child: pi inside the module's bar (<= 1e-6) of the
+    float64 host softmax.  On the 8x8 engine HW = 64: the lanes 16 .. 63 hold no cell."""
+    engine = net if side == 15 else net8
+    names, v = hb.near_tie_rows(side * side)
+    bar = hb.sampler_pi_bar(v, temp)
+    assert bar.max() <= 1e-6
+    for eps in (0.0, 0.25):
+        pi, mv = engine.sample_moves(v, temp=temp, eps=eps, seed=4, step=1)
+        assert np.isfinite(pi).all()
+        for i, name in enumerate(names):
+            want, acts = host_pi(v[i], temp)
+            q = hb.ratio(pi[i], want, bar[i])
+            if eps == 0.0:
+                print("side %d temp %g %-32s |pi - host| %.2e = %.3f of its bar" % (side, temp, name, np.abs(pi[i] - want).max(), q))
+            assert q <= 1.0, (name, q)
+            assert mv[i] in acts, name
+            assert not pi[i][v[i] < 0].any(), name
+            if len(acts) == 1:
+                assert pi[i, acts[0]] == 1.0 and mv[i] == acts[0], name
+            if v[i].max() == 0:                                      # unvisited children only: uniform, the same bits
+                assert len(set(pi[i, acts].tolist())) == 1, name
+    if temp == 1e-3:                # cold and without noise: one of the most visited children
+        _, mv = engine.sample_moves(v, temp=temp, eps=0.0, seed=9, step=0)
+        for i in range(len(v)):
+            if pi[i].max() == 1.0:
+                assert v[i, mv[i]] == v[i].max(), names[i]
+
+
+@pytest.mark.parametrize("side", [15, 8])
+def test_a_row_without_a_child_returns_zero_pi_and_no_move(net, net8, side):
+    """include/alphapig_hip.h: visits all -1 -> pi all zero, move -1, nothing non-finite, the other rows untouched."""
+    engine = net if side == 15 else net8
+    hw = side * side
+    empty = np.full((1, hw), -1, dtype=np.int32)
+    pi, mv = engine.sample_moves(empty, temp=1.0, seed=2, step=3)
+    assert not pi.any() and mv[0] == -1
+    rows = make_visits(np.random.RandomState(8), 6, hw)
+    keys = np.arange(1, 10, dtype=np.uint64) << np.uint64(20)
+    mixed = np.vstack([empty, rows[:3], empty, rows[3:], empty])
+    where = np.array([1, 2, 3, 5, 6, 7])
+    for temp in hb.SAMPLER_TEMPS:
+        pi, mv = engine.sample_moves(mixed, temp=temp, seed=2, step=3, keys=keys)
+        assert np.isfinite(pi).all()
+        assert not pi[[0, 4, 8]].any() and (mv[[0, 4, 8]] == -1).all()
+        pi_alone, mv_alone = engine.sample_moves(rows, temp=temp, seed=2, step=77, keys=keys[where])
+        np.testing.assert_array_equal(pi[where], pi_alone)
+        np.testing.assert_array_equal(mv[where], mv_alone)
+
+
+@pytest.mark.parametrize("every", [1, 2])
+def test_move_frequencies_follow_pi_with_every_lane_occupied(net, every):
+    """All 225 children (every lane of the wavefront holds cells, the scan crosses all of them), and every second cell
+    absent; temp 1, no noise, 4096 rows x 8 steps.  The draw is a pure function of (seed, step, row): deterministic.
+    Thresholds: the 1 - 1e-5 quantile of chi-square with 224 / 112 degrees of freedom (325.96 / 187.60; the
+    existing 5-dof threshold of 30 is the same level)."""
+    row = np.full(225, -1, dtype=np.int32)
+    acts = np.arange(0, 225, every)
+    row[acts] = 1 + (acts * 37) % 23
+    want, _ = host_pi(row, 1.0)
+    G = 4096
+    v = np.tile(row, (G, 1))
+    counts = np.zeros(225)
+    for step in range(8):
+        pi, mv = net.sample_moves(v, temp=1.0, eps=0.0, seed=13, step=step)
+        counts += np.bincount(mv, minlength=225)
+    assert hb.ratio(pi[0], want, hb.sampler_pi_bar(row[None], 1.0)[0]) <= 1.0
+    n = counts.sum()
+    assert n == 8 * G and counts[row < 0].sum() == 0
+    assert (n * want[acts]).min() > 5                       # expected counts large enough for the chi-square law
+    chi2 = ((counts[acts] - n * want[acts]) ** 2 / (n * want[acts])).sum()
+    print("every %d: chi-square %.1f over %d degrees of freedom" % (every, chi2, len(acts) - 1))
+    assert chi2 < {1: 326.0, 2: 187.6}[every]
