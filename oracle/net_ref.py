@@ -74,39 +74,50 @@ def _heads(x, prm):
     return logits, probs, vlogit, np.tanh(vlogit)
 
 
-def forward_resnet(prm, planes, n_blocks, dtype=np.float64, return_trunk=False):
-    """policy_value_net_mxnet.py:70-102."""
+def forward_resnet(prm, planes, n_blocks, dtype=np.float64, return_trunk=False, return_layers=False):
+    """policy_value_net_mxnet.py:70-102.  return_layers: the output of every 3x3 convolution layer (after BatchNorm, the
+    skip connection where there is one, and ReLU) as one more list at the end, in the engine's apz_layer_io order: the
+    stem, then per block the output of convA / bnA and the block's output (2 * n_blocks + 1 arrays)."""
     x = np.asarray(planes).astype(dtype)
     x = _conv_act(x, prm, "res_conv1")
     stem = x
+    layers = [x]
     for i in range(1, n_blocks + 1):
         skip = x
         y = _conv(x, prm["convA%d_weight" % i].astype(dtype), prm["convA%d_bias" % i].astype(dtype))
         y = np.maximum(_bn(y, prm, "bnA%d" % i, False, ("_moving_mean", "_moving_var")), 0)
+        layers.append(y)
         y = _conv(y, prm["convB%d_weight" % i].astype(dtype), prm["convB%d_bias" % i].astype(dtype))
         y = _bn(y, prm, "bnB%d" % i, False, ("_moving_mean", "_moving_var"))
         x = np.maximum(y + skip, 0)
+        layers.append(x)
     out = _heads(x, prm)
-    return out + ((stem, x),) if return_trunk else out
+    if return_trunk:
+        out = out + ((stem, x),)
+    return out + (layers,) if return_layers else out
 
 
-def forward_simple(prm, planes, dtype=np.float64, return_trunk=False):
-    """policy_value_net_mxnet_simple.py:68-92."""
+def forward_simple(prm, planes, dtype=np.float64, return_trunk=False, return_layers=False):
+    """policy_value_net_mxnet_simple.py:68-92.  return_layers: the six conv_act outputs as one more list at the end."""
     x = np.asarray(planes).astype(dtype)
     first = None
+    layers = []
     for name, _ in SIMPLE_LAYERS:
         x = _conv_act(x, prm, name)
+        layers.append(x)
         if first is None:
             first = x
     out = _heads(x, prm)
-    return out + ((first, x),) if return_trunk else out
+    if return_trunk:
+        out = out + ((first, x),)
+    return out + (layers,) if return_layers else out
 
 
-def forward(prm, planes, kind="resnet", n_blocks=10, dtype=np.float64, return_trunk=False):
-    """-> (logits [N,HW], probs [N,HW], value_logit [N,1], value [N,1]) [+ (stem, trunk)]."""
+def forward(prm, planes, kind="resnet", n_blocks=10, dtype=np.float64, return_trunk=False, return_layers=False):
+    """-> (logits [N,HW], probs [N,HW], value_logit [N,1], value [N,1]) [+ (stem, trunk)] [+ [layer outputs]]."""
     if kind == "resnet":
-        return forward_resnet(prm, planes, n_blocks, dtype, return_trunk)
-    return forward_simple(prm, planes, dtype, return_trunk)
+        return forward_resnet(prm, planes, n_blocks, dtype, return_trunk, return_layers)
+    return forward_simple(prm, planes, dtype, return_trunk, return_layers)
 
 
 def flops_per_leaf(kind, h, w, c_in=9, n_blocks=10, n_filter=128):

@@ -92,3 +92,31 @@ def test_oracle_matches_an_independent_operator_library(kind, h, blocks):
     got = (logits, torch.softmax(logits, dim=1), vlogit, torch.tanh(vlogit))
     for g, w in zip(got, want):
         np.testing.assert_allclose(g.numpy(), w, rtol=0, atol=1e-10)
+
+
+@pytest.mark.parametrize("kind,h,blocks", [("resnet", 15, 3), ("resnet", 8, 2), ("simple", 8, 0)])
+def test_per_layer_outputs_match_an_independent_operator_library(kind, h, blocks):
+    """return_layers=True: every convolution layer's output in the engine's apz_layer_io order (stem, then convA / block
+    output per block; the six conv_act layers of the plain net), second-sourced like the heads above: the same graph with
+    PyTorch's library operators in float64 (tests/trained_nets.py).  The flag changes none of the other results."""
+    import torch
+    from trained_nets import torch_forward_layers
+    prm = weights.init_params(kind, h, h, 9, blocks, 128, seed=6, style="bench")
+    rs = np.random.RandomState(8)
+    planes = (rs.rand(3, 9, h, h) > 0.65).astype(np.float64)
+    plain = net_ref.forward(prm, planes, kind, blocks, np.float64, return_trunk=True)
+    want = net_ref.forward(prm, planes, kind, blocks, np.float64, return_trunk=True, return_layers=True)
+    assert len(want) == len(plain) + 1
+    for a, b in zip(plain[:4], want[:4]):
+        np.testing.assert_array_equal(a, b)
+    layers = want[-1]
+    assert len(layers) == (2 * blocks + 1 if kind == "resnet" else 6)
+    np.testing.assert_array_equal(layers[0], want[4][0])
+    np.testing.assert_array_equal(layers[-1], want[4][1])
+    got = torch_forward_layers(prm, planes, kind, blocks, torch.float64)
+    assert len(got[4]) == len(layers)
+    for g, w in zip(got[4], layers):
+        assert g.shape == w.shape and np.abs(w).max() > 0.1
+        np.testing.assert_allclose(g, w, rtol=0, atol=1e-10)
+    np.testing.assert_allclose(got[0], want[0], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(got[2], want[2][:, 0], rtol=0, atol=1e-10)
