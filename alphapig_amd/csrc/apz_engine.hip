@@ -32,6 +32,7 @@
 #include "heads_train.h"
 #include "weights_pack.h"
 #include "act_max.h"
+#include "replay.h"
 
 namespace {
 
@@ -152,6 +153,8 @@ struct apz_engine {
     size_t wgw_floats = 0;                         // capacity of wgw_scratch
     void* adam_tab = nullptr;                      // apz_adam_step: device copy of the tensor table
     size_t adam_cap = 0;
+    int32_t* gather_entries = nullptr;             // apz_replay_gather: device copy of the entry words
+    size_t gather_cap = 0;
     float* wino_scratch[2] = {nullptr, nullptr};   // apz_wino_conv: rows16 input / output copies
     size_t wino_scratch_boards = 0;
     bool wgrad_attr_set[2] = {false, false};
@@ -1034,7 +1037,7 @@ void apz_destroy(apz_engine* e) {
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
                    e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
-                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->w3hs_slabs, e->w3hs_tickets, e->amax_dev};
+                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->w3hs_slabs, e->w3hs_tickets, e->amax_dev, e->gather_entries};
     for (void* p : dev)
         if (p) hipFree(p);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -2419,6 +2422,73 @@ int apz_layout_convert(apz_engine* e, const void* src_dev, void* dst_dev, int64_
         hipLaunchKernelGGL(apz::rows16_to_dense_kernel, dim3(grid), dim3(256), 0, e->stream, (const float*)src_dev, (float*)dst_dev,
                            (long)planes);
     HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// ---- device replay buffer (csrc/replay.h)
+int apz_replay_gather(apz_engine* e, const void* codes_dev, const void* pi_dev, const void* z_dev, int64_t capacity,
+                      const int32_t* entries_host, int n, int n_planes, void* planes_out_dev, void* pi_out_dev, void* z_out_dev,
+                      void* stream) {
+    if (!e) return fail(APZ_E_ARG, "null engine");
+    if (!e->perm_s) return fail(APZ_E_UNSUPPORTED, "the replay gather needs a square board");
+    if (n_planes != 9 && n_planes != 4) return fail(APZ_E_ARG, "n_planes must be 9 or 4");
+    if (n < 0 || capacity < 0 || capacity > (INT32_MAX >> 3)) return fail(APZ_E_ARG, "replay gather: bad sample count / capacity");
+    if (n == 0) return APZ_OK;
+    if (!codes_dev || !pi_dev || !z_dev || !entries_host || !planes_out_dev || !pi_out_dev || !z_out_dev)
+        return fail(APZ_E_ARG, "null argument");
+    // every entry before anything is copied or launched: the kernel indexes the ring with them unchecked
+    for (int j = 0; j < n; j++)
+        if (entries_host[j] < 0 || (int64_t)entries_host[j] >= 8 * capacity)
+            return fail(APZ_E_ARG, "replay gather: entry " + std::to_string(j) + " = " + std::to_string(entries_host[j]) +
+                                       " lies outside [0, 8 * capacity = " + std::to_string(8 * capacity) + ")");
+    EngineLock guard(e->submit_lock);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    StreamScope sc(e, stream);
+    if ((size_t)n > e->gather_cap) {
+        if (e->gather_entries) HIP_TRY(hipFree(e->gather_entries));
+        e->gather_entries = nullptr;
+        e->gather_cap = 0;
+        HIP_TRY(hipMalloc((void**)&e->gather_entries, (size_t)n * sizeof(int32_t)));
+        e->gather_cap = n;
+    }
+    // stream-ordered upload behind the previous gather's kernel (apz_adam_step's table travels the same way)
+    HIP_TRY(hipMemcpyAsync(e->gather_entries, entries_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    const long total = (long)n * e->hw;
+    hipLaunchKernelGGL(apz::replay_gather_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 16)), dim3(256), 0,
+                       e->stream, (const unsigned char*)codes_dev, (const float*)pi_dev, (const float*)z_dev,
+                       (const int*)e->gather_entries, e->perm_s, e->perm_p, (float*)planes_out_dev, (float*)pi_out_dev,
+                       (float*)z_out_dev, n, e->cfg.height, e->cfg.width, e->code_stride, n_planes);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// apz_forward_host for planes that already live in device memory (a mini-batch of the device replay buffer): the engine's
+// stream waits for what `after_stream` has queued so far (the kernel that wrote the planes), runs the same forward and
+// copies the results out.  Returns with the engine's stream drained: the planes may be released or rewritten.
+int apz_forward_dev_host(apz_engine* e, const void* planes_dev, int n, float* probs_host, float* values_host, void* after_stream) {
+    if (!e || !planes_dev || !probs_host || !values_host) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
+    if (n == 0) return APZ_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (after_stream != APZ_ENGINE_STREAM && (hipStream_t)after_stream != e->stream) {
+        hipEvent_t ev = get_event(e);
+        hipError_t he = hipEventRecord(ev, (hipStream_t)after_stream);
+        if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev, 0);
+        e->free_events.push_back(ev);
+        HIP_TRY(he);
+    }
+    const size_t hw = e->hw;
+    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() {
+        return forward_dev(e, (const float*)planes_dev, n, e->probs, e->values, nullptr, nullptr);
+    }, true);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(e->h_probs, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->h_values, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    resolve_pending(e);
+    std::memcpy(probs_host, e->h_probs, n * hw * sizeof(float));
+    std::memcpy(values_host, e->h_values, n * sizeof(float));
     return APZ_OK;
 }
 

@@ -441,6 +441,48 @@ def from_rows16(x):
     return y
 
 
+# ---- device replay buffer -------------------------------------------------------------------------------------------
+def replay_gather(codes, pi, z, entries, height, width, n_planes=9):
+    """The mini-batch of a device replay ring (apz_replay_gather, csrc/replay.h).  codes u8 [cap][code stride], pi f32
+    [cap][HW], z f32 [cap]: contiguous device tensors; entries: k entry words slot * 8 + symmetry (any integer sequence).
+    -> (states [k][n_planes][H][W], pis [k][HW], zs [k]) on the same device, queued on torch's current stream.  Entries
+    outside [0, 8 * cap) raise ValueError here, before the library is called."""
+    import numpy as np
+    torch = _torch()
+    h, w, n_planes = int(height), int(width), int(n_planes)
+    hw = h * w
+    stride = (hw + 1 + 15) // 16 * 16
+    if h != w:
+        raise ValueError("replay_gather rotates boards: it needs a square board")
+    if n_planes not in (9, 4):
+        raise ValueError("n_planes must be 9 or 4")
+    cap = int(codes.shape[0])
+    if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape) == (cap, stride)):
+        raise ValueError("codes: a contiguous uint8 device tensor [cap][%d]" % stride)
+    for t, shape, what in ((pi, (cap, hw), "pi"), (z, (cap,), "z")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and
+                t.device == codes.device):
+            raise ValueError("%s: a contiguous float32 tensor %s on the device of codes" % (what, list(shape)))
+    ent = np.asarray(entries).reshape(-1)
+    if ent.size and not np.issubdtype(ent.dtype, np.integer):
+        raise ValueError("entries must be integers")
+    if ent.size and (int(ent.min()) < 0 or int(ent.max()) >= 8 * cap):
+        raise ValueError("replay_gather: entries must lie in [0, 8 * capacity = %d), got %d ... %d" %
+                         (8 * cap, int(ent.min()), int(ent.max())))
+    ent = np.ascontiguousarray(ent, dtype=np.int32)
+    k = int(ent.size)
+    states = torch.empty((k, n_planes, h, w), dtype=torch.float32, device=codes.device)
+    pis, zs = _empty((k, hw), states), _empty((k,), states)
+    if k == 0:
+        return states, pis, zs
+    L = _native.hip()
+    hnd = _engine(h, w, codes.device.index or 0)
+    stream = C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)
+    _ck(L, L.apz_replay_gather(hnd, codes.data_ptr(), pi.data_ptr(), z.data_ptr(), cap, _native.as_ptr(ent, C.c_int32), k,
+                               n_planes, states.data_ptr(), pis.data_ptr(), zs.data_ptr(), stream))
+    return states, pis, zs
+
+
 # ---- Adam -----------------------------------------------------------------------------------------------------------
 def adam_step(entries, lr_t, b1, b2, eps, rescale, device, skip=None):
     """One launch over all tensors.  entries: [(w, grad, m, v, wd)] of float32 device tensors (apz_adam_step).  skip: a

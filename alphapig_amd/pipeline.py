@@ -8,6 +8,12 @@ kl_targ, check_freq, pure_mcts_playout_num, game_batch_num, play_batch_size, sgf
     sgf_batches        how many leading batches replay SGF records instead of searching (the
                        reference hard-codes 4000, train_mxnet.py:270; default 0 = none)
     n_blocks, n_filter network size (the reference hard-codes 10 / 128, train_mxnet.py:79-91)
+    replay             what the replay buffer stores (alphapig_amd/replay.py).  "tuples" (default): the reference's deque of 8x
+                       augmented float32 tuples, filled by get_equi_data on the host.  "compact": the position codes, pi and z
+                       as the exchange delivers them (1 144 B instead of 72 000 B per ply on 15x15), decoded and rotated on the
+                       host for the rows a mini-batch draws.  "device": the same ring in the trainer's device memory, the
+                       mini-batch gathered there by a kernel and handed to the trainer and the KL monitor without crossing
+                       PCIe.  Same draws, same mini-batch bits in all three; square boards only for the last two.
 
 One `game batch` of the reference = ONE self-play game followed by a policy update; here a batch
 collects `play_batch_size` games from the engine, which keeps `concurrent_games` running so that
@@ -145,6 +151,18 @@ class TrainPipeline(object):
         # small-batch f16x2 kernel, so that a game's bits do not depend on how many games share a forward
         # (PolicyValueNet's uniform_trunk).  The trainer's internal evaluator is not concerned.
         self.uniform_trunk = bool(conf.get("uniform_trunk", False))
+        # replay: what the replay buffer stores (module docstring)
+        self.replay = conf.get("replay", "tuples")
+        if self.replay not in ("tuples", "compact", "device"):
+            raise ValueError("replay must be 'tuples', 'compact' or 'device', not %r" % (self.replay,))
+        if self.replay == "device":
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("replay='device' keeps the replay buffer in GPU memory and there is no GPU "
+                                   "(replay='compact' keeps the same codes on the host)")
+            if trainer is not None and not hasattr(trainer, "upload"):
+                raise RuntimeError("replay='device' hands the trainer mini-batches in GPU memory; the trainer passed in has "
+                                   "no upload(), so it does not take device batches (replay='compact' stays on the host)")
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -191,6 +209,14 @@ class TrainPipeline(object):
             if eval_net is not None and eval_net is not self.policy_value_net:
                 eval_net.set_act_scale_auto(True)
         self.keep_replica_buffers = bool(conf.get("replica_buffers", False))    # every rank keeps the replay buffer (host RAM x world)
+        if self.replay != "tuples":
+            from . import replay
+            c_in = int(getattr(self.policy_value_net, "channelnum", 9))
+            if self.replay == "device" and (self.rank == 0 or self.keep_replica_buffers):
+                self.data_buffer = replay.DeviceReplayBuffer(conf["buffer_size"], self.board_height, self.board_width, c_in,
+                                                             device=device)
+            else:       # (also the ranks that never fill theirs: untouched zero pages)
+                self.data_buffer = replay.CompactReplayBuffer(conf["buffer_size"], self.board_height, self.board_width, c_in)
         self._taken = 0
         self._rng = random.Random(seed)
         self.episode_len = 0
@@ -219,6 +245,10 @@ class TrainPipeline(object):
         self._taken += n_games
         self.episode_len = int(np.mean([len(e.moves) for e in eps]))
         if not self.distributed:
+            if self.replay != "tuples":         # the episodes' own codes, as they are
+                self.data_buffer.extend_codes(np.concatenate([e.codes for e in eps]), np.concatenate([e.pis for e in eps]),
+                                              np.concatenate([e.zs for e in eps]))
+                return
             states, pis, zs = episodes_to_tuples(eps, self.engine.pool)
         else:
             codes = np.concatenate([e.codes for e in eps])
@@ -227,6 +257,9 @@ class TrainPipeline(object):
             codes, pis, zs = dist.all_gather_tuples(codes, pis, zs, consumer=None if self.keep_replica_buffers else 0)   # THE exchange of the round (RCCL all-gather)
             self.last_gathered = dist.last_gather_total
             if self.rank != 0 and not self.keep_replica_buffers:
+                return
+            if self.replay != "tuples":         # the gathered block, as it is
+                self.data_buffer.extend_codes(codes, pis, zs)
                 return
             states = self.engine.pool.codes_to_planes(codes, 9)
         self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
@@ -240,6 +273,11 @@ class TrainPipeline(object):
             return
         data = list(data)
         self.episode_len = len(data)
+        if self.replay != "tuples":             # game records yield planes: stored as the codes that reproduce them
+            if data:
+                self.data_buffer.extend_planes(np.stack([np.asarray(d[0], dtype=np.float32) for d in data]),
+                                               np.stack([np.asarray(d[1]).reshape(-1) for d in data]), [d[2] for d in data])
+            return
         self.data_buffer.extend(get_equi_data(data, self.board_height, self.board_width))
 
     # ---- update / evaluation ---------------------------------------------------------------
@@ -480,8 +518,11 @@ class TrainPipeline(object):
                             stop = True
                             continue
                         codes, pis, zs, n_games = it
-                        states = self.engine.pool.codes_to_planes(codes, 9)
-                        self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
+                        if self.replay != "tuples":
+                            self.data_buffer.extend_codes(codes, pis, zs)
+                        else:
+                            states = self.engine.pool.codes_to_planes(codes, 9)
+                            self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
                         games_recv += n_games
                     due = n_sgf + games_recv // self.play_batch_size - batches_done
                     if due <= 0:
@@ -657,6 +698,8 @@ class _KeepTrainer(object):
 
     def __init__(self, net):
         self.net = net
+        if hasattr(net, "policy_value_dev"):        # planes in device memory (replay "device"): only where the net has it
+            self.policy_value_dev = net.policy_value_dev
 
     def policy_value(self, states):
         return self.net.policy_value(states)

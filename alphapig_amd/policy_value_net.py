@@ -325,6 +325,26 @@ class PolicyValueNet(object):
         probs, vals = self.forward_planes(states.reshape(-1, self.channelnum, self.board_height, self.board_width))
         return probs, vals.reshape(-1, 1)
 
+    def policy_value_dev(self, planes):
+        """policy_value on planes that already live on this evaluator's device -- a contiguous float32 torch tensor
+        [n][C][H][W], e.g. the states of a DeviceReplayBuffer's mini-batch: nothing is uploaded, the forward waits for what
+        torch's current stream has queued (apz_forward_dev_host), and the results carry policy_value's bits."""
+        import torch
+        shape = (self.channelnum, self.board_height, self.board_width)
+        if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous() and
+                planes.dim() == 4 and tuple(planes.shape[1:]) == shape and (planes.device.index or 0) == self._device):
+            raise ValueError("planes must be a contiguous float32 tensor [n, %d, %d, %d] on device %d" % (shape + (self._device,)))
+        n = int(planes.shape[0])
+        probs = np.empty((n, self.hw), dtype=np.float32)
+        vals = np.empty(n, dtype=np.float32)
+        stream = C.c_void_p(torch.cuda.current_stream(planes.device).cuda_stream)
+        row = self.channelnum * self.hw * 4
+        for s in range(0, n, self.batchsize):
+            k = min(self.batchsize, n - s)
+            self._ck(self.L.apz_forward_dev_host(self._h, planes.data_ptr() + s * row, k, as_ptr(probs[s:s + k], C.c_float),
+                                                 as_ptr(vals[s:s + k], C.c_float), stream))
+        return probs, vals.reshape(-1, 1)
+
     def policy_value2(self, state_batch):
         return self.policy_value(state_batch)
 

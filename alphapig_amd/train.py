@@ -386,6 +386,13 @@ class HipTrainer(object):
     def policy_value(self, state_batch):
         """Inference-mode (moving statistics) probabilities and values for the KL monitor: the self-play path's own
         evaluator (PolicyValueNet) on the current weights."""
+        return self._evaluator().policy_value(state_batch)
+
+    def policy_value_dev(self, planes):
+        """policy_value on a device tensor of planes (PolicyValueNet.policy_value_dev): same bits, no upload"""
+        return self._evaluator().policy_value_dev(planes)
+
+    def _evaluator(self):
         from .policy_value_net import PolicyValueNet
         if self._eval is None:
             nf = int(next(iter(self.p.values())).shape[0]) if self.kind == "resnet" else 128
@@ -396,7 +403,7 @@ class HipTrainer(object):
         elif self._eval_t != self.t:
             self.sync_evaluator(self._eval)
             self._eval_t = self.t
-        return self._eval.policy_value(state_batch)
+        return self._eval
 
     def get_params(self):
         return collections.OrderedDict((k, v.cpu().numpy()) for k, v in self.p.items())
@@ -423,7 +430,10 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
     mini_batch: list of (state, mcts_prob, winner_z).  `evaluator.policy_value(states)` (the HIP
     PolicyValueNet) supplies old/new predictions when given, else the trainer's own inference
     graph.  -> (loss, entropy, kl, lr_multiplier); `monitors` (a dict, optional) receives the reference's value-head
-    monitors explained_var_old / explained_var_new (train_mxnet.py:222-227) and the learning rate used."""
+    monitors explained_var_old / explained_var_new (train_mxnet.py:222-227) and the learning rate used.
+    mini_batch may also be the DeviceBatch a code replay buffer draws (alphapig_amd/replay.py): see _policy_update_batch."""
+    if isinstance(mini_batch, DeviceBatch):
+        return _policy_update_batch(trainer, mini_batch, learn_rate, lr_multiplier, epochs, kl_targ, evaluator, monitors)
     states = np.stack([np.ascontiguousarray(d[0]) for d in mini_batch]).astype(np.float32)
     pis = np.stack([d[1] for d in mini_batch]).astype(np.float32)
     zs = np.array([d[2] for d in mini_batch], dtype=np.float32)
@@ -433,6 +443,51 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
     loss = entropy = kl = 0.0
     batch = trainer.upload(states, pis, zs) if hasattr(trainer, "upload") else states     # once for all epochs
     lr_used = lr_multiplier                               # (the reference logs learn_rate * the multiplier the epochs ran with)
+    for _ in range(epochs):
+        loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
+        if evaluator is not None:
+            if hasattr(trainer, "sync_evaluator") and hasattr(evaluator, "load_device_params"):
+                trainer.sync_evaluator(evaluator)
+            else:
+                evaluator.set_params(trainer.get_params())
+        new_probs, new_v = pv(states)
+        kl = float(np.mean(np.sum(old_probs * (np.log(old_probs + 1e-10) - np.log(new_probs + 1e-10)), axis=1)))
+        if kl > kl_targ * 4:
+            break
+    if kl > kl_targ * 2 and lr_multiplier > 0.05:        # train_mxnet.py:215-218
+        lr_multiplier /= 1.5
+    elif kl < kl_targ / 2 and lr_multiplier < 20:
+        lr_multiplier *= 1.5
+    if monitors is not None:
+        monitors["explained_var_old"] = explained_variance(zs, old_v)
+        monitors["explained_var_new"] = explained_variance(zs, new_v)
+        monitors["learn_rate"] = float(learn_rate * lr_used)
+    return loss, entropy, kl, lr_multiplier
+
+
+def _policy_update_batch(trainer, mini_batch, learn_rate, lr_multiplier, epochs, kl_targ, evaluator, monitors):
+    """policy_update on a mini-batch that is already stacked.  NumPy arrays (CompactReplayBuffer): uploaded once, like the
+    list's.  Device tensors (DeviceReplayBuffer): no stacking and no upload; the KL monitor's forwards read the planes where
+    they are (`policy_value_dev`; an evaluator without it gets them on the host, once) and zs come to the host once for the
+    explained-variance monitors.  The KL stays the NumPy expression on the probabilities copied back: it decides the early
+    stop and the learning-rate multiplier, so its bits must not depend on the buffer kind."""
+    states, pis, zs = mini_batch
+    pv = (evaluator.policy_value if evaluator is not None else trainer.policy_value)
+    if isinstance(states, np.ndarray):
+        states, pis, zs = (np.ascontiguousarray(a, dtype=np.float32) for a in (states, pis, zs))
+        batch = trainer.upload(states, pis, zs) if hasattr(trainer, "upload") else states     # once for all epochs
+    else:
+        batch = mini_batch
+        pv_dev = getattr(evaluator if evaluator is not None else trainer, "policy_value_dev", None)
+        if pv_dev is not None:
+            pv = pv_dev
+        else:
+            states = states.cpu().numpy()
+        pis, zs = None, zs.cpu().numpy()           # (train_step ignores them beside a DeviceBatch)
+    old_probs, old_v = pv(states)
+    new_v = old_v
+    loss = entropy = kl = 0.0
+    lr_used = lr_multiplier
     for _ in range(epochs):
         loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
         if evaluator is not None:

@@ -288,6 +288,22 @@ int apz_colsum(apz_engine *e, const void *in_dev, void *out_dev, int rows, int c
  * apz_load_weights; the engine must have been loaded once from the host. */
 int apz_load_weights_dev(apz_engine *e, const char *const *names, const void *const *dev_ptrs, const int64_t *sizes,
                          int n, void *stream);
+/* Device replay buffer (alphapig_amd/replay.py, csrc/replay.h): the ring keeps what the self-play exchange delivers --
+ * codes_dev [capacity][code stride] u8, pi_dev [capacity][H*W] f32, z_dev [capacity] f32, one slot per tuple -- and a
+ * mini-batch is gathered on the device.  entries_host [n] i32: slot * 8 + symmetry (the order of apz_augment8).
+ * Sample j gets planes_out_dev [j][n_planes][H][W] = the planes apz_encode_planes writes for its slot, permuted like row
+ * `symmetry` of apz_augment8; pi_out_dev [j][H*W] = that row's pi; z_out_dev [j] = z[slot] -- the same bits.  Queued on
+ * `stream` (the entry words are copied in stream order; entries_host need not outlive the call).  APZ_E_UNSUPPORTED on a
+ * non-square board; APZ_E_ARG for n_planes other than 9 / 4 or any entry outside [0, 8 * capacity), before anything is
+ * copied or launched; n == 0 is APZ_OK. */
+int apz_replay_gather(apz_engine *e, const void *codes_dev, const void *pi_dev, const void *z_dev, int64_t capacity,
+                      const int32_t *entries_host, int n, int n_planes, void *planes_out_dev, void *pi_out_dev,
+                      void *z_out_dev, void *stream);
+/* apz_forward_host on planes that already live in device memory: the engine's stream is ordered behind everything queued
+ * on `after_stream` so far (APZ_ENGINE_STREAM: nothing to wait for), runs the same forward and copies probs / values to
+ * the host.  Same bits as apz_forward_host on the same planes; returns with the engine's stream drained. */
+int apz_forward_dev_host(apz_engine *e, const void *planes_dev, int n, float *probs_host, float *values_host,
+                         void *after_stream);
 int apz_conv1x1_fwd(apz_engine *e, const void *x_dev, const void *w_dev, const void *bias_dev, void *y_dev, int n,
                     int C, int CO, int layout, void *stream);
 int apz_conv1x1_bwd(apz_engine *e, const void *x_dev, const void *w_dev, const void *dy_dev, void *dx_dev,

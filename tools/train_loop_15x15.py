@@ -8,11 +8,42 @@ Prints one JSON line per reporting window (profiles/r04_train_loop_15x15.log); -
 import argparse
 import json
 import os
+import resource
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from alphapig_amd.pipeline import TrainPipeline  # noqa: E402
+
+
+def _time_trainer_thread(tp):
+    """Wall clock the trainer thread spends filling the replay buffer (codes_to_planes + get_equi_data + extend, or
+    extend_codes), drawing a mini-batch (sample) and inside train_step -> a dict that fills while the loop runs.  What is
+    left of the update intervals beside sample and train_step is the KL monitor and the weight snapshot."""
+    import threading
+    from alphapig_amd import pipeline, train
+    acc = {"fill_s": 0.0, "sample_s": 0.0, "train_step_s": 0.0}
+
+    def timed(fn, key):
+        def inner(*a, **kw):
+            if threading.current_thread().name != "apz-trainer":
+                return fn(*a, **kw)
+            t = time.perf_counter()
+            try:
+                return fn(*a, **kw)
+            finally:
+                acc[key] += time.perf_counter() - t
+        return inner
+    buf = tp.data_buffer
+    buf.sample = timed(buf.sample, "sample_s")
+    if tp.replay == "tuples":
+        buf.extend = timed(buf.extend, "fill_s")
+        pipeline.get_equi_data = timed(pipeline.get_equi_data, "fill_s")
+        tp.engine.pool.codes_to_planes = timed(tp.engine.pool.codes_to_planes, "fill_s")
+    else:
+        buf.extend_codes = timed(buf.extend_codes, "fill_s")
+    train.HipTrainer.train_step = timed(train.HipTrainer.train_step, "train_step_s")
+    return acc
 
 
 def main():
@@ -27,6 +58,8 @@ def main():
     ap.add_argument("--train-arith", default="f32", choices=("f32", "f16x2"), help="the trainer's trunk arithmetic (HipTrainer trunk_arith)")
     ap.add_argument("--act-scale", default="off", choices=("off", "auto"),
                     help="the self-play evaluator's static activation exponents (TrainPipeline act_scale)")
+    ap.add_argument("--replay", default="tuples", choices=("tuples", "compact", "device"),
+                    help="what the replay buffer stores (TrainPipeline replay): augmented tuples, codes on the host, codes on the GPU")
     args = ap.parse_args()
     conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
                 n_playout=400, c_puct=5, buffer_size=2198800, batch_size=128, epochs=8, kl_targ=0.02,
@@ -34,8 +67,9 @@ def main():
                 play_batch_size=1, concurrent_games=1024, n_blocks=10, n_filter=128, eval_games=args.eval_games,
                 model_dir="/tmp/apz_models_15", async_update=not args.lock_step, round_seconds=0.25,
                 max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith,
-                act_scale=args.act_scale)
+                act_scale=args.act_scale, replay=args.replay)
     tp = TrainPipeline(conf, seed=1)
+    host = _time_trainer_thread(tp)
     t0 = time.time()
     if args.lock_step:
         hist = tp.run()
@@ -83,7 +117,9 @@ def main():
                       "games": tp._taken, "updates_done": tp.updates_done, "updates_skipped": tp.updates_skipped,
                       "leaf_evals_per_s_whole_run": round(tp.engine.stats["leaf_evals"] / dt),
                       "update_share_of_wall_whole_run": round(sum(b - a for a, b in tp.update_intervals) / dt, 3),
-                      "exclusive_updates": tp.exclusive_updates,
+                      "exclusive_updates": tp.exclusive_updates, "replay": tp.replay,
+                      "trainer_thread_s": {k: round(v, 3) for k, v in host.items()},
+                      "peak_rss_mb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0, 1),
                       "self_play_held_s": round(tp.engine.timers.get("gate_s", 0.0), 2), "train_arith": tp.train_arith,
                       "policy_update_ms_whole_run": round(1e3 * sum(b - a for a, b in tp.update_intervals) /
                                                           max(1, len(tp.update_intervals)), 1),
