@@ -87,6 +87,44 @@ struct Pending {
     int launches;   // kernel launches bracketed by the pair
 };
 
+struct LdsAttr {
+    const void* kernel;   // host function pointer
+    int bytes;            // largest hipFuncAttributeMaxDynamicSharedMemorySize configured so far
+};
+
+// The exchange of the small-batch trunk kernels (T = apz::Wino3S, apz::Wino3HS): the workgroups that share a board meet
+// through global slabs + ticket words keyed by a per-launch epoch (csrc/trunk15_wino3s.h)
+template <class T>
+struct TicketExchange {
+    float* slabs = nullptr;        // row partials of the position halves
+    unsigned* tickets = nullptr;   // the pairs' ticket words (each launch exchanges its epoch in)
+    unsigned epoch = 0;            // last epoch handed out; never 0, never repeated between two memsets of the words
+
+    // In front of every launch on `stream`: allocates at the first one and hands out the launch's epoch
+    int prepare(hipStream_t stream, unsigned* launch_epoch) {
+        if (!slabs) HIP_TRY(hipMalloc((void**)&slabs, T::slab_floats() * sizeof(float)));
+        if (!tickets) {
+            HIP_TRY(hipMalloc((void**)&tickets, T::counters() * sizeof(unsigned)));
+            epoch = 0;
+        }
+        if (++epoch == 0 || epoch == 1) {
+            // first launch, or the 32-bit epoch wrapped: zero the words ON THE LAUNCH STREAM (ordered before the kernel)
+            epoch = 1;
+            HIP_TRY(hipMemsetAsync(tickets, 0, T::counters() * sizeof(unsigned), stream));
+        }
+        *launch_epoch = epoch;
+        return APZ_OK;
+    }
+    // apz_submit_codes captures no launch sequence this close to the wrap: the ticket reset has to stay outside a capture
+    bool near_wrap() const { return epoch >= 0xFFFF0000u; }
+    void release() {
+        if (slabs) (void)hipFree(slabs);
+        if (tickets) (void)hipFree(tickets);
+        slabs = nullptr;
+        tickets = nullptr;
+    }
+};
+
 }  // namespace
 
 struct apz_engine {
@@ -136,15 +174,14 @@ struct apz_engine {
     bool small8 = false;    // 8x8 boards: conv8_kernel / head8_kernel (conv8_small.h)
     float* wfc_raw = nullptr;   // head8_kernel: the policy FullyConnected weight as stored, [hw][4 hw]
     int act_ps = 0, act_rs = 0;
-    bool lds_attr_set[49] = {false};   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done, per kernel variant
-    int conv_lds_set[16] = {0};
+    std::vector<LdsAttr> lds_attrs;   // need_lds: one entry per kernel launched with dynamic LDS so far
     // persistent sampler staging (apz_sample_moves_host)
     int32_t* smp_vis = nullptr;
     float* smp_pi = nullptr;
     int32_t* smp_mv = nullptr;
     uint64_t* smp_keys = nullptr;
     size_t smp_cap = 0;
-    float* zeros256 = nullptr;          // bias stand-in for bias-free convolutions
+    float* zeros256 = nullptr;          // bias stand-in for bias-free convolutions (ensure_zeros256)
     double* bn_part = nullptr;                     // apz_bn_fwd / _bwd: per-(channel, batch split) partial sums [256 * BN_SPLITS][2]
     float* wgw_scratch = nullptr;                  // apz_wgrad_wino: partial dU per batch slice
     double* fold_ws = nullptr;                     // apz_load_weights_dev: scale / shift of one layer (2 x 256 doubles)
@@ -157,17 +194,12 @@ struct apz_engine {
     size_t gather_cap = 0;
     float* wino_scratch[2] = {nullptr, nullptr};   // apz_wino_conv: rows16 input / output copies
     size_t wino_scratch_boards = 0;
-    bool wgrad_attr_set[2] = {false, false};
     hipStream_t scratch_stream = nullptr;          // the stream of the last entry point that may have used the scratch buffers
     bool scratch_stream_valid = false;
-    float* w3s_slabs = nullptr;              // trunk15_wino3s_kernel: row partials of the position halves
-    unsigned* w3s_tickets = nullptr;         // ... and the pairs' ticket words (each launch exchanges its epoch in: trunk15_wino3s.h)
-    unsigned w3s_epoch = 0;                  // last epoch handed out; never 0, never repeated between two memsets of the words
+    TicketExchange<apz::Wino3S> w3s;         // trunk15_wino3s_kernel
     // apz_set_trunk_uniform: APZ_ARITH_F16X2 batches of <= 32 boards run trunk15_wino3hs_kernel (the batched kernel's bits)
     bool uniform_trunk = false;
-    float* w3hs_slabs = nullptr;             // ... its row partials and ticket words (trunk15_wino3hs.h), allocated at the first launch
-    unsigned* w3hs_tickets = nullptr;
-    unsigned w3hs_epoch = 0;                 // as w3s_epoch
+    TicketExchange<apz::Wino3HS> w3hs;       // ... and its exchange (trunk15_wino3hs.h)
     bool no_small_trunk = false;             // apz_test_select_trunk(APZ_TRUNK_WINOGRAD_BATCHED): tests compare the two forms
     bool no_quarter_trunk = false;           // apz_test_select_trunk(APZ_TRUNK_WINOGRAD_NO_QUARTER): 64-channel items for every batch
     int trunk_arith = APZ_ARITH_F32;         // apz_set_trunk_arith: APZ_ARITH_BF16X3 / _F16X2 = the split kernels for batches > 32
@@ -346,6 +378,31 @@ void resolve_pending(apz_engine* e) {
     e->pending.clear();
 }
 
+// In front of every launch with dynamic LDS: hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel, and again
+// only for a larger size.  Keyed by the kernel's host function pointer; a few dozen entries at most, searched linearly (the
+// one-board forward is ~45 launches of a few microseconds each), and nothing is allocated once a kernel has its entry.
+int need_lds(apz_engine* e, const void* kernel, int bytes) {
+    for (LdsAttr& a : e->lds_attrs)
+        if (a.kernel == kernel) {
+            if (bytes > a.bytes) {
+                HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+                a.bytes = bytes;
+            }
+            return APZ_OK;
+        }
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    e->lds_attrs.push_back({kernel, bytes});
+    return APZ_OK;
+}
+
+int ensure_zeros256(apz_engine* e) {
+    if (!e->zeros256) {
+        HIP_TRY(hipMalloc((void**)&e->zeros256, 256 * sizeof(float)));
+        HIP_TRY(hipMemset(e->zeros256, 0, 256 * sizeof(float)));
+    }
+    return APZ_OK;
+}
+
 template <int H, int W, int CT, bool RESID>
 int launch_conv_r(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n,
                   int out_ps, int out_rs, int relu = 1, int cout_groups = 1) {
@@ -355,14 +412,10 @@ int launch_conv_r(apz_engine* e, const ConvLayer& L, const float* in, const floa
     while (cchunk > G::max_chunk()) cchunk = ((cchunk / 2) + 3) & ~3;
     const int lds = G::lds_bytes(cchunk);
     auto kern = apz::conv3x3_mfma_kernel<H, W, CT, RESID>;
-    int& configured_lds = e->conv_lds_set[(H == 15 ? 0 : 8) + (CT == 1 ? 0 : CT == 2 ? 2 : 4) + (RESID ? 1 : 0)];
-    if (lds > configured_lds) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        configured_lds = lds;
-    }
     // persistent grid: as many workgroups as fit at once, each loops over boards
     int per_cu = std::max(1, std::min(4, (160 * 1024) / std::max(lds, 1)));
     int grid = std::min(n, e->num_cu * per_cu);
+    if (int rc = need_lds(e, (const void*)kern, lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid, cout_groups), dim3(256), lds, e->stream, in, L.wpk, L.bias, resid, out, n, L.cin,
                        L.cin_pad, cchunk, relu, out_ps, out_rs, L.cout);
     HIP_TRY(hipGetLastError());
@@ -389,21 +442,16 @@ int launch_conv_t(apz_engine* e, const ConvLayer& L, const float* in, const floa
 template <int NW>
 int launch_trunk_ring_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Trunk15;
-    bool& configured = e->lds_attr_set[NW == 8 ? 1 : 0];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_ring_kernel<true, NW>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_ring_kernel<false, NW>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
     const int grid = std::min(n, e->num_cu);   // one persistent workgroup per CU (LDS-bound)
-    if (resid)
+    if (resid) {
+        if (int rc = need_lds(e, (const void*)apz::trunk15_ring_kernel<true, NW>, T::LDS_BYTES)) return rc;
         hipLaunchKernelGGL((apz::trunk15_ring_kernel<true, NW>), dim3(grid), dim3(64 * NW), T::LDS_BYTES, e->stream, in,
                            L.wpk, L.bias, resid, out, n);
-    else
+    } else {
+        if (int rc = need_lds(e, (const void*)apz::trunk15_ring_kernel<false, NW>, T::LDS_BYTES)) return rc;
         hipLaunchKernelGGL((apz::trunk15_ring_kernel<false, NW>), dim3(grid), dim3(64 * NW), T::LDS_BYTES, e->stream, in,
                            L.wpk, L.bias, resid, out, n);
+    }
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }
@@ -414,93 +462,72 @@ int launch_trunk_ring_t(apz_engine* e, const ConvLayer& L, const float* in, cons
 constexpr int WINO3_MAX_BOARDS = 16384;   // even (board pairs), 16384 * 128 planes * 960 B = 2^31 - 2^27
 static_assert((long long)WINO3_MAX_BOARDS * 128 * 960 < (1ll << 31), "wino3 buffer offsets");
 
+// `launch(nb, off)` queues one launch of nb boards whose rows16 activations start `off` floats into the tensors
+template <class F>
+int for_board_chunks(int n, F launch) {
+    using T = apz::Trunk15;
+    for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS)
+        if (int rc = launch(std::min(n - b0, WINO3_MAX_BOARDS), (size_t)b0 * T::C * T::GPLANE)) return rc;
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
 template <bool RESID, bool RELU>
-int launch_wino3_t(apz_engine* e, int attr_slot, const float* in, const float* upk, const float* bias, const float* resid,
-                   float* out, int n, const float* upk_small = nullptr) {
+int launch_wino3_t(apz_engine* e, const float* in, const float* upk, const float* bias, const float* resid, float* out, int n,
+                   const float* upk_small = nullptr) {
     using T = apz::Wino3;
-    bool& configured = e->lds_attr_set[attr_slot];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<RESID, RELU>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<RESID, RELU, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3s_kernel<RESID, RELU>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, apz::Wino3S::LDS_BYTES));
-        configured = true;
+    if (!upk_small || n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk) {
+        return for_board_chunks(n, [&](int nb, size_t off) -> int {
+            bool quarter = false;                                 // few pairs (training batch 128, arena): four workgroups per pair
+            const int grid = apz::wino3_grid(nb, e->num_cu, e->no_quarter_trunk ? nullptr : &quarter);   // persistent workgroups; item = board pair x channel half (quarter)
+            if (!quarter) {
+                if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<RESID, RELU>, T::LDS_BYTES)) return rc;
+                hipLaunchKernelGGL((apz::trunk15_wino3_kernel<RESID, RELU>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
+                                   upk, bias, RESID ? resid + off : nullptr, out + off, nb);
+            } else {
+                if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<RESID, RELU, true>, T::LDS_BYTES)) return rc;
+                hipLaunchKernelGGL((apz::trunk15_wino3_kernel<RESID, RELU, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
+                                   in + off, upk, bias, RESID ? resid + off : nullptr, out + off, nb);
+            }
+            return APZ_OK;
+        });
     }
-    if (upk_small && n <= apz::Wino3S::MAX_BOARDS && !e->no_small_trunk) {
-        // the latency path: sixteen workgroups per board (16 output channels x half the positions), the same bits
-        // (csrc/trunk15_wino3s.h); the halves meet through global slabs + ticket words keyed by a per-launch epoch
-        if (!e->w3s_slabs) {
-            HIP_TRY(hipMalloc((void**)&e->w3s_slabs, apz::Wino3S::slab_floats() * sizeof(float)));
-            HIP_TRY(hipMalloc((void**)&e->w3s_tickets, apz::Wino3S::counters() * sizeof(unsigned)));
-            e->w3s_epoch = 0;
-        }
-        if (++e->w3s_epoch == 0 || e->w3s_epoch == 1) {
-            // first launch, or the 32-bit epoch wrapped: zero the words ON THE LAUNCH STREAM (ordered before the kernel)
-            e->w3s_epoch = 1;
-            HIP_TRY(hipMemsetAsync(e->w3s_tickets, 0, apz::Wino3S::counters() * sizeof(unsigned), e->stream));
-        }
-        hipLaunchKernelGGL((apz::trunk15_wino3s_kernel<RESID, RELU>), dim3(n * 16), dim3(256), apz::Wino3S::LDS_BYTES, e->stream, in,
-                           upk_small, bias, RESID ? resid : nullptr, out, n, e->w3s_slabs, e->w3s_tickets, e->w3s_epoch);
-        HIP_TRY(hipGetLastError());
-        return APZ_OK;
-    }
-    for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS) {
-        const int nb = std::min(n - b0, WINO3_MAX_BOARDS);
-        const size_t off = (size_t)b0 * T::C * T::GPLANE;
-        bool quarter = false;                                 // few pairs (training batch 128, arena): four workgroups per pair
-        const int grid = apz::wino3_grid(nb, e->num_cu, e->no_quarter_trunk ? nullptr : &quarter);   // persistent workgroups; item = board pair x channel half (quarter)
-        if (quarter)
-            hipLaunchKernelGGL((apz::trunk15_wino3_kernel<RESID, RELU, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
-                               in + off, upk, bias, RESID ? resid + off : nullptr, out + off, nb);
-        else
-            hipLaunchKernelGGL((apz::trunk15_wino3_kernel<RESID, RELU>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
-                               upk, bias, RESID ? resid + off : nullptr, out + off, nb);
-    }
+    // the latency path: sixteen workgroups per board (16 output channels x half the positions), the same bits
+    // (csrc/trunk15_wino3s.h); the halves meet through e->w3s
+    unsigned epoch;
+    if (int rc = e->w3s.prepare(e->stream, &epoch)) return rc;
+    if (int rc = need_lds(e, (const void*)apz::trunk15_wino3s_kernel<RESID, RELU>, apz::Wino3S::LDS_BYTES)) return rc;
+    hipLaunchKernelGGL((apz::trunk15_wino3s_kernel<RESID, RELU>), dim3(n * 16), dim3(256), apz::Wino3S::LDS_BYTES, e->stream, in,
+                       upk_small, bias, RESID ? resid : nullptr, out, n, e->w3s.slabs, e->w3s.tickets, epoch);
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }
 
 // The 3 x bf16 split kernel (opt-in): same layouts, same grids, 512 threads
 template <bool RESID>
-int launch_wino3b_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_wino3b_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Wino3B;
-    bool& configured = e->lds_attr_set[attr_slot];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3b_kernel<RESID, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    T::LDS_BYTES));
-        configured = true;
-    }
-    for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS) {
-        const int nb = std::min(n - b0, WINO3_MAX_BOARDS);
-        const size_t off = (size_t)b0 * T::C * T::GPLANE;
+    return for_board_chunks(n, [&](int nb, size_t off) -> int {
         const int grid = apz::wino3_grid(nb, e->num_cu);
+        if (int rc = need_lds(e, (const void*)apz::trunk15_wino3b_kernel<RESID, true>, T::LDS_BYTES)) return rc;
         hipLaunchKernelGGL((apz::trunk15_wino3b_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
                            (const void*)L.upk3b, L.bias, RESID ? resid + off : nullptr, out + off, nb);
-    }
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+        return APZ_OK;
+    });
 }
 
 // The 2 x fp16 split kernels (K16: trunk15_wino3h16_kernel, else trunk15_wino3h_kernel): same layouts, same grids, 512 threads
 // (SCALED, K16 only: the form with the layer's static input exponent, launched for L.act_exp != 0 and never otherwise --
 // an engine without exponents runs the same code objects as before they existed)
 template <bool RESID, bool K16, bool SCALED = false>
-int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_wino3h_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     static_assert(K16 || !SCALED, "only the 16-channel kernel has a scaled form");
     using T = typename std::conditional<K16, apz::Wino3H16, apz::Wino3H>::type;
     constexpr int FORM = SCALED ? apz::WINO3H16_PLAIN_SCALED : apz::WINO3H16_PLAIN;
     const void* kern = K16 ? (const void*)apz::trunk15_wino3h16_kernel<RESID, true, FORM> : (const void*)apz::trunk15_wino3h_kernel<RESID, true>;
-    bool& configured = e->lds_attr_set[attr_slot];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
-    for (int b0 = 0; b0 < n; b0 += WINO3_MAX_BOARDS) {
-        const int nb = std::min(n - b0, WINO3_MAX_BOARDS);
-        const size_t off = (size_t)b0 * T::C * T::GPLANE;
+    return for_board_chunks(n, [&](int nb, size_t off) -> int {
         const int grid = apz::wino3_grid(nb, e->num_cu);
+        if (int rc = need_lds(e, kern, T::LDS_BYTES)) return rc;
         if constexpr (K16)
             hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<RESID, true, FORM>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
                                in + off, (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur,
@@ -508,68 +535,59 @@ int launch_wino3h_t(apz_engine* e, int attr_slot, const ConvLayer& L, const floa
         else
             hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
                                (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
-    }
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+        return APZ_OK;
+    });
 }
 
 // The small-batch form of the 16-channel split kernel (apz_set_trunk_uniform): 1 .. 32 boards, eight workgroups per board,
 // the batched kernel's weights, bias, overflow word and exponent -- and its bits (csrc/trunk15_wino3hs.h)
 template <bool RESID, bool SCALED>
-int launch_wino3hs_t(apz_engine* e, int attr_slot, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_wino3hs_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Wino3HS;
-    bool& configured = e->lds_attr_set[attr_slot];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3hs_kernel<RESID, SCALED>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
-    if (!e->w3hs_slabs) {
-        HIP_TRY(hipMalloc((void**)&e->w3hs_slabs, T::slab_floats() * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->w3hs_tickets, T::counters() * sizeof(unsigned)));
-        e->w3hs_epoch = 0;
-    }
-    if (++e->w3hs_epoch == 0 || e->w3hs_epoch == 1) {
-        // first launch, or the 32-bit epoch wrapped: zero the words ON THE LAUNCH STREAM (ordered before the kernel)
-        e->w3hs_epoch = 1;
-        HIP_TRY(hipMemsetAsync(e->w3hs_tickets, 0, T::counters() * sizeof(unsigned), e->stream));
-    }
+    unsigned epoch;
+    if (int rc = e->w3hs.prepare(e->stream, &epoch)) return rc;
+    if (int rc = need_lds(e, (const void*)apz::trunk15_wino3hs_kernel<RESID, SCALED>, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((apz::trunk15_wino3hs_kernel<RESID, SCALED>), dim3(T::grid(n)), dim3(512), T::LDS_BYTES, e->stream, in,
                        (const void*)L.upk3h, L.bias3h, RESID ? resid : nullptr, out, n, e->ovf_cur, SCALED ? L.act_exp : 0,
-                       e->w3hs_slabs, e->w3hs_tickets, e->w3hs_epoch);
+                       e->w3hs.slabs, e->w3hs.tickets, epoch);
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }
 
+// The routes of a 15x15 trunk layer, first match wins; each launcher's template arguments name its kernel
 int launch_trunk_wino3(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    // uniform: f16x2, <= 32 boards on the small-batch form of the 16-channel kernel
     if (e->uniform_trunk && e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur && !e->f16x2_k8 &&
         n <= apz::Wino3S::MAX_BOARDS && !e->no_small_trunk) {
         if (L.act_exp != 0) {
-            if (resid) return launch_wino3hs_t<true, true>(e, 45, L, in, resid, out, n);
-            return launch_wino3hs_t<false, true>(e, 46, L, in, resid, out, n);
+            if (resid) return launch_wino3hs_t<true, true>(e, L, in, resid, out, n);
+            return launch_wino3hs_t<false, true>(e, L, in, resid, out, n);
         }
-        if (resid) return launch_wino3hs_t<true, false>(e, 47, L, in, resid, out, n);
-        return launch_wino3hs_t<false, false>(e, 48, L, in, resid, out, n);
+        if (resid) return launch_wino3hs_t<true, false>(e, L, in, resid, out, n);
+        return launch_wino3hs_t<false, false>(e, L, in, resid, out, n);
     }
+    // batched f16x2: the 8-channel kernel (APZ_F16X2_K8), the scaled 16-channel kernel, the 16-channel kernel
     if (e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur &&
         (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
         if (e->f16x2_k8) {
-            if (resid) return launch_wino3h_t<true, false>(e, 32, L, in, resid, out, n);
-            return launch_wino3h_t<false, false>(e, 33, L, in, resid, out, n);
+            if (resid) return launch_wino3h_t<true, false>(e, L, in, resid, out, n);
+            return launch_wino3h_t<false, false>(e, L, in, resid, out, n);
         }
         if (L.act_exp != 0) {
-            if (resid) return launch_wino3h_t<true, true, true>(e, 43, L, in, resid, out, n);
-            return launch_wino3h_t<false, true, true>(e, 44, L, in, resid, out, n);
+            if (resid) return launch_wino3h_t<true, true, true>(e, L, in, resid, out, n);
+            return launch_wino3h_t<false, true, true>(e, L, in, resid, out, n);
         }
-        if (resid) return launch_wino3h_t<true, true>(e, 36, L, in, resid, out, n);
-        return launch_wino3h_t<false, true>(e, 37, L, in, resid, out, n);
+        if (resid) return launch_wino3h_t<true, true>(e, L, in, resid, out, n);
+        return launch_wino3h_t<false, true>(e, L, in, resid, out, n);
     }
+    // batched bf16x3
     if (e->trunk_arith == APZ_ARITH_BF16X3 && L.upk3b && (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
-        if (resid) return launch_wino3b_t<true>(e, 26, L, in, resid, out, n);
-        return launch_wino3b_t<false>(e, 27, L, in, resid, out, n);
+        if (resid) return launch_wino3b_t<true>(e, L, in, resid, out, n);
+        return launch_wino3b_t<false>(e, L, in, resid, out, n);
     }
-    if (resid) return launch_wino3_t<true, true>(e, 6, in, L.upk2, L.bias, resid, out, n, L.upk3s);
-    return launch_wino3_t<false, true>(e, 7, in, L.upk2, L.bias, nullptr, out, n, L.upk3s);
+    // exact fp32: small, quarter or batched by the number of boards (launch_wino3_t)
+    if (resid) return launch_wino3_t<true, true>(e, in, L.upk2, L.bias, resid, out, n, L.upk3s);
+    return launch_wino3_t<false, true>(e, in, L.upk2, L.bias, nullptr, out, n, L.upk3s);
 }
 
 int launch_trunk_ring(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
@@ -580,14 +598,9 @@ int launch_trunk_ring(apz_engine* e, const ConvLayer& L, const float* in, const 
 template <int C4, int CIN, bool CODES>
 int launch_stem15_t(apz_engine* e, const ConvLayer& L, const float* in, float* out, int n) {
     constexpr int lds = apz::stem15_lds_bytes<C4>();
-    bool& configured = e->lds_attr_set[(C4 == 1 ? 2 : 3) + (CODES ? 22 : 0)];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::stem15_kernel<C4, CIN, CODES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    lds));
-        configured = true;
-    }
     // two resident workgroups per CU; at C_in = 4 twice as many workgroups as fit, so that the dispatcher evens out the tail
     const int grid = std::min(n, e->num_cu * (C4 == 1 ? 4 : 2));
+    if (int rc = need_lds(e, (const void*)apz::stem15_kernel<C4, CIN, CODES>, lds)) return rc;
     hipLaunchKernelGGL((apz::stem15_kernel<C4, CIN, CODES>), dim3(grid), dim3(256), lds, e->stream, in, L.wpk, L.bias, out, n,
                        L.cin, (int)e->code_stride);
     HIP_TRY(hipGetLastError());
@@ -610,14 +623,9 @@ int launch_stem15(apz_engine* e, const ConvLayer& L, const float* in, float* out
 template <bool RESID, bool CODES>
 int launch_conv8_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Conv8;
-    bool& configured = e->lds_attr_set[28 + (RESID ? 1 : 0) + (CODES ? 2 : 0)];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::conv8_kernel<RESID, CODES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    T::LDS_BYTES));
-        configured = true;
-    }
     const long items = (long)n * (L.cout / 16);
     const int grid = (int)std::min<long>(items, 2L * e->num_cu);       // two workgroups per CU (LDS), persistent over items
+    if (int rc = need_lds(e, (const void*)apz::conv8_kernel<RESID, CODES>, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((apz::conv8_kernel<RESID, CODES>), dim3(grid), dim3(256), T::LDS_BYTES, e->stream, in, L.wpk12, L.bias,
                        resid, out, n, L.cin, L.cin_pad / 4, L.cout, 1, (int)e->code_stride);
     HIP_TRY(hipGetLastError());
@@ -628,13 +636,9 @@ int launch_conv8_t(apz_engine* e, const ConvLayer& L, const float* in, const flo
 template <bool RESID>
 int launch_conv8h_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Conv8H;
-    bool& configured = e->lds_attr_set[34 + (RESID ? 1 : 0)];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::conv8h_kernel<RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
     const long items = (long)n * (L.cout / 16);
     const int grid = (int)std::min<long>(items, 2L * e->num_cu);
+    if (int rc = need_lds(e, (const void*)apz::conv8h_kernel<RESID>, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((apz::conv8h_kernel<RESID>), dim3(grid), dim3(256), T::LDS_BYTES, e->stream, in, (const void*)L.wpk8h,
                        L.bias8h, resid, out, n, L.cin, L.cout, 1, e->ovf_cur);
     HIP_TRY(hipGetLastError());
@@ -783,11 +787,13 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
         const int grid = (n + 15) / 16;
         const int tpw = (ntile + 3) / 4;
         if (tpw <= 1) {
+            if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1>, lds)) return rc2;
             hipLaunchKernelGGL(apz::head_fc_kernel<1>, dim3(grid), dim3(256), lds, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw);
         } else if (tpw <= 4) {
             // the n-tiles over four workgroups per 16 boards, then one wavefront per board for softmax + value head
             const int lds1 = 16 * (4 * hw + 1) * (int)sizeof(float);
+            if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1, true>, lds1)) return rc2;
             hipLaunchKernelGGL((apz::head_fc_kernel<1, true>), dim3(grid, tpw), dim3(256), lds1, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw, e->fc_logits);
             hipLaunchKernelGGL(apz::head_softmax_value_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits, e->featv,
@@ -798,6 +804,27 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
         HIP_TRY(hipGetLastError());
     }
     e->last_n = n;
+    return APZ_OK;
+}
+
+// The forward of n boards from their position codes: the stem decodes them itself where it can, else they are expanded
+// into e->planes first
+int forward_from_codes(apz_engine* e, const unsigned char* codes_dev, int n, float* probs, float* values) {
+    if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, probs, values, nullptr, nullptr, codes_dev);
+    if (int rc = apz_encode_planes(e, codes_dev, n, e->cfg.c_in, e->planes)) return rc;
+    return forward_dev(e, e->planes, n, probs, values, nullptr, nullptr);
+}
+
+// The tail of the synchronous host entry points: e->probs / e->values of n boards through the pinned staging buffers to
+// the caller.  Returns with the stream drained.
+int collect_to_host(apz_engine* e, int n, float* probs_host, float* values_host) {
+    const size_t hw = e->hw;
+    HIP_TRY(hipMemcpyAsync(e->h_probs, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->h_values, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    resolve_pending(e);
+    std::memcpy(probs_host, e->h_probs, n * hw * sizeof(float));
+    std::memcpy(values_host, e->h_values, n * sizeof(float));
     return APZ_OK;
 }
 
@@ -1037,9 +1064,11 @@ void apz_destroy(apz_engine* e) {
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
                    e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
-                   e->wfc_raw, e->w3s_slabs, e->w3s_tickets, e->w3hs_slabs, e->w3hs_tickets, e->amax_dev, e->gather_entries};
+                   e->wfc_raw, e->amax_dev, e->gather_entries};
     for (void* p : dev)
         if (p) hipFree(p);
+    e->w3s.release();
+    e->w3hs.release();
     if (e->ovf_host) hipHostFree(e->ovf_host);
     if (e->amax_host) hipHostFree(e->amax_host);
     for (auto& sl : e->slots) {
@@ -1349,18 +1378,12 @@ int apz_forward_host(apz_engine* e, const float* planes_host, int n, float* prob
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
-    const size_t hw = e->hw, pin = (size_t)n * e->cfg.c_in * hw * sizeof(float);
+    const size_t pin = (size_t)n * e->cfg.c_in * e->hw * sizeof(float);
     std::memcpy(e->h_planes, planes_host, pin);
     HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, pin, hipMemcpyHostToDevice, e->stream));
     int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() { return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr); }, true);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->h_probs, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_values, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    resolve_pending(e);
-    std::memcpy(probs_host, e->h_probs, n * hw * sizeof(float));
-    std::memcpy(values_host, e->h_values, n * sizeof(float));
-    return APZ_OK;
+    return collect_to_host(e, n, probs_host, values_host);
 }
 
 int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, float* probs_pinned,
@@ -1374,11 +1397,7 @@ int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, f
     const size_t hw = e->hw;
     HIP_TRY(hipMemcpyAsync(e->codes, codes_pinned, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
     // (APZ_ARITH_F16X2: the forward is collected here, see forward_guarded -- the copies below are queued behind it)
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() -> int {
-        if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, e->probs, e->values, nullptr, nullptr, e->codes);
-        if (int r = apz_encode_planes(e, e->codes, n, e->cfg.c_in, e->planes)) return r;
-        return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
-    }, true);
+    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() { return forward_from_codes(e, e->codes, n, e->probs, e->values); }, true);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(probs_pinned, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(values_pinned, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1426,12 +1445,8 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
         HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     }
     std::memcpy(sl.h_codes, codes_host, (size_t)n * e->code_stride);
-    auto launch_all = [&]() -> int {
-        if (stem_takes_codes(e))    // the stem decodes the codes itself (read straight from the pinned slot)
-            return forward_dev(e, nullptr, n, sl.d_probs, sl.d_values, nullptr, nullptr, sl.d_codes);
-        if (int rc = apz_encode_planes(e, sl.d_codes, n, e->cfg.c_in, e->planes)) return rc;
-        return forward_dev(e, e->planes, n, sl.d_probs, sl.d_values, nullptr, nullptr);
-    };
+    // (the codes are read straight from the pinned slot)
+    auto launch_all = [&]() { return forward_from_codes(e, sl.d_codes, n, sl.d_probs, sl.d_values); };
     int rc = APZ_OK;
     if (e->trunk_arith == APZ_ARITH_F16X2 && e->ovf_host) {   // the slot's overflow word: read by apz_wait
         e->ovf_host[slot] = 0;
@@ -1447,8 +1462,11 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     if (it != e->fwd_graphs.end()) {
         HIP_TRY(hipGraphLaunch(it->second, e->stream));
         e->last_n = n;
-    } else if (graphable && ++e->fwd_seen[key] >= 3 && e->w3s_epoch < 0xFFFF0000u && e->w3hs_epoch < 0xFFFF0000u) {
-        // (third use: every lazy allocation / attribute / ticket reset of this shape has happened outside the capture)
+    } else if (graphable && ++e->fwd_seen[key] >= 3 && !e->w3s.near_wrap() && !e->w3hs.near_wrap()) {
+        // (third use: every lazy allocation / attribute / ticket reset of this shape has happened outside the capture --
+        // need_lds is per kernel, and the two plain submissions before this one launched the kernels the capture launches:
+        // whatever changes the route of a batch size (weights, arithmetic, exponents, uniform, the test selection) goes
+        // through drop_forward_graphs, which starts the count again)
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
@@ -1492,11 +1510,7 @@ int apz_wait(apz_engine* e, int slot, float* probs_host, float* values_host) {
         // an activation of this batch left the fp16 range (trunk15_wino3h.h): the same batch again on the exact-fp32 kernel
         EngineLock guard(e->submit_lock);
         e->ovf_host[slot] = 0;
-        int rc = repeat_exact(e, sl.n, [&]() -> int {
-            if (stem_takes_codes(e)) return forward_dev(e, nullptr, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr, sl.d_codes);
-            if (int r = apz_encode_planes(e, sl.d_codes, sl.n, e->cfg.c_in, e->planes)) return r;
-            return forward_dev(e, e->planes, sl.n, sl.d_probs, sl.d_values, nullptr, nullptr);
-        });
+        int rc = repeat_exact(e, sl.n, [&]() { return forward_from_codes(e, sl.d_codes, sl.n, sl.d_probs, sl.d_values); });
         if (rc) return rc;
     }
     std::memcpy(probs_host, sl.h_probs, (size_t)sl.n * e->hw * sizeof(float));
@@ -1748,10 +1762,7 @@ int apz_conv3x3_fwd(apz_engine* e, const void* x_dev, const void* wpk_dev, const
         return fail(APZ_E_UNSUPPORTED, "conv3x3_fwd: C_out must be 64, 128 or 256");
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
-    if (!e->zeros256) {
-        HIP_TRY(hipMalloc((void**)&e->zeros256, 256 * sizeof(float)));
-        HIP_TRY(hipMemset(e->zeros256, 0, 256 * sizeof(float)));
-    }
+    if (int rc = ensure_zeros256(e)) return rc;
     StreamScope sc(e, stream);
     ConvLayer L;
     L.cin = cin_p;
@@ -1811,10 +1822,7 @@ int apz_wino_conv_add(apz_engine* e, const void* x_dev, const void* upk_dev, con
     if (resid_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "wino_conv: residual input in the padded-row layout only");
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
-    if (!e->zeros256) {
-        HIP_TRY(hipMalloc((void**)&e->zeros256, 256 * sizeof(float)));
-        HIP_TRY(hipMemset(e->zeros256, 0, 256 * sizeof(float)));
-    }
+    if (int rc = ensure_zeros256(e)) return rc;
     StreamScope sc(e, stream);
     if (layout == APZ_LAYOUT_DENSE && (size_t)n > e->wino_scratch_boards) {   // grow the rows16 copies (previous users are ordered on their stream)
         HIP_TRY(hipDeviceSynchronize());
@@ -1837,10 +1845,10 @@ int apz_wino_conv_add(apz_engine* e, const void* x_dev, const void* upk_dev, con
     const float* rs = (const float*)resid_dev;
     // the self-play path's kernel (csrc/trunk15_wino3.h)
     int rc;
-    if (rs && relu) rc = launch_wino3_t<true, true>(e, 6, xin, (const float*)upk_dev, b, rs, yout, n);
-    else if (rs) rc = launch_wino3_t<true, false>(e, 17, xin, (const float*)upk_dev, b, rs, yout, n);
-    else if (relu) rc = launch_wino3_t<false, true>(e, 7, xin, (const float*)upk_dev, b, nullptr, yout, n);
-    else rc = launch_wino3_t<false, false>(e, 19, xin, (const float*)upk_dev, b, nullptr, yout, n);
+    if (rs && relu) rc = launch_wino3_t<true, true>(e, xin, (const float*)upk_dev, b, rs, yout, n);
+    else if (rs) rc = launch_wino3_t<true, false>(e, xin, (const float*)upk_dev, b, rs, yout, n);
+    else if (relu) rc = launch_wino3_t<false, true>(e, xin, (const float*)upk_dev, b, nullptr, yout, n);
+    else rc = launch_wino3_t<false, false>(e, xin, (const float*)upk_dev, b, nullptr, yout, n);
     if (rc) return rc;
     if (dense)
         hipLaunchKernelGGL(apz::rows16_to_dense_kernel, dim3(cgrid), dim3(256), 0, e->stream, e->wino_scratch[1],
@@ -1857,28 +1865,20 @@ int apz_wino_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev, c
     using T = apz::Wino3;
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
-    if (!e->zeros256) {
-        HIP_TRY(hipMalloc((void**)&e->zeros256, 256 * sizeof(float)));
-        HIP_TRY(hipMemset(e->zeros256, 0, 256 * sizeof(float)));
-    }
+    if (int rc = ensure_zeros256(e)) return rc;
     StreamScope sc(e, stream);
-    bool& configured = e->lds_attr_set[11];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<false, false, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::trunk15_wino3_kernel<false, false, true, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
     const float* b = bias_dev ? (const float*)bias_dev : e->zeros256;
     bool quarter = false;
     const int grid = apz::wino3_grid(n, e->num_cu, e->no_quarter_trunk ? nullptr : &quarter);
-    if (quarter)
-        hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false, false, true, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)upk_dev, b, (const float*)stats_dev, (float*)y_dev, n);
-    else
+    if (!quarter) {
+        if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<false, false, false, true>, T::LDS_BYTES)) return rc;
         hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false, false, false, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
                            (const float*)x_dev, (const float*)upk_dev, b, (const float*)stats_dev, (float*)y_dev, n);
+    } else {
+        if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<false, false, true, true>, T::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false, false, true, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
+                           (const float*)x_dev, (const float*)upk_dev, b, (const float*)stats_dev, (float*)y_dev, n);
+    }
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }
@@ -1906,7 +1906,7 @@ int apz_wino3h_pack_many(apz_engine* e, const void* w_dev, const void* b_dev, in
 extern "C++" {
 namespace {
 template <int FORM, bool RESID>
-int launch_wino3h16_train(apz_engine* e, int attr_slot, const void* x_dev, const void* upk_dev, const void* bias_dev,
+int launch_wino3h16_train(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev,
                           const void* resid_dev, void* y_dev, int n, void* flag_dev, void* aux, int aux_n, void* stream) {
     if (!e || !x_dev || !upk_dev || !bias_dev || !y_dev || !aux || n < 1) return fail(APZ_E_ARG, "bad argument");
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wino3h: 15x15 boards only");
@@ -1916,11 +1916,7 @@ int launch_wino3h16_train(apz_engine* e, int attr_slot, const void* x_dev, const
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     StreamScope sc(e, stream);
-    bool& configured = e->lds_attr_set[attr_slot];
-    if (!configured) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        configured = true;
-    }
+    if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL(kern, dim3(apz::wino3_grid(n, e->num_cu)), dim3(512), T::LDS_BYTES, e->stream, (const float*)x_dev, upk_dev,
                        (const float*)bias_dev, (const float*)resid_dev, (float*)y_dev, n, (unsigned*)flag_dev, aux, aux_n);
     HIP_TRY(hipGetLastError());
@@ -1931,7 +1927,7 @@ int launch_wino3h16_train(apz_engine* e, int attr_slot, const void* x_dev, const
 
 int apz_wino3h_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev, void* y_dev,
                           void* stats_dev, int n, void* flag_dev, void* stream) {
-    return launch_wino3h16_train<apz::WINO3H16_STATS, false>(e, 40, x_dev, upk_dev, bias_dev, nullptr, y_dev, n, flag_dev,
+    return launch_wino3h16_train<apz::WINO3H16_STATS, false>(e, x_dev, upk_dev, bias_dev, nullptr, y_dev, n, flag_dev,
                                                              stats_dev, 0, stream);
 }
 
@@ -1940,9 +1936,9 @@ int apz_wino3h_conv_dgrad(apz_engine* e, const void* dy_dev, const void* upk_dev
     if (dymax_count < 1) return fail(APZ_E_ARG, "bad argument");
     void* dm = const_cast<void*>(dymax_dev);
     if (add_dev)
-        return launch_wino3h16_train<apz::WINO3H16_DGRAD, true>(e, 41, dy_dev, upk_dev, bias_dev, add_dev, dx_dev, n, flag_dev, dm,
+        return launch_wino3h16_train<apz::WINO3H16_DGRAD, true>(e, dy_dev, upk_dev, bias_dev, add_dev, dx_dev, n, flag_dev, dm,
                                                                 dymax_count, stream);
-    return launch_wino3h16_train<apz::WINO3H16_DGRAD, false>(e, 42, dy_dev, upk_dev, bias_dev, nullptr, dx_dev, n, flag_dev, dm,
+    return launch_wino3h16_train<apz::WINO3H16_DGRAD, false>(e, dy_dev, upk_dev, bias_dev, nullptr, dx_dev, n, flag_dev, dm,
                                                              dymax_count, stream);
 }
 
@@ -1974,34 +1970,22 @@ int apz_conv3x3_wgrad(apz_engine* e, const void* x_dev, const void* dy_dev, void
     int slices = std::max(1, std::min(n, (e->num_cu * 2) / std::max(1, gx * gy)));
     if (H == 15 && W == 15) {
         using G = apz::WgradGeo<15, 15>;
-        if (!e->wgrad_attr_set[0]) {
-            HIP_TRY(hipFuncSetAttribute((const void*)apz::conv3x3_wgrad_kernel<15, 15>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-            e->wgrad_attr_set[0] = true;
-        }
         slices = std::max(1, std::min(n, e->num_cu / std::max(1, gx * gy)));   // 85 KB LDS: one workgroup per CU
         if (int rc = wgrad_scratch(e, (size_t)slices * cout * cin * 9)) return rc;
-        if (layout == APZ_LAYOUT_ROWS16) {
-            using G16 = apz::WgradGeo<15, 15, true>;
-            bool& set16 = e->lds_attr_set[8];       // per engine (= per device), like every other attribute flag
-            if (!set16) {
-                HIP_TRY(hipFuncSetAttribute((const void*)apz::conv3x3_wgrad_kernel<15, 15, true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, G16::LDS_BYTES));
-                set16 = true;
-            }
-            hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<15, 15, true>), dim3(gx, gy, slices), dim3(256), G16::LDS_BYTES,
-                               e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
-        } else
+        if (layout == APZ_LAYOUT_DENSE) {
+            if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<15, 15>, G::LDS_BYTES)) return rc;
             hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<15, 15>), dim3(gx, gy, slices), dim3(256), G::LDS_BYTES, e->stream,
                                (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
+        } else {
+            using G16 = apz::WgradGeo<15, 15, true>;
+            if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<15, 15, true>, G16::LDS_BYTES)) return rc;
+            hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<15, 15, true>), dim3(gx, gy, slices), dim3(256), G16::LDS_BYTES,
+                               e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
+        }
     } else if (H == 8 && W == 8) {
         using G = apz::WgradGeo<8, 8>;
         if (int rc = wgrad_scratch(e, (size_t)slices * cout * cin * 9)) return rc;
-        if (!e->wgrad_attr_set[1]) {
-            HIP_TRY(hipFuncSetAttribute((const void*)apz::conv3x3_wgrad_kernel<8, 8>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-            e->wgrad_attr_set[1] = true;
-        }
+        if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<8, 8>, G::LDS_BYTES)) return rc;
         hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<8, 8>), dim3(gx, gy, slices), dim3(256), G::LDS_BYTES, e->stream,
                            (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
     } else {
@@ -2143,38 +2127,45 @@ int apz_colsum(apz_engine* e, const void* in_dev, void* out_dev, int rows, int c
     return APZ_OK;
 }
 
+namespace {
+// The decomposition of both Winograd weight-gradient kernels, by channel blocks (csrc/wgrad_wino3.h: 16 blocks x slices =
+// one workgroup per CU); the workgroups of a slice sit on one XCD (see the kernel).  Grows the slices' scratch.
+int wgrad_wino_plan(apz_engine* e, int n, int blocks, int* spx, int* slices) {
+    *spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * blocks)));
+    *slices = 8 * *spx;
+    return wgrad_scratch(e, (size_t)*slices * apz::WgradWino::SCRATCH_FLOATS_PER_SLICE);
+}
+
+// ... and their second launch: the slices' partial dU summed and transformed back into dw
+int launch_wgrad_wino_finish(apz_engine* e, int slices, void* dw_dev) {
+    hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
+                       (const float*)e->wgw_scratch, slices, (float*)dw_dev);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+}  // namespace
+
 int apz_wgrad_wino(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, void* stream) {
     if (!e || !x_dev || !dy_dev || !dw_dev || n < 1) return fail(APZ_E_ARG, "bad argument");
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
     if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
-    using T = apz::WgradWino;
     using T3 = apz::WgradWino3;
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     StreamScope sc(e, stream);
-    // Decomposition by channel blocks (csrc/wgrad_wino3.h: 16 blocks x slices = one workgroup per CU); the workgroups of a
-    // slice sit on one XCD (see the kernel)
-    const int spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * T3::BLOCKS)));
-    const int slices = 8 * spx;
-    if (int rc = wgrad_scratch(e, (size_t)slices * T::SCRATCH_FLOATS_PER_SLICE)) return rc;
-    bool& attr = e->lds_attr_set[10];
-    if (!attr) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
-        attr = true;
-    }
+    int spx, slices;
+    if (int rc = wgrad_wino_plan(e, n, T3::BLOCKS, &spx, &slices)) return rc;
     // rows through raw buffer loads (hardware zero fill for rows off the board, scalar board offset) from 256 boards on:
     // 133.6 against 144.4 us at 512 boards, 38.7 against 37.8 us at 128 (same box, alternating rounds: tools/wgrad_kernel_bench.hip)
+    const void* kern = n < 256 ? (const void*)apz::wgrad_wino3_kernel<false> : (const void*)apz::wgrad_wino3_kernel<true>;
+    if (int rc = need_lds(e, kern, T3::LDS_BYTES)) return rc;
     if (n >= 256)
         hipLaunchKernelGGL(apz::wgrad_wino3_kernel<true>, dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES, e->stream,
                            (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx);
     else
         hipLaunchKernelGGL(apz::wgrad_wino3_kernel<false>, dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES, e->stream,
                            (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx);
-    hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
-                       (const float*)e->wgw_scratch, slices, (float*)dw_dev);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return launch_wgrad_wino_finish(e, slices, dw_dev);
 }
 
 int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, const void* dymax_dev,
@@ -2182,21 +2173,14 @@ int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, v
     if (!e || !x_dev || !dy_dev || !dw_dev || !dymax_dev || dymax_count < 1 || n < 1) return fail(APZ_E_ARG, "bad argument");
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
     if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
-    using T = apz::WgradWino;
     using T3 = apz::WgradWino3H;
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     StreamScope sc(e, stream);
-    // the decomposition of apz_wgrad_wino
-    const int spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * T3::BLOCKS)));
-    const int slices = 8 * spx;
-    if (int rc = wgrad_scratch(e, (size_t)slices * T::SCRATCH_FLOATS_PER_SLICE)) return rc;
-    bool& attr = e->lds_attr_set[44];
-    if (!attr) {
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute((const void*)apz::wgrad_wino3h_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, T3::LDS_BYTES));
-        attr = true;
-    }
+    int spx, slices;
+    if (int rc = wgrad_wino_plan(e, n, T3::BLOCKS, &spx, &slices)) return rc;
+    const void* kern = n < 256 ? (const void*)apz::wgrad_wino3h_kernel<false> : (const void*)apz::wgrad_wino3h_kernel<true>;
+    if (int rc = need_lds(e, kern, T3::LDS_BYTES)) return rc;
     if (n >= 256)                                     // buffer loads from 256 boards on, as apz_wgrad_wino
         hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<true>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
                            e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
@@ -2205,10 +2189,7 @@ int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, v
         hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<false>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
                            e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
                            dymax_count, (unsigned*)flag_dev);
-    hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
-                       (const float*)e->wgw_scratch, slices, (float*)dw_dev);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return launch_wgrad_wino_finish(e, slices, dw_dev);
 }
 
 int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
@@ -2277,8 +2258,9 @@ int apz_conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const v
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (e->cfg.height * e->cfg.width + 63) / 64), dim3(256),
-                       ((size_t)CO * C + 4 * 8 * 64) * sizeof(float), e->stream,
+    const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
+    if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
+    hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (e->cfg.height * e->cfg.width + 63) / 64), dim3(256), lds, e->stream,
                        (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, e->cfg.height,
                        e->cfg.width, ps, rs);
     HIP_TRY(hipGetLastError());
@@ -2306,7 +2288,8 @@ int apz_conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const
     StreamScope sc(e, stream);
     const int P = e->cfg.height * e->cfg.width, CO = CO1 + CO2;
     if (int rc = head_scratch(e, (size_t)n * CO * C)) return rc;
-    const size_t lds = ((size_t)CO * 32 + (size_t)CO * P) * sizeof(float);
+    const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
+    if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
     hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
                        (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
                        e->head_scratch, C, CO1, CO2, e->cfg.height, e->cfg.width, ps, rs, accumulate_dx);
@@ -2478,18 +2461,11 @@ int apz_forward_dev_host(apz_engine* e, const void* planes_dev, int n, float* pr
         e->free_events.push_back(ev);
         HIP_TRY(he);
     }
-    const size_t hw = e->hw;
     int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() {
         return forward_dev(e, (const float*)planes_dev, n, e->probs, e->values, nullptr, nullptr);
     }, true);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->h_probs, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->h_values, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    resolve_pending(e);
-    std::memcpy(probs_host, e->h_probs, n * hw * sizeof(float));
-    std::memcpy(values_host, e->h_values, n * sizeof(float));
-    return APZ_OK;
+    return collect_to_host(e, n, probs_host, values_host);
 }
 
 int apz_prewarm(apz_engine* e, int n, int iters) {
@@ -2500,16 +2476,8 @@ int apz_prewarm(apz_engine* e, int n, int iters) {
     HIP_TRY(hipSetDevice(e->cfg.device));
     // e->codes is zero-filled at creation and only ever overwritten with valid codes: any content is a legal input
     ArmOverflowWord arm(e);
-    for (int i = 0; i < iters; i++) {
-        int rc;
-        if (stem_takes_codes(e)) {
-            rc = forward_dev(e, nullptr, n, e->probs, e->values, nullptr, nullptr, e->codes);
-        } else {
-            rc = apz_encode_planes(e, e->codes, n, e->cfg.c_in, e->planes);
-            if (!rc) rc = forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
-        }
-        if (rc) return rc;
-    }
+    for (int i = 0; i < iters; i++)
+        if (int rc = forward_from_codes(e, e->codes, n, e->probs, e->values)) return rc;
     return APZ_OK;
 }
 
@@ -2713,9 +2681,7 @@ int apz_calibrate_trunk_codes(apz_engine* e, const uint8_t* codes_host, int n, f
     return calibrate_trunk(e, n, layer_max_out, count, [&]() -> int {
         std::memcpy(e->h_codes, codes_host, (size_t)n * e->code_stride);
         HIP_TRY(hipMemcpyAsync(e->codes, e->h_codes, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
-        if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, e->probs, e->values, nullptr, nullptr, e->codes);
-        if (int r = apz_encode_planes(e, e->codes, n, e->cfg.c_in, e->planes)) return r;
-        return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
+        return forward_from_codes(e, e->codes, n, e->probs, e->values);
     });
 }
 

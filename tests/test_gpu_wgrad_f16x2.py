@@ -135,3 +135,52 @@ def test_operator_validation():
     x = torch.zeros(2, 128, 15, 16, device="cuda")
     with pytest.raises(ValueError):
         hipconv.conv3x3_wgrad_f16x2(x, torch.zeros(2, 64, 15, 16, device="cuda"), dm, flag)
+
+
+def test_evaluator_engine_serves_the_weight_gradient_in_both_orders():
+    """One engine runs the scaled f16x2 trunk kernels (a 33-board forward with activation exponents: the batched route) and
+    apz_wgrad_wino_f16x2, in both orders: each kernel gets its own dynamic-LDS attribute whichever came first.  dw carries
+    the bits of hipconv's engine (the decomposition depends on n and the CU count only), the forward those of a net that
+    never ran a training operator.  The attribute is process-wide, so the case discriminates only where it is the first in
+    its process to touch these kernels."""
+    import ctypes as C
+    import numpy as np
+    from alphapig_amd import hipconv, weights
+    from alphapig_amd.policy_value_net import PolicyValueNet
+    prm = weights.init_params("resnet", 15, 15, 9, 1, 128, seed=3, style="bench")
+    planes = (np.random.RandomState(5).rand(33, 9, 15, 15) < 0.3).astype(np.float32)
+    x, base = _inputs(6, 7300)
+    xc, dyc = _rows16(x).cuda(), _rows16(base).cuda()
+    dymax = _dymax(dyc)
+
+    def make():
+        net = PolicyValueNet(15, 15, batch_size=64, n_blocks=1, n_filter=128, model_params=prm, trunk_arith="f16x2")
+        net.set_trunk_act_exponents([1, 1])
+        return net
+
+    def wgrad_on(net):
+        dw, flag = torch.empty(128, 128, 3, 3, device="cuda"), _flag()
+        rc = net.L.apz_wgrad_wino_f16x2(net._h, xc.data_ptr(), dyc.data_ptr(), dw.data_ptr(), 6, dymax.data_ptr(),
+                                        int(dymax.numel()), flag.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        assert rc == 0, net.L.apz_last_error().decode()
+        assert int(flag.item()) == 0
+        return dw
+
+    a, b, plain = make(), make(), make()
+    fwd_a = a.forward_planes(planes)
+    dw_a = wgrad_on(a)
+    dw_b = wgrad_on(b)
+    fwd_b = b.forward_planes(planes)
+    fwd = plain.forward_planes(planes)
+    flag = _flag()
+    dw = hipconv.conv3x3_wgrad_f16x2(xc, dyc, dymax, flag)
+    torch.cuda.synchronize()
+    assert int(flag.item()) == 0
+    for net, got_dw, got_fwd in ((a, dw_a, fwd_a), (b, dw_b, fwd_b)):
+        assert torch.equal(got_dw, dw)
+        assert np.array_equal(got_fwd[0], fwd[0]) and np.array_equal(got_fwd[1], fwd[1])
+        assert net.trunk_overflows() == 0
+    assert plain.trunk_overflows() == 0
+    for net in (a, b, plain):
+        net.close()
