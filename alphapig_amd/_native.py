@@ -94,6 +94,9 @@ def host():
         "apzh_root_sample": (C.c_int, [C.c_int, C.c_int, f64p, i32p, i32p, C.c_double, C.c_double, C.c_int, u32p, i32p,
                                        i32p, f64p, f64p, i32p, C.c_int]),
         "apzh_pretouch_limit_gb": (C.c_double, [C.c_double, C.c_int]),
+        "apzh_game_save_size": (C.c_int64, [vp, C.c_int]),
+        "apzh_game_save": (C.c_int64, [vp, C.c_int, vp, C.c_int64]),
+        "apzh_game_load": (C.c_int, [vp, C.c_int, vp, C.c_int64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -110,7 +113,7 @@ HOST_SYMBOLS = ["apzh_last_error", "apzh_version", "apzh_create", "apzh_destroy"
                 "apzh_set_playouts_done", "apzh_set_n_playout", "apzh_node_children", "apzh_set_prior_mode",
                 "apzh_root_visits_dense", "apzh_update_with_move", "apzh_play_move", "apzh_play_moves", "apzh_stats",
                 "apzh_pool_info", "apzh_pure_get_move", "apzh_mt_seed", "apzh_np_sum", "apzh_root_sample",
-                "apzh_pretouch_limit_gb"]
+                "apzh_pretouch_limit_gb", "apzh_game_save_size", "apzh_game_save", "apzh_game_load"]
 
 HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create", "apz_destroy",
                "apz_param_count", "apz_param_name", "apz_param_size", "apz_load_weights", "apz_forward",

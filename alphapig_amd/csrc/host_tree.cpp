@@ -999,6 +999,170 @@ int apzh_pure_get_move(apzh_pool *p, int gi, uint32_t *mt_key624, int32_t *mt_po
     return move;
 }
 
+/* ---- one game out of a pool and back in (header: "checkpoint of one game slot") ------------------------------ */
+}  // extern "C"
+
+namespace {
+
+const uint32_t SAVE_MAGIC = 0x47485a41u;        // "AZHG"
+const uint32_t SAVE_VERSION = 1;
+
+struct SaveHeader {
+    uint32_t magic, version;
+    int32_t width, height, n_in_row, n_playout, prior_is_f32;
+    int32_t current_player, last_move, playouts_done, pending, pending_leaf, leaf_player;
+    int32_t n_hist, n_path, n_nodes;
+    int64_t n_net, n_term, peak_nodes;
+};
+static_assert(sizeof(SaveHeader) == 88, "the blob header has no padding");
+
+// bytes behind the header for a board of hw cells: cells i8, ply_of i16 | history i16 + i8 | path i16 | the eight arena arrays
+inline uint64_t save_body_bytes(uint64_t hw, uint64_t n_hist, uint64_t n_path, uint64_t n_nodes) {
+    return hw * 3 + n_hist * 3 + n_path * 2 + n_nodes * (uint64_t)Arena::bytes_per_node();
+}
+
+template <class T>
+inline uint8_t *put(uint8_t *at, const T *src, size_t count) {
+    if (count) std::memcpy(at, src, count * sizeof(T));
+    return at + count * sizeof(T);
+}
+
+template <class T>
+inline const uint8_t *get(const uint8_t *at, T *dst, size_t count) {
+    if (count) std::memcpy(dst, at, count * sizeof(T));
+    return at + count * sizeof(T);
+}
+
+// element i of an array of T that starts at `at` (blobs carry no alignment)
+template <class T>
+inline T peek(const uint8_t *at, size_t i) {
+    T v;
+    std::memcpy(&v, at + i * sizeof(T), sizeof(T));
+    return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t apzh_game_save_size(apzh_pool *p, int gi) {
+    CHECK_GAME(p, gi);
+    const Game &g = p->games[gi];
+    return (int64_t)(sizeof(SaveHeader) +
+                     save_body_bytes((uint64_t)p->hw, g.hist_move.size(), g.path.size(), (uint64_t)g.tree[g.cur].size()));
+}
+
+int64_t apzh_game_save(apzh_pool *p, int gi, void *buf, int64_t cap) {
+    CHECK_GAME(p, gi);
+    const Game &g = p->games[gi];
+    const Arena &t = g.tree[g.cur];
+    const int64_t need = apzh_game_save_size(p, gi);
+    if (!buf || cap < need) return fail(APZH_E_ARG, "save buffer too small");
+    SaveHeader h;
+    std::memset(&h, 0, sizeof h);
+    h.magic = SAVE_MAGIC; h.version = SAVE_VERSION;
+    h.width = p->cfg.width; h.height = p->cfg.height; h.n_in_row = p->cfg.n_in_row;
+    h.n_playout = p->cfg.n_playout; h.prior_is_f32 = p->cfg.prior_is_f32;
+    h.current_player = g.current_player; h.last_move = g.last_move; h.playouts_done = g.playouts_done;
+    h.pending = g.pending ? 1 : 0; h.pending_leaf = g.pending_leaf; h.leaf_player = g.leaf_player;
+    h.n_hist = (int32_t)g.hist_move.size(); h.n_path = (int32_t)g.path.size(); h.n_nodes = t.size();
+    h.n_net = g.n_net; h.n_term = g.n_term; h.peak_nodes = g.peak_nodes;
+    uint8_t *at = (uint8_t *)buf;
+    at = put(at, &h, 1);
+    at = put(at, g.cells.data(), (size_t)p->hw);
+    at = put(at, g.ply_of.data(), (size_t)p->hw);
+    at = put(at, g.hist_move.data(), g.hist_move.size());
+    at = put(at, g.hist_mover.data(), g.hist_mover.size());
+    at = put(at, g.path.data(), g.path.size());
+    const size_t n = (size_t)t.size();
+    at = put(at, t.parent.data(), n);
+    at = put(at, t.first_child.data(), n);
+    at = put(at, t.n.data(), n);
+    at = put(at, t.n_child.data(), n);
+    at = put(at, t.action.data(), n);
+    at = put(at, t.qk.data(), n);
+    at = put(at, t.q.data(), n);
+    at = put(at, t.prior.data(), n);
+    return (int64_t)(at - (uint8_t *)buf);
+}
+
+int apzh_game_load(apzh_pool *p, int gi, const void *buf, int64_t len) {
+    CHECK_GAME(p, gi);
+    if (!buf || len < (int64_t)sizeof(SaveHeader)) return fail(APZH_E_ARG, "game blob shorter than its header");
+    const uint8_t *at = (const uint8_t *)buf;
+    SaveHeader h;
+    at = get(at, &h, 1);
+    if (h.magic != SAVE_MAGIC) return fail(APZH_E_ARG, "not a game blob (magic)");
+    if (h.version != SAVE_VERSION) return fail(APZH_E_ARG, "game blob of another format version");
+    const apzh_config &c = p->cfg;
+    if (h.width != c.width || h.height != c.height || h.n_in_row != c.n_in_row)
+        return fail(APZH_E_ARG, "game blob of another board");
+    if (h.n_playout != c.n_playout) return fail(APZH_E_ARG, "game blob of another n_playout");
+    if (h.prior_is_f32 != c.prior_is_f32) return fail(APZH_E_ARG, "game blob of another prior mode");
+    const int hw = p->hw;
+    if (h.n_hist < 0 || h.n_path < 0 || h.n_nodes < 1 || (int64_t)h.n_hist + h.n_path > hw)
+        return fail(APZH_E_ARG, "game blob: bad counts");
+    if ((uint64_t)len != sizeof(SaveHeader) + save_body_bytes((uint64_t)hw, (uint64_t)h.n_hist, (uint64_t)h.n_path, (uint64_t)h.n_nodes))
+        return fail(APZH_E_ARG, "game blob: length does not match its counts");
+    if ((h.current_player != 1 && h.current_player != 2) || (h.leaf_player != 1 && h.leaf_player != 2) ||
+        h.last_move < -1 || h.last_move >= hw || h.playouts_done < 0 || (h.pending != 0 && h.pending != 1))
+        return fail(APZH_E_ARG, "game blob: bad scalar field");
+    if (h.pending ? (h.pending_leaf < 0 || h.pending_leaf >= h.n_nodes) : (h.pending_leaf != -1 || h.n_path != 0))
+        return fail(APZH_E_ARG, "game blob: pending leaf out of range");
+    if (h.n_path >= h.n_nodes) return fail(APZH_E_ARG, "game blob: path longer than the tree is deep");
+    const size_t n = (size_t)h.n_nodes;
+    const uint8_t *cells = at, *ply_of = cells + hw, *hist_move = ply_of + 2 * (size_t)hw,
+                  *hist_mover = hist_move + 2 * (size_t)h.n_hist, *path = hist_mover + h.n_hist,
+                  *parent = path + 2 * (size_t)h.n_path, *first_child = parent + 4 * n, *visits = first_child + 4 * n,
+                  *n_child = visits + 4 * n, *action = n_child + 2 * n, *qk = action + 2 * n, *q = qk + n, *prior = q + 8 * n;
+    int stones = 0;
+    for (int m = 0; m < hw; m++) {
+        if (cells[m] > 2) return fail(APZH_E_ARG, "game blob: bad cell");
+        stones += cells[m] != 0;
+        const int16_t ply = peek<int16_t>(ply_of, m);
+        if (ply < 0 || ply >= hw) return fail(APZH_E_ARG, "game blob: bad ply");
+    }
+    // (a search on a board with more stones than the history and the path count would not see the board fill up)
+    if (stones != h.n_hist + h.n_path) return fail(APZH_E_ARG, "game blob: the board does not hold the stones of its history");
+    for (int k = 0; k < h.n_hist; k++) {
+        const int16_t m = peek<int16_t>(hist_move, k);
+        if (m < 0 || m >= hw || (hist_mover[k] != 1 && hist_mover[k] != 2)) return fail(APZH_E_ARG, "game blob: bad history");
+    }
+    for (int k = 0; k < h.n_path; k++) {
+        const int16_t m = peek<int16_t>(path, k);
+        if (m < 0 || m >= hw) return fail(APZH_E_ARG, "game blob: path entry off the board");
+    }
+    // the arena: children come behind their parent (alloc appends, reroot copies breadth first), so every walk ends
+    for (size_t i = 0; i < n; i++) {
+        const int32_t par = peek<int32_t>(parent, i), fc = peek<int32_t>(first_child, i);
+        const int16_t nc = peek<int16_t>(n_child, i), act = peek<int16_t>(action, i);
+        if (i == 0 ? par != -1 : (par < 0 || (size_t)par >= i)) return fail(APZH_E_ARG, "game blob: parent index out of range");
+        if (fc != -1 && (fc <= (int32_t)i || nc < 1 || (int64_t)fc + nc > (int64_t)n))
+            return fail(APZH_E_ARG, "game blob: first_child / n_child out of range");
+        if (nc < 0 || nc > hw) return fail(APZH_E_ARG, "game blob: n_child out of range");
+        if (act >= hw || act < (i == 0 ? -1 : 0)) return fail(APZH_E_ARG, "game blob: action off the board");
+        if (qk[i] > APZH_Q_F32 || peek<int32_t>(visits, i) < 0) return fail(APZH_E_ARG, "game blob: bad node statistics");
+    }
+    // nothing was written so far; from here on nothing fails
+    Game &g = p->games[gi];
+    get(cells, g.cells.data(), (size_t)hw);
+    get(ply_of, g.ply_of.data(), (size_t)hw);
+    g.hist_move.resize((size_t)h.n_hist); get(hist_move, g.hist_move.data(), (size_t)h.n_hist);
+    g.hist_mover.resize((size_t)h.n_hist); get(hist_mover, g.hist_mover.data(), (size_t)h.n_hist);
+    g.path.resize((size_t)h.n_path); get(path, g.path.data(), (size_t)h.n_path);
+    g.current_player = h.current_player; g.last_move = h.last_move; g.playouts_done = h.playouts_done;
+    g.pending = h.pending != 0; g.pending_leaf = h.pending_leaf; g.leaf_player = h.leaf_player;
+    g.n_net = h.n_net; g.n_term = h.n_term; g.peak_nodes = h.peak_nodes;
+    Arena &t = g.tree[g.cur];                   // (clear + alloc: the reserved capacity stays)
+    g.tree[g.cur ^ 1].clear();
+    t.clear();
+    t.alloc((int)n);
+    get(parent, t.parent.data(), n); get(first_child, t.first_child.data(), n); get(visits, t.n.data(), n);
+    get(n_child, t.n_child.data(), n); get(action, t.action.data(), n); get(qk, t.qk.data(), n);
+    get(q, t.q.data(), n); get(prior, t.prior.data(), n);
+    return APZH_OK;
+}
+
 double apzh_pretouch_limit_gb(double avail_gb, int local_world) {
     if (local_world < 1) local_world = 1;
     // half of what is available, split between the ranks of this node, never more than 96 GB per rank.  A single rank keeps

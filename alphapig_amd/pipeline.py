@@ -42,7 +42,7 @@ Two schedules (`async_update` in the configuration; default True):
                GPU idles through every update).
   asynchronous (True)  nobody waits for the trainer.  Self-play runs in ROUNDS of `round_seconds` wall clock (or
                `round_steps` engine steps); at the end of a round every rank hands over the games it finished since the
-               last one (any number, also none) in one all-gather and receives a 9-float header from rank 0; weights
+               last one (any number, also none) in one all-gather and receives a 10-float header from rank 0; weights
                travel only in rounds in which rank 0 has a NEW version.  On rank 0 the trainer lives in its own thread
                with its own HIP stream, its own evaluator handle (KL monitor, arena) and its own HipTrainer: it takes
                the gathered game batches from a queue, puts them into the replay buffer, runs `policy_update` -- one per
@@ -55,6 +55,15 @@ Two schedules (`async_update` in the configuration; default True):
                inside a game, as in lock step.  `max_update_share` < 1 makes the trainer pause after an update so that it
                is busy at most that share of the time (on ONE GPU self-play and training share the device: the
                reference's one-update-per-game rule costs 0.36 - 0.55 of it; see profiles/r04_train_loop_15x15.log).
+
+Checkpoints (`checkpoint_every` game batches, default 0 = never; `resume=` of the constructor; alphapig_amd/checkpoint.py has
+the file layout).  Lock step: saved after batch i when (i + 1) % checkpoint_every == 0, and a resumed run() starts at the
+saved batch index with the trainer's weights installed in the evaluator the way an update installs them -- the run that was
+never stopped, bit for bit.  Asynchronous: the cut is a round boundary; when the collected games cross a multiple of
+checkpoint_every * play_batch_size rank 0 sets the header's tenth field, every rank writes its self-play part at that
+boundary, and rank 0 queues a marker behind that round's games; its trainer thread, on reaching the marker, writes the
+trainer, the buffer and the schedule and completes the directory.  The buffer then holds exactly the games handed over
+before the cut; self-play does not wait.  Consistent, and as timing-dependent as the schedule itself.
 """
 import logging
 import os
@@ -65,11 +74,11 @@ import time
 
 import numpy as np
 
-from . import dist, sgf
+from . import checkpoint, dist, sgf
 from .arena import Arena, win_ratio
 from .augment import get_equi_data
 from .game import Board, Game
-from .policy_value_net import PolicyValueNet
+from .policy_value_net import EvaluatorError, PolicyValueNet
 from .selfplay import SelfPlayEngine, episodes_to_tuples
 from .train import policy_update
 
@@ -116,16 +125,37 @@ class ReplayBuffer(object):
         """`rng.sample(list(buffer), k)` -- the same draws from the same generator state -- without the copy."""
         return [self[j] for j in rng.sample(range(len(self._items)), k)]
 
+    def state(self):
+        """The entries, oldest first, stacked: {"meta": maxlen and count, "states", "pis", "zs"} (9 000 B per entry on 15x15
+        where the code buffers of alphapig_amd/replay.py keep 143)."""
+        items = list(self)
+        out = {"meta": {"maxlen": self.maxlen, "n": len(items)}}
+        for j, name in enumerate(("states", "pis", "zs")):
+            out[name] = np.stack([np.asarray(x[j]) for x in items]) if items else np.zeros(0, np.float32)
+        return out
+
+    def load_state(self, state):
+        if int(state["meta"]["maxlen"]) != self.maxlen:
+            raise ValueError("this replay state was taken with maxlen=%r, the buffer has maxlen=%r" %
+                             (state["meta"]["maxlen"], self.maxlen))
+        n = int(state["meta"]["n"])
+        if n > self.maxlen or (n and not len(state["states"]) == len(state["pis"]) == len(state["zs"]) == n):
+            raise ValueError("this replay state does not hold the %d entries it announces" % n)
+        self._items = [(state["states"][i], state["pis"][i], state["zs"][i]) for i in range(n)]
+        self._head = 0
+
 
 class TrainPipeline(object):
     def __init__(self, conf, init_model=None, policy_value_net=None, device=0, seed=0, distributed=None, trainer=None,
-                 eval_net=None):
+                 eval_net=None, resume=None):
         """policy_value_net: an evaluator to use instead of building the HIP PolicyValueNet (needs evaluate_codes, params /
         set_params; policy_value for the KL monitor on rank 0).  trainer: an object with HipTrainer's interface
         (train_step, get_params; optionally sync_evaluator) to use instead of creating a HipTrainer -- the CPU tests pass
         stand-ins for both.  eval_net (asynchronous schedule, rank 0): the trainer thread's own evaluator for the KL
         monitor, checkpoints and the arena; default: a second HIP PolicyValueNet, or `policy_value_net` itself when one
-        was passed in.  distributed: None = on iff alphapig_amd.dist holds a process group."""
+        was passed in.  distributed: None = on iff alphapig_amd.dist holds a process group.
+        resume: the directory of a checkpoint (save_checkpoint; conf key checkpoint_every) written by a pipeline of the same
+        board, net, batch_size, buffer_size, replay, concurrent_games and world size: run() goes on where that one stood."""
         self.async_update = bool(conf.get("async_update", True))
         self.round_seconds = float(conf.get("round_seconds", 0.5))
         self.round_steps = conf.get("round_steps")
@@ -163,6 +193,19 @@ class TrainPipeline(object):
             if trainer is not None and not hasattr(trainer, "upload"):
                 raise RuntimeError("replay='device' hands the trainer mini-batches in GPU memory; the trainer passed in has "
                                    "no upload(), so it does not take device batches (replay='compact' stays on the host)")
+        # checkpoints (module docstring).  checkpoint_every: game batches between two of them, 0 (default) = never;
+        # checkpoint_keep: how many complete ones stay on disk; checkpoint_selfplay: "games" saves the games in flight with
+        # their trees, "none" abandons them (the game sequence and the finished games nobody took are kept either way);
+        # checkpoint_buffer: whether the replay buffer travels (default: the code buffers do, the 9 000 B tuples do not)
+        self.checkpoint_every = int(conf.get("checkpoint_every", 0) or 0)
+        self.checkpoint_keep = int(conf.get("checkpoint_keep", 2))
+        self.checkpoint_selfplay = conf.get("checkpoint_selfplay", "games")
+        if self.checkpoint_selfplay not in ("games", "none"):
+            raise ValueError("checkpoint_selfplay must be 'games' or 'none', not %r" % (self.checkpoint_selfplay,))
+        self.checkpoint_buffer = bool(conf.get("checkpoint_buffer", self.replay != "tuples"))
+        self._conf_match = {k: conf.get(k) for k in ("board_width", "board_height", "n_in_row", "n_blocks", "n_filter",
+                                                     "batch_size", "buffer_size", "concurrent_games")}
+        self._conf_match["replay"] = self.replay
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -192,6 +235,7 @@ class TrainPipeline(object):
             self._training_data = sgf.get_files_as_list(self._sgf_home)
             random.shuffle(self._training_data)
         self.model_dir = conf.get("model_dir", "./logs")
+        self.checkpoint_dir = conf.get("checkpoint_dir") or os.path.join(self.model_dir, "checkpoints")
         self.board = Board(width=self.board_width, height=self.board_height, n_in_row=self.n_in_row)
         self.game = Game(self.board)
         concurrent = conf.get("concurrent_games", 1024)
@@ -233,6 +277,16 @@ class TrainPipeline(object):
         self._trainer_error = None
         self._sgf_done = threading.Event()     # asynchronous schedule: set by rank 0's trainer thread behind the SGF bootstrap
         self._last = (0.0, 0.0, 0.0)
+        self._conf_match["world"] = self.world
+        self._batches_done = 0                  # lock step: the loop index run() starts at
+        self._eval_overflows0 = 0               # the self-play evaluator's overflow count before a resume
+        self.trainer_history = []
+        self._games_collected = 0
+        self._round = 0
+        self._async_resume = None               # asynchronous schedule: what the trainer thread picks up (resume=)
+        self.checkpoint_log = []                # one record per part written: (part, seconds, bytes)
+        if resume is not None:
+            self._resume(resume)
 
     # ---- data collection -----------------------------------------------------------------
     def collect_selfplay_data_ai(self, n_games=1):
@@ -303,7 +357,7 @@ class TrainPipeline(object):
         (evaluators without such a count: left out); act_scale "auto": its current activation exponents too."""
         net = self.policy_value_net
         if hasattr(net, "trunk_overflows"):
-            rec["eval_trunk_overflows"] = int(net.trunk_overflows())
+            rec["eval_trunk_overflows"] = self._eval_overflows0 + int(net.trunk_overflows())
         if self.act_scale == "auto":
             rec["act_exponents"] = [int(a) for a in net.trunk_act_exponents()]
 
@@ -388,7 +442,7 @@ class TrainPipeline(object):
         if self.async_update:
             return self._run_async()
         lead = self.rank == 0
-        for i in range(self.game_batch_num):
+        for i in range(self._batches_done, self.game_batch_num):
             if i < self.sgf_batches and self._training_data:
                 if lead:                                    # game records are rank 0's (lock step: the other ranks wait in the next collective)
                     self.collect_selfplay_data(i)
@@ -413,7 +467,163 @@ class TrainPipeline(object):
                         self.best_win_ratio = 0.0
             self.history.append(rec)
             _logger.info("batch %s", rec)
+            self._batches_done = i + 1
+            if self.checkpoint_every and (i + 1) % self.checkpoint_every == 0:
+                self.save_checkpoint(os.path.join(self.checkpoint_dir, "ckpt_%08d" % (i + 1)))
+                if lead:
+                    checkpoint.prune(self.checkpoint_dir, self.checkpoint_keep)
         return self.history
+
+    # ---- checkpoints (alphapig_amd/checkpoint.py holds the file layout) ------------------------------------------------
+    def _timed_part(self, directory, part, state):
+        t0 = time.perf_counter()
+        nbytes = checkpoint.write_part(directory, part, state)
+        self.checkpoint_log.append((part, time.perf_counter() - t0, nbytes))
+
+    def _write_selfplay_part(self, directory):
+        """This rank's engine, between two run_steps calls (the caller's thread is the one that drives the engine)"""
+        t0 = time.perf_counter()
+        state = self.engine.state(games=self.checkpoint_selfplay == "games")
+        nbytes = checkpoint.write_part(directory, "selfplay_rank%d" % self.rank, state)
+        self.checkpoint_log.append(("selfplay_rank%d" % self.rank, time.perf_counter() - t0, nbytes))
+
+    def _write_trainer_parts(self, directory, trainer):
+        """Rank 0: the trainer (or, before the first update, the evaluator's weights) and the replay buffer"""
+        if trainer is not None:
+            if not hasattr(trainer, "state"):
+                raise RuntimeError("a checkpoint needs a trainer with state() / load_state(); %r has none" % (trainer,))
+            self._timed_part(directory, "trainer", trainer.state())
+        else:
+            self._timed_part(directory, "weights", dict(self.policy_value_net.params(), meta={}))
+        if self.checkpoint_buffer:
+            self._timed_part(directory, "buffer", self.data_buffer.state())
+
+    def _schedule_state(self):
+        """The values the training side owns (lock step: the one thread; asynchronous: the trainer thread)"""
+        return {"lr_multiplier": self.lr_multiplier, "best_win_ratio": self.best_win_ratio,
+                "pure_mcts_playout_num": self.pure_mcts_playout_num, "train_steps": self._train_steps,
+                "rng": checkpoint.rng_to_json(self._rng), "updates_done": self.updates_done,
+                "updates_skipped": self.updates_skipped, "trainer_history": list(self.trainer_history),
+                "last": list(self._last), "with_buffer": self.checkpoint_buffer}
+
+    def _main_state(self):
+        """The values the self-play side owns, and the configuration a resumed run must share"""
+        net = self.policy_value_net
+        out = {"format": checkpoint.FORMAT, "conf": dict(self._conf_match), "async_update": self.async_update,
+               "next_batch": self._batches_done, "taken": self._taken, "episode_len": self.episode_len,
+               "weights_version": self.weights_version, "games_collected": self._games_collected, "round": self._round,
+               "training_data": list(self._training_data), "history": list(self.history),
+               "checkpoint_selfplay": self.checkpoint_selfplay,
+               "eval_trunk_overflows": self._eval_overflows0 + (int(net.trunk_overflows()) if hasattr(net, "trunk_overflows") else 0)}
+        if hasattr(net, "trunk_act_exponents"):
+            try:
+                out["act_exponents"] = [int(a) for a in net.trunk_act_exponents()]
+            except EvaluatorError:          # (the 8x8 kernels and the other arithmetics have no such exponents)
+                pass
+        return out
+
+    def save_checkpoint(self, path):
+        """Write everything a later TrainPipeline(conf, resume=path) needs to go on from here: legal between two game
+        batches of the lock-step schedule (run() calls it every `checkpoint_every` batches; the asynchronous schedule
+        writes its checkpoints itself, at a round boundary).  With several ranks every rank calls it, with the same path on
+        a file system all of them see: each writes its own self-play part, rank 0 the rest."""
+        lead = self.rank == 0
+        tmp = checkpoint.tmp_path(path)
+        if lead:
+            checkpoint.begin(path)
+        if self.distributed:
+            dist.barrier()
+        self._write_selfplay_part(tmp)
+        if self.distributed:
+            dist.barrier()
+        if not lead:
+            return path
+        missing = [r for r in range(self.world) if not checkpoint.has_part(tmp, "selfplay_rank%d" % r)]
+        if missing:
+            raise RuntimeError("checkpoint %s: no self-play part of rank(s) %s -- every rank must write into the same "
+                               "directory (conf checkpoint_dir on a file system all ranks see)" % (path, missing))
+        trainer = self._trainer_override
+        if trainer is None:
+            trainer = getattr(self.policy_value_net, "_trainer", None)
+        self._write_trainer_parts(tmp, trainer)
+        state = self._main_state()
+        state.update(self._schedule_state())
+        checkpoint.finish(path, state)
+        _logger.info("checkpoint %s", path)
+        return path
+
+    def _resume(self, path):
+        state = checkpoint.read_state(path)
+        for k, mine in self._conf_match.items():
+            if state["conf"].get(k) != mine:
+                raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
+                                 (path, k, state["conf"].get(k), k, mine))
+        if bool(state["async_update"]) != self.async_update:
+            raise ValueError("the checkpoint %s was written with async_update=%r" % (path, state["async_update"]))
+        part = "selfplay_rank%d" % self.rank
+        if not checkpoint.has_part(path, part):
+            raise ValueError("the checkpoint %s has no part %s" % (path, part))
+        self.engine.load_state(checkpoint.read_part(path, part))
+        self.lr_multiplier = state["lr_multiplier"]
+        self.best_win_ratio = state["best_win_ratio"]
+        self.pure_mcts_playout_num = state["pure_mcts_playout_num"]
+        self._train_steps = state["train_steps"]
+        checkpoint.rng_from_json(self._rng, state["rng"])
+        self.updates_done, self.updates_skipped = state["updates_done"], state["updates_skipped"]
+        self._last = tuple(state["last"])
+        self._batches_done = state["next_batch"]
+        self._taken, self.episode_len = state["taken"], state["episode_len"]
+        self.weights_version = state["weights_version"]
+        self._games_collected, self._round = state["games_collected"], state["round"]
+        self._training_data = list(state["training_data"])
+        self.history = list(state["history"])
+        self.trainer_history = list(state["trainer_history"])
+        self._eval_overflows0 = int(state.get("eval_trunk_overflows", 0))
+        net = self.policy_value_net
+        has_buffer = self.rank == 0 or self.keep_replica_buffers
+        if has_buffer and checkpoint.has_part(path, "buffer"):
+            self.data_buffer.load_state(checkpoint.read_part(path, "buffer"))
+        elif has_buffer:
+            _logger.info("the checkpoint %s holds no replay buffer: the resumed run starts with an empty buffer", path)
+        # the weights: the trainer's, installed in the self-play evaluator the way an update installs them
+        tstate = checkpoint.read_part(path, "trainer") if checkpoint.has_part(path, "trainer") else None
+        if tstate is None:
+            w = checkpoint.read_part(path, "weights")
+            net.set_params({k: v for k, v in w.items() if k != "meta"}, _keep_trainer=True)
+        else:
+            weights = {k[2:]: v for k, v in tstate.items() if k.startswith("p/")}
+            if self.rank == 0 and (self._trainer_override is not None or not self.async_update):
+                tr = self._trainer()
+                if not hasattr(tr, "load_state"):
+                    raise RuntimeError("resume needs a trainer with state() / load_state(); %r has none" % (tr,))
+                tr.load_state(tstate)
+                if hasattr(tr, "sync_evaluator") and hasattr(net, "load_device_params"):
+                    tr.sync_evaluator(net)
+                else:
+                    net.set_params(tr.get_params(), _keep_trainer=True)
+            else:
+                if self.rank == 0:
+                    self._async_trainer_state = tstate          # the trainer thread builds its trainer, then loads this
+                self._install_host_weights(weights)
+        if "act_exponents" in state and hasattr(net, "set_trunk_act_exponents") and any(state["act_exponents"]):
+            net.set_trunk_act_exponents(state["act_exponents"])
+        self._async_resume = {"games_recv": state.get("games_recv", 0), "batches_done": state.get("trainer_batches_done", 0)}
+        if self.async_update:
+            self.weights_version = max(self.weights_version, int(self.updates_done))   # (versions count updates; the evaluator holds the trainer's)
+        _logger.info("resumed from %s: next batch %d, %d games taken so far", path, self._batches_done, self._taken)
+
+    def _install_host_weights(self, weights):
+        """Weights read from a checkpoint into the self-play evaluator: through device tensors where the evaluator folds
+        and packs on the device (what a broadcast update does on a GPU rank), else through set_params"""
+        net = self.policy_value_net
+        if hasattr(net, "load_device_params") and hasattr(net, "_device"):
+            import torch
+            dev = torch.device("cuda", int(net._device))
+            self._held = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in weights.items()}
+            torch.cuda.synchronize(dev)
+            net.load_device_params(self._held)
+        else:
+            net.set_params(weights, _keep_trainer=True)
 
     # ---- the asynchronous schedule (module docstring) ---------------------------------------------
     def _play_round(self):
@@ -474,7 +684,12 @@ class TrainPipeline(object):
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                          device_index=net._device, seed=self._seed, trunk_arith=self.train_arith)
                 self._async_trainer = trainer
-                games_recv = 0
+                tstate = getattr(self, "_async_trainer_state", None)
+                if tstate is not None:                  # resume=: the trainer this thread built continues the saved one
+                    trainer.load_state(tstate)
+                    self._async_trainer_state = None
+                resumed = self._async_resume or {}
+                games_recv = int(resumed.get("games_recv", 0))
                 busy_until = 0.0
                 stop = False
                 # SGF bootstrap (train_mxnet.py:270-271: the first batches replay game records instead of searching):
@@ -482,7 +697,7 @@ class TrainPipeline(object):
                 # starts from the net these batches trained (train_mxnet.py:268-272): every rank HOLDS in _run_async until
                 # `_sgf_done` is set, so no game of the untrained net enters the buffer or counts toward the budget.
                 n_sgf = self._sgf_phase_batches()
-                for i in range(n_sgf):
+                for i in range(min(n_sgf, int(resumed.get("batches_done", 0))), n_sgf):
                     before = len(self.data_buffer)
                     self.collect_selfplay_data(i)
                     # (the record's own length: self.episode_len belongs to the main thread once self-play runs)
@@ -505,7 +720,7 @@ class TrainPipeline(object):
                     with self._lock:
                         self.trainer_history.append(rec)
                 self._sgf_done.set()
-                batches_done = n_sgf
+                batches_done = max(n_sgf, int(resumed.get("batches_done", 0)))
                 while not stop:
                     items = [self._train_q.get()]
                     while True:
@@ -516,6 +731,9 @@ class TrainPipeline(object):
                     for it in items:
                         if it is None:
                             stop = True
+                            continue
+                        if isinstance(it[0], str):      # the checkpoint marker: the buffer holds exactly the games before the cut
+                            self._write_async_checkpoint(it[1], it[2], trainer, games_recv, batches_done)
                             continue
                         codes, pis, zs, n_games = it
                         if self.replay != "tuples":
@@ -593,8 +811,10 @@ class TrainPipeline(object):
         lead = self.rank == 0
         # the SGF bootstrap batches (rank 0's trainer thread) count as game batches, like the reference's loop index
         target_games = (self.game_batch_num - self._sgf_phase_batches()) * self.play_batch_size * self.world
-        self.trainer_history = []
-        self._games_collected = 0
+        if self._async_resume is None:
+            self.trainer_history = []
+            self._games_collected = 0
+            self._round = 0
         if lead:
             self._train_q = queue.Queue()
             self.engine.gate = self._gpu_gate if self.exclusive_updates else None
@@ -615,7 +835,7 @@ class TrainPipeline(object):
                 raise RuntimeError("the trainer thread died on rank 0") from (self._trainer_error if lead else None)
             if flags[0] != 0.0:
                 break
-        rnd = 0
+        rnd = self._round
         stop = False
         draining = False            # the budget is reached and rank 0's trainer works off its queue: rounds without play
         while not stop:
@@ -641,13 +861,26 @@ class TrainPipeline(object):
                 n_games = int(round(dist.all_reduce_sum(len(eps))))
                 codes, pis, zs = dist.all_gather_tuples(codes, pis, zs, consumer=0)      # THE exchange of the round
             self.last_gathered = n_games
-            head = [0.0] * 9
+            head = [0.0] * 10
             fresh = None
             failed = False
             if lead:
                 self._games_collected += n_games
                 if len(zs) and self._trainer_error is None:
                     self._train_q.put((codes, pis, zs, n_games))
+                cut = 0
+                if self.checkpoint_every and n_games and not draining and self._trainer_error is None:
+                    unit = self.checkpoint_every * self.play_batch_size
+                    if self._games_collected // unit > (self._games_collected - n_games) // unit:
+                        cut = self._games_collected // unit
+                if cut:
+                    # the cut is this round boundary: rank 0's engine now, every other rank's behind the header, the
+                    # trainer's side when its thread reaches the marker behind this round's data -- nobody waits for it
+                    path = self._async_checkpoint_path(cut)
+                    checkpoint.begin(path)
+                    self._round = rnd
+                    self._write_selfplay_part(checkpoint.tmp_path(path))
+                    self._train_q.put(("checkpoint", path, self._main_state()))
                 done = self._games_collected >= target_games
                 state = 0.0
                 if done and self._trainer_error is None:
@@ -661,7 +894,7 @@ class TrainPipeline(object):
                     loss, entropy, kl = self._last
                     head = [state, float(fresh[0]) if fresh else float(self.weights_version),
                             float(self.updates_done), loss, entropy, kl, self.lr_multiplier, float(self._games_collected),
-                            float(self.updates_skipped)]
+                            float(self.updates_skipped), float(cut)]
                 if failed:
                     head[0] = -1.0
             if self.distributed:
@@ -669,6 +902,8 @@ class TrainPipeline(object):
             if head[0] < 0.0:
                 # rank 0 raises with the cause; the others raise too instead of blocking in the next collective
                 raise RuntimeError("the trainer thread died on rank 0") from (self._trainer_error if lead else None)
+            if head[9] > 0.0 and not lead:
+                self._write_selfplay_part(checkpoint.tmp_path(self._async_checkpoint_path(int(head[9]))))
             version = int(head[1])
             rec = {"round": rnd, "games": n_games, "games_collected": int(head[7]), "version": version,
                    "updates": int(head[2]), "updates_skipped": int(head[8]), "leaf_evals": int(self.engine.stats["leaf_evals"])}
@@ -681,6 +916,28 @@ class TrainPipeline(object):
             stop = head[0] == 1.0
             draining = head[0] == 2.0
         return self.history
+
+    def _async_checkpoint_path(self, cut):
+        return os.path.join(self.checkpoint_dir, "ckpt_%08d" % (int(cut) * self.checkpoint_every))
+
+    def _write_async_checkpoint(self, path, main_state, trainer, games_recv, batches_done):
+        """Rank 0's trainer thread, at the marker: its own parts, then -- once every rank's self-play part is there --
+        state.json and COMPLETE"""
+        tmp = checkpoint.tmp_path(path)
+        self._write_trainer_parts(tmp, trainer)
+        state = dict(main_state)
+        with self._lock:
+            state.update(self._schedule_state())
+        state.update(games_recv=int(games_recv), trainer_batches_done=int(batches_done))
+        t_end = time.time() + 120.0
+        while not all(checkpoint.has_part(tmp, "selfplay_rank%d" % r) for r in range(self.world)):
+            if time.time() > t_end:
+                _logger.error("checkpoint %s abandoned: a rank's self-play part did not arrive", path)
+                return
+            time.sleep(0.05)
+        checkpoint.finish(path, state)
+        checkpoint.prune(self.checkpoint_dir, self.checkpoint_keep)
+        _logger.info("checkpoint %s", path)
 
     def close(self):
         self.engine.close()

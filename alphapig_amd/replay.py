@@ -118,7 +118,7 @@ class _Decoder(object):
 
 
 class _CodeBuffer(object):
-    """The interface of both backends; the storage itself (`_alloc`, `_write`, `_rows`, `_gather`) is the backend's."""
+    """The interface of both backends; the storage itself (`_alloc`, `_write`, `_read`, `_rows`, `_gather`) is the backend's."""
 
     def __init__(self, maxlen, height, width, c_in=9):
         if int(height) != int(width):
@@ -157,6 +157,50 @@ class _CodeBuffer(object):
             raise ValueError("extend_planes: these planes are not the planes of a position (no code row reproduces them)")
         self.extend_codes(codes, pis, zs)
 
+    # ---- checkpoint: the live tuples only, oldest first
+    def _live(self):
+        """-> (number of the oldest live tuple, how many are live, their ring segments [(slot, count)] -- two at the wrap)"""
+        A, n, cap = self.ring.appended, len(self.ring), self.ring.capacity
+        if A == 0:
+            return 0, 0, []
+        first = (A - n) // 8
+        count = (A + 7) // 8 - first
+        slot = first % cap
+        head = min(count, cap - slot)
+        return first, count, [(slot, head)] + ([(0, count - head)] if count > head else [])
+
+    def state(self):
+        """{"meta": maxlen, board, c_in and the count of entries appended so far; "codes" / "pi" / "z": the tuples the live
+        entries belong to -- tuple numbers (appended - len) // 8 to ceil(appended / 8) - 1 -- in order} as host arrays."""
+        _, count, segs = self._live()
+        parts = [self._read(slot, cnt) for slot, cnt in segs]
+        cat = lambda j, empty: np.concatenate([p[j] for p in parts]) if parts else empty
+        return {"meta": {"maxlen": self.maxlen, "height": self.height, "width": self.width, "c_in": self.c_in,
+                         "appended": int(self.ring.appended)},
+                "codes": cat(0, np.zeros((0, self.code_stride), np.uint8)), "pi": cat(1, np.zeros((0, self.hw), np.float32)),
+                "z": cat(2, np.zeros(0, np.float32))}
+
+    def load_state(self, state):
+        """The inverse of state(), into a buffer of the same maxlen, board and c_in (anything else: ValueError)."""
+        meta = state["meta"]
+        for k in ("maxlen", "height", "width", "c_in"):
+            if int(meta[k]) != getattr(self, k):
+                raise ValueError("this replay state was taken with %s=%r, the buffer has %s=%r" % (k, meta[k], k, getattr(self, k)))
+        appended = int(meta["appended"])
+        codes = np.ascontiguousarray(state["codes"], dtype=np.uint8).reshape(-1, self.code_stride)
+        pis = np.ascontiguousarray(state["pi"], dtype=np.float32).reshape(-1, self.hw)
+        zs = np.ascontiguousarray(state["z"], dtype=np.float32).reshape(-1)
+        old = self.ring.appended
+        self.ring.appended = appended
+        _, count, segs = self._live()
+        if appended < 0 or appended % 8 or not len(codes) == len(pis) == len(zs) == count:
+            self.ring.appended = old
+            raise ValueError("this replay state holds %d tuples; %d appended entries keep %d alive" % (len(codes), appended, count))
+        at = 0
+        for slot, cnt in segs:
+            self._write(slot, codes[at:at + cnt], pis[at:at + cnt], zs[at:at + cnt])
+            at += cnt
+
     def sample(self, rng, k):
         """-> DeviceBatch(states, pis, zs) of k entries, drawn like ReplayBuffer.sample draws them"""
         return self._gather(self.ring.sample(rng, k))
@@ -186,6 +230,9 @@ class CompactReplayBuffer(_CodeBuffer):
 
     def _rows(self, slot):
         return self.codes[slot:slot + 1], self.pi[slot], self.z[slot]
+
+    def _read(self, slot, cnt):
+        return self.codes[slot:slot + cnt].copy(), self.pi[slot:slot + cnt].copy(), self.z[slot:slot + cnt].copy()
 
     def _gather(self, words):
         slots, syms = words >> 3, words & 7
@@ -230,6 +277,9 @@ class DeviceReplayBuffer(_CodeBuffer):
 
     def _rows(self, slot):
         return self.codes[slot:slot + 1].cpu().numpy(), self.pi[slot].cpu().numpy(), self.z[slot].cpu().numpy()[()]
+
+    def _read(self, slot, cnt):
+        return tuple(t[slot:slot + cnt].cpu().numpy() for t in (self.codes, self.pi, self.z))
 
     def _gather(self, words):
         from . import hipconv

@@ -404,6 +404,147 @@ class SelfPlayEngine(object):
         out = sorted(self.finished, key=lambda e: e.index)
         return out
 
+    # ---- checkpoint ------------------------------------------------------------------------
+    _STATE_KEYS = ("board_width", "board_height", "n_in_row", "n_games", "n_playout", "sampler", "index_offset",
+                   "index_stride", "base_seed")
+    _STATE_STATS = ("games", "plies", "moves", "leaf_evals", "forced_openings")
+
+    def _state_meta(self):
+        p = self.pool
+        return {"board_width": p.width, "board_height": p.height, "n_in_row": p.n_in_row, "n_games": self.G,
+                "n_playout": self.n_playout, "sampler": self.sampler, "index_offset": self.index_offset,
+                "index_stride": self.index_stride, "base_seed": self.base_seed}
+
+    def state(self, games=True):
+        """Everything the next run_steps reads, as {"meta": plain values, name: ndarray, ...} -- what load_state takes,
+        and what np.save / json can write without pickling.  Legal between run_steps calls only (run_steps leaves no
+        evaluation in flight: it collects and feeds every group before it returns).
+        Per slot: active, index, the NumPy legacy stream, random.Random's state, the recorded codes / pis / movers and the
+        pool's game blob (board, live tree, counters); the finished episodes nobody took yet; next_index, slot_games, the
+        sample step and the counters.  games=False leaves the slots out: their games are abandoned, and a loaded engine
+        starts fresh games at next_index."""
+        hw, stride = self.hw, self.pool.code_stride
+        meta = self._state_meta()
+        meta.update(next_index=int(self.next_index), sample_step=int(self._sample_step), with_games=bool(games),
+                    stats={k: int(self.stats[k]) for k in self._STATE_STATS})
+        out = {"meta": meta, "slot_games": self.slot_games.copy()}
+        fin = self.finished
+        out["fin_index"] = np.array([e.index for e in fin], dtype=np.int64)
+        out["fin_winner"] = np.array([e.winner for e in fin], dtype=np.int64)
+        out["fin_len"] = np.array([len(e.movers) for e in fin], dtype=np.int64)
+        out["fin_moves"] = np.concatenate([e.moves for e in fin] + [np.zeros(0, np.int32)]).astype(np.int32)
+        out["fin_movers"] = np.concatenate([e.movers for e in fin] + [np.zeros(0, np.int8)]).astype(np.int8)
+        out["fin_codes"] = np.concatenate([e.codes for e in fin] + [np.zeros((0, stride), np.uint8)]).astype(np.uint8)
+        out["fin_pis"] = np.concatenate([e.pis for e in fin] + [np.zeros((0, hw))]).astype(np.float64)
+        out["fin_zs"] = np.concatenate([e.zs for e in fin] + [np.zeros(0)]).astype(np.float64)
+        if self.last_codes is not None:
+            out["last_codes"] = np.array(self.last_codes, dtype=np.uint8)
+        if not games:
+            return out
+        G = self.G
+        active = np.array([s.active for s in self.slots], dtype=np.bool_)
+        out["active"] = active
+        out["index"] = np.array([s.index if s.active else -1 for s in self.slots], dtype=np.int64)
+        keys = np.zeros((G, 624), dtype=np.uint32)
+        pos = np.zeros(G, dtype=np.int32)
+        has_gauss = np.zeros(G, dtype=np.int32)
+        gauss = np.zeros(G, dtype=np.float64)
+        py_key = np.zeros((G, 625), dtype=np.uint32)
+        py_gauss = np.full(G, np.nan)               # random.Random's gauss_next; NaN stands for None
+        codes, pis, movers = [], [], []
+        rec_len = np.zeros(G, dtype=np.int64)
+        # the game blobs (the trees: gigabytes for 1024 games at n_playout 400) are written straight into ONE array
+        blob_len = np.array([self.pool.save_size(s) if slot.active else 0 for s, slot in enumerate(self.slots)], dtype=np.int64)
+        blobs = np.empty(int(blob_len.sum()), dtype=np.uint8)
+        blob_at = 0
+        for s, slot in enumerate(self.slots):
+            if not slot.active:
+                continue
+            st = self.rng_bank.get_state(s) if self.rng_bank is not None else slot.rng.get_state()
+            keys[s], pos[s], has_gauss[s], gauss[s] = st[1], st[2], st[3], st[4]
+            version, key, gnext = slot.pyrnd.getstate()
+            if version != 3:
+                raise RuntimeError("random.Random state version %r" % (version,))
+            py_key[s] = key
+            if gnext is not None:
+                py_gauss[s] = gnext
+            rec_len[s] = len(slot.movers)
+            codes.extend(slot.codes)
+            pis.extend(slot.pis)
+            movers.extend(slot.movers)
+            if self.pool.save_game_into(s, blobs[blob_at:blob_at + blob_len[s]]) != blob_len[s]:
+                raise RuntimeError("slot %d: the game blob changed its size while it was saved" % s)
+            blob_at += int(blob_len[s])
+        out.update(rng_keys=keys, rng_pos=pos, rng_has_gauss=has_gauss, rng_gauss=gauss, py_key=py_key, py_gauss=py_gauss,
+                   rec_len=rec_len, blob_len=blob_len)
+        out["rec_codes"] = np.array(codes, dtype=np.uint8).reshape(-1, stride)
+        out["rec_pis"] = np.array(pis, dtype=np.float64).reshape(-1, hw)
+        out["rec_movers"] = np.array(movers, dtype=np.int32).reshape(-1)
+        out["blobs"] = blobs
+        return out
+
+    def load_state(self, state):
+        """Continue where the engine that returned `state` stood.  That engine must have had the same board, n_games,
+        n_playout, sampler, index_offset, index_stride and base_seed: anything else is a ValueError naming the field, raised
+        before this engine changes.  Legal between run_steps calls only."""
+        meta = state["meta"]
+        mine = self._state_meta()
+        for k in self._STATE_KEYS:
+            if meta.get(k) != mine[k]:
+                raise ValueError("this state was taken with %s=%r, the engine has %s=%r" % (k, meta.get(k), k, mine[k]))
+        hw, stride = self.hw, self.pool.code_stride
+        with_games = bool(meta.get("with_games", True))
+        if with_games:
+            active = np.asarray(state["active"], dtype=np.bool_)
+            rec_at = np.concatenate([[0], np.cumsum(state["rec_len"])]).astype(np.int64)
+            blob_at = np.concatenate([[0], np.cumsum(state["blob_len"])]).astype(np.int64)
+            if (len(active) != self.G or rec_at[-1] != len(state["rec_codes"]) or blob_at[-1] != len(state["blobs"]) or
+                    np.asarray(state["rec_codes"]).shape[1:] != (stride,) or np.asarray(state["rec_pis"]).shape[1:] != (hw,)):
+                raise ValueError("this state's per-slot arrays do not fit together")
+            blobs = np.ascontiguousarray(state["blobs"], dtype=np.uint8)
+            for s in range(self.G):                 # (a refused blob leaves its slot alone; the slots before it are reset below)
+                if active[s]:
+                    try:
+                        self.pool.load_game(s, blobs[blob_at[s]:blob_at[s + 1]])
+                    except Exception:
+                        for r in range(s):
+                            self.pool.reset(r, 0)
+                        for slot in self.slots:
+                            slot.active = False
+                        self._active_epoch += 1
+                        raise
+        self.next_index = int(meta["next_index"])
+        self._sample_step = int(meta["sample_step"])
+        for k in self._STATE_STATS:
+            self.stats[k] = int(meta["stats"][k])
+        self.slot_games[:] = state["slot_games"]
+        fin_at = np.concatenate([[0], np.cumsum(state["fin_len"])]).astype(np.int64)
+        self.finished = [
+            Episode(int(state["fin_index"][i]), np.array(state["fin_moves"][a:b], dtype=np.int32),
+                    np.array(state["fin_movers"][a:b], dtype=np.int8), np.array(state["fin_codes"][a:b], dtype=np.uint8),
+                    np.array(state["fin_pis"][a:b], dtype=np.float64), np.array(state["fin_zs"][a:b], dtype=np.float64),
+                    int(state["fin_winner"][i]))
+            for i, (a, b) in enumerate(zip(fin_at[:-1], fin_at[1:]))]
+        self.last_codes = np.array(state["last_codes"], dtype=np.uint8) if "last_codes" in state else None
+        self._active_epoch += 1
+        self._grp_cache = {}
+        for s, slot in enumerate(self.slots):
+            slot.active = bool(with_games and active[s])
+            if not slot.active:
+                continue
+            slot.index = int(state["index"][s])
+            rs = np.random.RandomState(0)
+            rs.set_state(("MT19937", np.asarray(state["rng_keys"][s], dtype=np.uint32), int(state["rng_pos"][s]),
+                          int(state["rng_has_gauss"][s]), float(state["rng_gauss"][s])))
+            self.set_slot_rng(s, rs)
+            g = float(state["py_gauss"][s])
+            slot.pyrnd = _random.Random(0)
+            slot.pyrnd.setstate((3, tuple(int(x) for x in state["py_key"][s]), None if g != g else g))
+            a, b = rec_at[s], rec_at[s + 1]
+            slot.codes = [np.array(r, dtype=np.uint8) for r in state["rec_codes"][a:b]]
+            slot.pis = [np.array(r, dtype=np.float64) for r in state["rec_pis"][a:b]]
+            slot.movers = [int(m) for m in state["rec_movers"][a:b]]
+
     def terminal_playouts(self):
         return sum(self.pool.stats(s)["terminal_playouts"] for s in range(self.G))
 

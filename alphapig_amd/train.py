@@ -408,6 +408,44 @@ class HipTrainer(object):
     def get_params(self):
         return collections.OrderedDict((k, v.cpu().numpy()) for k, v in self.p.items())
 
+    # ---- checkpoint -----------------------------------------------------------------------------------------------
+    def state(self):
+        """Everything the next train_step reads, as host values: {"meta": t, dropout_step0, seed, trunk_overflows and the
+        net's kind (the dropout masks are keyed by seed and dropout_step0 + t), "p/<name>": every parameter and BatchNorm
+        statistic, "m/<name>" / "v/<name>": Adam's moments} -- what load_state takes."""
+        out = {"meta": {"t": int(self.t), "dropout_step0": int(self.dropout_step0), "seed": int(self.seed),
+                        "trunk_overflows": int(self.trunk_overflows), "net_kind": self.kind, "n_blocks": int(self.n_blocks),
+                        "trunk_arith": self.trunk_arith}}
+        for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
+            for k, t in group.items():
+                out["%s/%s" % (tag, k)] = t.cpu().numpy()
+        return out
+
+    def load_state(self, state):
+        """Continue where the trainer that returned `state` stood (same net: names and shapes are checked before anything
+        is written).  The values are copied INTO the existing tensors: the trunk weights, biases and statistics are views
+        into the packed buffers the kernels read.  The internal evaluator is stale afterwards and re-synchronises on its
+        next use."""
+        meta = state["meta"]
+        if meta["net_kind"] != self.kind or int(meta["n_blocks"]) != self.n_blocks:
+            raise ValueError("this trainer state belongs to a %s net of %s blocks" % (meta["net_kind"], meta["n_blocks"]))
+        todo = []
+        for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
+            for k, t in group.items():
+                a = state.get("%s/%s" % (tag, k))
+                if a is None or tuple(np.shape(a)) != tuple(t.shape):
+                    raise ValueError("this trainer state has no %s/%s of shape %s" % (tag, k, tuple(t.shape)))
+                todo.append((t, np.ascontiguousarray(a, dtype=np.float32)))
+        for t, a in todo:
+            t.copy_(self.torch.from_numpy(a))
+        self.torch.cuda.current_stream(self.device).synchronize()
+        self.t = int(meta["t"])
+        self.dropout_step0 = int(meta["dropout_step0"])
+        self.seed = int(meta["seed"])
+        self.trunk_overflows = int(meta["trunk_overflows"])
+        self._eval_t = -1
+        self.tape = None
+
     def get_grads(self):
         return collections.OrderedDict((k, self.grad[k].cpu().numpy()) for k in self.train_names)
 

@@ -215,6 +215,29 @@ class TreePool(object):
         self._ck(self.L.apzh_pool_info(self._h, as_ptr(out, C.c_int64)))
         return dict(arena_bytes=int(out[0]), pretouched=bool(out[1]), peak_nodes=int(out[2]), live_nodes=int(out[3]))
 
+    # ---- checkpoint of one slot
+    def save_game(self, g):
+        """Everything a later advance / feed / play_moves of slot g reads (board, live tree, pending leaf, counters)
+        -> bytes for load_game, on this pool or another one of the same board, n_playout and prior mode."""
+        buf = np.empty(self.save_size(g), dtype=np.uint8)
+        return buf[:self.save_game_into(g, buf)].tobytes()
+
+    def save_size(self, g):
+        """bytes save_game(g) would return now"""
+        return self._ck(self.L.apzh_game_save_size(self._h, int(g)))
+
+    def save_game_into(self, g, out):
+        """save_game into a C-contiguous uint8 array of at least save_size(g) bytes (no copy on the way) -> bytes written"""
+        out = _native.check_c(out, np.uint8)
+        return self._ck(self.L.apzh_game_save(self._h, int(g), out.ctypes.data, out.size))
+
+    def load_game(self, g, blob):
+        """Slot g := the game of a save_game blob.  The blob is checked as a whole first: one that does not fit this pool
+        or is damaged raises TreePoolError and leaves the slot as it was."""
+        buf = blob if isinstance(blob, np.ndarray) else np.frombuffer(bytes(blob), dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        self._ck(self.L.apzh_game_load(self._h, int(g), buf.ctypes.data if len(buf) else None, len(buf)))
+
     def arena_bytes(self):
         return self.pool_info()["arena_bytes"]
 

@@ -141,6 +141,22 @@ int apzh_stats(apzh_pool *p, int g, int64_t *out4);
  * reference allocates one Python object per node, mcts_alphaZero.py:34-41, and has nothing to report.) */
 int apzh_pool_info(apzh_pool *p, int64_t *out4);
 
+/* ---- checkpoint of one game slot ----------------------------------------------------------------------------- */
+/* (Build-side addition: the reference keeps its tree as Python objects, mcts_alphaZero.py:19-88, and has no way to
+ * carry a search from one process to the next.)  A blob holds everything a later advance / feed / play_moves of the
+ * slot reads: a header (magic, format version, width, height, n_in_row, n_playout, prior_is_f32), the board (cells,
+ * ply of every stone, move / mover history, player to move, last move), the LIVE tree arena (its eight arrays up to
+ * its size; the other arena is empty between calls), the playout count, the pending leaf with its path and player,
+ * and the counters.  Blobs are for the machine that wrote them (native byte order).
+ * save_size -> bytes; save -> bytes written (cap must be at least save_size).
+ * load checks the whole blob before it writes anything: the header against the pool, the length against the counts
+ * inside, every parent / first_child index and first_child + n_child against the arena size, every action and path
+ * entry against the board.  A blob that fails returns a negative code and leaves the slot as it was.  The arena keeps
+ * its reserved capacity (the pre-touch of pool creation is not undone). */
+int64_t apzh_game_save_size(apzh_pool *p, int g);
+int64_t apzh_game_save(apzh_pool *p, int g, void *buf, int64_t cap);
+int apzh_game_load(apzh_pool *p, int g, const void *buf, int64_t len);
+
 /* ---- pure-MCTS move (mcts_pure.py) ------------------------------------------------------ */
 /* Runs n_playout rollout playouts from a fresh root on game g's position, drawing
  * np.random.rand() values from the MT19937 state (key[624], pos) -- the same legacy stream

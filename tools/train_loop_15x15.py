@@ -4,7 +4,8 @@
 with 1000 playouts) on ONE MI355X, asynchronous schedule (alphapig_amd/pipeline.py): 1024 concurrent self-play games
 step on while the trainer thread updates; every published version is installed device to device.
 Prints one JSON line per reporting window (profiles/r04_train_loop_15x15.log); --lock-step runs round 3's loop;
---max-update-share caps the share of the wall clock the trainer may be busy."""
+--max-update-share caps the share of the wall clock the trainer may be busy; --checkpoint-every / --checkpoint-dir / --resume
+write checkpoints and continue from one (the final line lists what every written part cost)."""
 import argparse
 import json
 import os
@@ -60,6 +61,11 @@ def main():
                     help="the self-play evaluator's static activation exponents (TrainPipeline act_scale)")
     ap.add_argument("--replay", default="tuples", choices=("tuples", "compact", "device"),
                     help="what the replay buffer stores (TrainPipeline replay): augmented tuples, codes on the host, codes on the GPU")
+    ap.add_argument("--checkpoint-every", type=int, default=0, help="game batches between two checkpoints (0: none)")
+    ap.add_argument("--checkpoint-dir", default=None, help="where they go (default: <model_dir>/checkpoints)")
+    ap.add_argument("--checkpoint-selfplay", default="games", choices=("games", "none"),
+                    help="save the games in flight with their trees, or abandon them")
+    ap.add_argument("--resume", default=None, help="a checkpoint directory, or 'latest' for the newest complete one in --checkpoint-dir")
     args = ap.parse_args()
     conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
                 n_playout=400, c_puct=5, buffer_size=2198800, batch_size=128, epochs=8, kl_targ=0.02,
@@ -67,8 +73,14 @@ def main():
                 play_batch_size=1, concurrent_games=1024, n_blocks=10, n_filter=128, eval_games=args.eval_games,
                 model_dir="/tmp/apz_models_15", async_update=not args.lock_step, round_seconds=0.25,
                 max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith,
-                act_scale=args.act_scale, replay=args.replay)
-    tp = TrainPipeline(conf, seed=1)
+                act_scale=args.act_scale, replay=args.replay, checkpoint_every=args.checkpoint_every,
+                checkpoint_dir=args.checkpoint_dir, checkpoint_selfplay=args.checkpoint_selfplay)
+    resume = args.resume
+    if resume == "latest":
+        from alphapig_amd import checkpoint
+        done = checkpoint.complete_checkpoints(args.checkpoint_dir or os.path.join(conf["model_dir"], "checkpoints"))
+        resume = done[-1] if done else None
+    tp = TrainPipeline(conf, seed=1, resume=resume)
     host = _time_trainer_thread(tp)
     t0 = time.time()
     if args.lock_step:
@@ -124,6 +136,8 @@ def main():
                       "policy_update_ms_whole_run": round(1e3 * sum(b - a for a, b in tp.update_intervals) /
                                                           max(1, len(tp.update_intervals)), 1),
                       "trunk_overflows": getattr(getattr(tp, "_async_trainer", None), "trunk_overflows", None),
+                      "checkpoint_parts": [{"part": p, "seconds": round(t, 3), "bytes": b} for p, t, b in tp.checkpoint_log],
+                      "tree_peak_nodes": tp.engine.pool.pool_info()["peak_nodes"],
                       "act_scale": tp.act_scale, "eval_trunk_overflows": tp.policy_value_net.trunk_overflows(),
                       "act_exponents": tp.policy_value_net.trunk_act_exponents() if tp.act_scale == "auto" else None}),
           flush=True)
