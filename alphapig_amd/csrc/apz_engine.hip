@@ -1304,6 +1304,7 @@ int apz_load_weights(apz_engine* e, const char* const* names, const float* const
                     for (int b = 0; b < 3; b++) t[b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
                     return t[0] * G[k][0] + t[1] * G[k][1] + t[2] * G[k][2];
                 };
+                static_assert(apz::Wino3H16::UPK_BYTES == apz::Wino3H::UPK_BYTES, "both f16x2 kernels share the layer's upk3h buffer");
                 if (e->f16x2_k8) apz::wino3h_pack_host<apz::Wino3H>(u_of, uh, b3.data() + 128);
                 else apz::wino3h_pack_host<apz::Wino3H16>(u_of, uh, b3.data() + 128);
                 if (!L.upk3h) HIP_TRY(hipMalloc(&L.upk3h, apz::Wino3H::UPK_BYTES));

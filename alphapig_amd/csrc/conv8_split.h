@@ -1,6 +1,6 @@
 // 8x8 boards: 3x3 convolution + folded BatchNorm (+ residual) + ReLU on the FP16 matrix pipe at fp32-level accuracy -- every
 // fp32 operand as two fp16 terms (x = hi + lo, both rounded to nearest even), fp32 accumulation; the 8x8 sibling of
-// trunk15_wino3h.h (read its header for the arithmetic, the error bound and the overflow word).  gfx950 only.  Round 6.
+// trunk15_wino3h.h (read its header for the arithmetic, the error bound and the overflow word; the shared code: wino_f16x2.h).  gfx950 only.  Round 6.
 // Reference layers: policy_value_net_mxnet_simple.py:68-92 (the 6-conv net of BASELINE configs[1]), the 8x8 residual nets.
 //
 // Why: at 32 boards the layers with >= 64 input channels are bound by the fp32 matrix pipe (256 -> 256: 26 us at 0.59 of
@@ -24,12 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <vector>
-
-#include "trunk15_wino3h.h"
+#include "wino_f16x2.h"
 
 namespace apz {
 
@@ -61,20 +56,13 @@ inline void conv8h_pack_host(const float* w, const double* scale, const double* 
     for (int co = 0; co < cout; co++) {
         double m = 0;
         for (int i = 0; i < cin * 9; i++) m = std::max(m, std::fabs((double)w[(size_t)co * cin * 9 + i] * scale[co]));
-        const float S = Wino3H::scale_for(m);
+        const float S = f16x2_scale_for(m);
         bias8h[co] = (float)shift[co];
         bias8h[cout + co] = 1.f / S;
         for (int ci = 0; ci < cin; ci++)
-            for (int tap = 0; tap < 9; tap++) {
-                const double x = (double)w[((size_t)co * cin + ci) * 9 + tap] * scale[co] * (double)S;
-                const _Float16 hi = (_Float16)(float)x;
-                const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
-                uint16_t hb, lb;
-                std::memcpy(&hb, &hi, 2);
-                std::memcpy(&lb, &lo, 2);
-                out[Conv8H::pk_index(co, ci, tap, 0, cin)] = hb;
-                out[Conv8H::pk_index(co, ci, tap, 1, cin)] = lb;
-            }
+            for (int tap = 0; tap < 9; tap++)
+                f16x2_split((double)w[((size_t)co * cin + ci) * 9 + tap] * scale[co] * (double)S,
+                            out[Conv8H::pk_index(co, ci, tap, 0, cin)], out[Conv8H::pk_index(co, ci, tap, 1, cin)]);
     }
 }
 
@@ -95,20 +83,16 @@ __global__ void pack_conv8h_kernel(const float* __restrict__ w, const double* __
         if (tid < s && tid + s < (int)blockDim.x) red[tid] = fmax(red[tid], red[tid + s]);
         __syncthreads();
     }
-    const float S = Wino3H::scale_for(red[0]);
+    const float S = f16x2_scale_for(red[0]);
     if (tid == 0) {
         bias8h[co] = (float)shift[co];
         bias8h[cout + co] = 1.f / S;
     }
     for (int ci = tid; ci < cin; ci += blockDim.x)
 #pragma unroll
-        for (int tap = 0; tap < 9; tap++) {
-            const double x = (double)w[((size_t)co * cin + ci) * 9 + tap] * sc * (double)S;
-            const _Float16 hi = (_Float16)(float)x;
-            const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
-            pk[Conv8H::pk_index(co, ci, tap, 0, cin)] = __builtin_bit_cast(unsigned short, hi);
-            pk[Conv8H::pk_index(co, ci, tap, 1, cin)] = __builtin_bit_cast(unsigned short, lo);
-        }
+        for (int tap = 0; tap < 9; tap++)
+            f16x2_split((double)w[((size_t)co * cin + ci) * 9 + tap] * sc * (double)S, pk[Conv8H::pk_index(co, ci, tap, 0, cin)],
+                        pk[Conv8H::pk_index(co, ci, tap, 1, cin)]);
 }
 
 // in: dense [n][cin][64] floats; out / resid: dense [n][cout][64]; pk: Conv8H layout; bias8h: [cout bias][cout 1/S].
@@ -153,16 +137,11 @@ __global__ __launch_bounds__(256) void conv8h_kernel(const float* __restrict__ i
             for (int u = 0; u < 16; u++) pre[u] = p[(size_t)u * T::HW];
         };
         auto stash = [&]() {                        // split and store: the pixel's 16 channels, hi cell and lo cell
-            typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
             u32x4 h[2], l[2];
 #pragma unroll
             for (int m = 0; m < 8; m++) {
-                const float a = pre[2 * m], c = pre[2 * m + 1];
-                const f16x2_ h2 = {(_Float16)a, (_Float16)c};
-                const unsigned hu = __builtin_bit_cast(unsigned, h2);
-                unsigned lu;
-                asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(a));
-                asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(c));
+                unsigned hu, lu;
+                f16x2_split(pre[2 * m], pre[2 * m + 1], hu, lu);
                 h[m >> 2][m & 3] = hu;
                 l[m >> 2][m & 3] = lu;
             }

@@ -43,8 +43,6 @@
 
 namespace apz {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct Wino3 {
     static constexpr int C = 128, CK = 8, NCHUNK = C / CK;            // 16 iterations per item
     static constexpr int GPLANE = 240;                 // floats per plane in HBM (15 rows x 16)
@@ -103,17 +101,6 @@ __device__ unsigned long long apz_wino3_stamps[4 * 8 * 8];
 // step has no statistics pass over the tensor this kernel has just written.  A board's 225 values: a fixed fp32 tree (the
 // lane's 4x4 patch row by row, its four rows, then the sixteen lanes of the tile group by DPP adds -- in double the same
 // chain cost 7.7 us per 512-board launch, more than half of the pass it replaces); boards are added in double by the consumer.
-template <int CTRL>
-__device__ __forceinline__ float wino3_dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wino3_row16_sum(float v) {
-    v = wino3_dpp_add<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-    v = wino3_dpp_add<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-    v = wino3_dpp_add<0x141>(v);      // row_half_mirror: the other quad of the 8
-    return wino3_dpp_add<0x140>(v);   // row_mirror: the other 8 of the 16
-}
-
 template <bool RESID, bool RELU = true, bool QUARTER = false, bool STATS = false>
 __global__ __launch_bounds__(512) void trunk15_wino3_kernel(const float* __restrict__ in, const float* __restrict__ upk,
                                                             const float* __restrict__ bias,
@@ -169,31 +156,15 @@ __global__ __launch_bounds__(512) void trunk15_wino3_kernel(const float* __restr
     auto item_pair = [&](int t) { return pair0 + (duo ? t : (QUARTER ? (t >> 2) : (t >> 1))) * pstride; };
     auto item_half = [&](int t) { return duo ? h_fix : (QUARTER ? (t & 3) : (t & 1)); };   // channel half (QUARTER: quarter)
 
-    // All global memory traffic goes through raw buffer instructions: descriptor (SGPRs) + per-lane 32-bit offset
-    // + wave-uniform SGPR offset.  No 64-bit per-lane addresses (registers, VALU), and lanes that must not take
-    // part (60..63 of a 960-byte plane) get an offset beyond the buffer: their loads return 0, their stores are dropped.
+    // All global memory traffic goes through raw buffer instructions (wino_common.h)
     const unsigned plane_b = T::GPLANE * 4;                    // 960
-    const unsigned act_bytes = (unsigned)n * T::C * plane_b;   // launchers keep this below 2^31
-    const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_res =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RESID ? resid : in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
+    const unsigned act_bytes = rows16_bytes(n);
+    const __amdgpu_buffer_rsrc_t r_in = wino_rsrc(in, act_bytes), r_res = wino_rsrc(RESID ? resid : in, act_bytes);
+    const __amdgpu_buffer_rsrc_t r_out = wino_rsrc(out, act_bytes);
     static_assert(!STATS || (!RESID && !RELU), "STATS: the training forward (bias only)");
-    const __amdgpu_buffer_rsrc_t r_st =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(STATS ? resid : in), 0, STATS ? (unsigned)n * T::C * 16u : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, T::C * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_u =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(upk), 0, (unsigned)(WinoPack::UPK_FLOATS * 4), 0x00020000);
-    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    // Stores keep soffset = 0 and add the uniform part into the per-lane offset.  With an SGPR soffset hipcc (ROCm 7.2)
-    // emits no wait state between a 128-bit buffer store and a VALU write of its data registers (LLVM's hazard
-    // recognizer exempts that form), and on gfx950 the store then picks up the NEW value of the last dword in some
-    // lanes (found the hard way: one element per 4x4 tile of every 16th channel wrong, and only in some builds).
-    auto bstore = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, const f32x4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, 0);
-    };
+    const __amdgpu_buffer_rsrc_t r_st = wino_rsrc(STATS ? resid : in, STATS ? (unsigned)n * T::C * 16u : 0u);
+    const __amdgpu_buffer_rsrc_t r_bias = wino_rsrc(bias, T::C * 4);
+    const __amdgpu_buffer_rsrc_t r_u = wino_rsrc(upk, (unsigned)(WinoPack::UPK_FLOATS * 4));
 
     // ---- staging roles: 2 boards x 8 planes x 60 pieces of 16 B; 32 threads per plane, two pieces each (four of them
     // twice).  thread -> plane tid>>5: board = tid>>8 (wave-uniform: waves 0..3 stage board 0), channel (tid>>5)&7.

@@ -147,31 +147,14 @@ __global__ __launch_bounds__(512) void trunk15_wino3b_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- work items: as trunk15_wino3_kernel (duo mode: blocks b and b + 8 take the two channel halves of the same pairs)
-    const int npairs = (n + 1) >> 1, G_ = (int)gridDim.x, b_ = (int)blockIdx.x;
-    const bool duo = (G_ & 15) == 0;
-    const int pair0 = duo ? ((b_ >> 4) * 8 + (b_ & 7)) : b_;
-    const int pstride = duo ? (G_ >> 1) : G_;
-    const int h_fix = (b_ >> 3) & 1;
-    const int np = pair0 < npairs ? (npairs - pair0 + pstride - 1) / pstride : 0;
-    const int nitems = duo ? np : 2 * np;
-    if (np == 0) return;
-    auto item_pair = [&](int t) { return pair0 + (duo ? t : (t >> 1)) * pstride; };
-    auto item_half = [&](int t) { return duo ? h_fix : (t & 1); };
+    const WinoItems items(n, (int)gridDim.x, (int)blockIdx.x);   // (board pair, channel half) per item
+    const int nitems = items.nitems;
+    if (items.np == 0) return;
 
     const unsigned plane_b = T::GPLANE * 4;
-    const unsigned act_bytes = (unsigned)n * T::C * plane_b;
-    const __amdgpu_buffer_rsrc_t r_res =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RESID ? resid : in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_u =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)T::UPK_BYTES, 0x00020000);
-    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto bstore = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, const f32x4 v) {   // soffset = 0: see trunk15_wino3.h
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, 0);
-    };
+    const unsigned act_bytes = rows16_bytes(n);
+    const __amdgpu_buffer_rsrc_t r_res = wino_rsrc(RESID ? resid : in, act_bytes), r_out = wino_rsrc(out, act_bytes);
+    const __amdgpu_buffer_rsrc_t r_u = wino_rsrc(upk, (unsigned)T::UPK_BYTES);
 
     // ---- staging role: wave w brings planes w (board 0) and w + 8 (board 1) of a chunk into LDS by LDS-DMA
     // (buffer_load_dwordx4 ... lds): one instruction per plane, lane l copies 16 bytes to LDS byte m0 + 16 l (lanes 60..63
@@ -187,7 +170,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3b_kernel(const float* __rest
     const unsigned dma_vo = lane < 60 ? lane * 16 : 0x80000000u;   // lanes 60..63: out of range (row 15 of the tile stays zero)
     auto raw_dma = [&](int t, int c, int par) {       // chunk c (clamped) of item t -> raw[par]
         c = c < T::NCHUNK ? c : T::NCHUNK - 1;
-        const int bd0_ = 2 * item_pair(t);
+        const int bd0_ = 2 * items.pair(t);
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int plane = 8 * j + wave;           // board j, channel `wave`
@@ -215,7 +198,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3b_kernel(const float* __rest
         if (p9 >= 9) { p9 -= 9; c += 1; }
         if (c >= T::NCHUNK) { c -= T::NCHUNK; t += 1; }
         if (t >= nitems) { t = nitems - 1; c = T::NCHUNK - 1; p9 = 8; }
-        const int cog = 2 * item_half(t) + cc;
+        const int cog = 2 * items.half(t) + cc;
         const unsigned so = (unsigned)(((cog * 4 + blk) * T::NCHUNK + c) * 9 + p9) * T::UNIT;
         af[slot][0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r_u, a_vo0, so, 0));
         af[slot][1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r_u, a_vo1, so, 0));
@@ -342,8 +325,8 @@ __global__ __launch_bounds__(512) void trunk15_wino3b_kernel(const float* __rest
         raw_dma(0, 1, 1);
 
         for (int t = 0; t < nitems; t++) {
-            const int h = item_half(t);
-            const int bd0 = 2 * item_pair(t);
+            const int h = items.half(t);
+            const int bd0 = 2 * items.pair(t);
             const bool two = bd0 + 1 < n;
             // ---- item prologue: raw(0), raw(1) have been requested; V[0] = transform(raw(0))
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -486,17 +469,13 @@ __global__ __launch_bounds__(512) void trunk15_wino3b_kernel(const float* __rest
                         float m[6];
 #pragma unroll
                         for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 512];
-                        const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-                        hrow[i][0] = (m[0] + s12) + s34;
-                        hrow[i][1] = __builtin_fmaf(2.f, d34, d12);
-                        hrow[i][2] = __builtin_fmaf(4.f, s34, s12);
-                        hrow[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+                        wino_out_row(m[0], m[1], m[2], m[3], m[4], m[5], hrow[i][0], hrow[i][1], hrow[i][2], hrow[i][3]);
                     }
                     const float bv = bias[co_base + co16];
                     float* sp = sw + (cosel * 2 + gbd) * T::SPLANE + (4 * gty) * T::SROW + 4 * gtx;
                     f32x4 y[4];
 #pragma unroll
-                    for (int ee = 0; ee < 4; ee++) {
+                    for (int ee = 0; ee < 4; ee++) {   // wino_out_row down the columns, restated: the call changes this kernel's code
                         const float s12 = hrow[1][ee] + hrow[2][ee], d12 = hrow[1][ee] - hrow[2][ee];
                         const float s34 = hrow[3][ee] + hrow[4][ee], d34 = hrow[3][ee] - hrow[4][ee];
                         y[0][ee] = (hrow[0][ee] + s12) + s34;

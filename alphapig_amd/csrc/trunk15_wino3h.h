@@ -8,7 +8,7 @@
 //
 // Range.  fp16 holds 6.1e-5 .. 65504 in normal numbers, so both operands are placed by powers of two:
 //   * weights: U = G g G^T of output channel co is multiplied by S[co] = 2^k chosen on the host / by the device packer
-//     so that max |U S| sits in [2^13, 2^14); the epilogue multiplies by 1 / S[co] (exact) inside the bias FMA.
+//     (f16x2_scale_for) so that max |U S| sits in [2^13, 2^14); the epilogue multiplies by 1 / S[co] (exact) inside the bias FMA.
 //   * activations: V = B^T d B is NOT scaled.  |V| <= 100 max|d|: post-ReLU activations up to 655 are representable;
 //     values below 2^-3 keep an absolute error of 2^-25.  An input that does overflow gives +-inf / NaN in the
 //     accumulators; the epilogue checks every pre-ReLU value (a NaN would otherwise be clamped to 0 silently) and raises
@@ -33,18 +33,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdint>
-#include <cstring>
 #include <type_traits>
-#include <vector>
 
-#include "trunk15_wino3.h"
+#include "wino_f16x2.h"
 
 namespace apz {
-
-typedef float f32x16h __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Wino3H {
     static constexpr int C = 128, CK = 8, NCHUNK = C / CK;             // 16 chunks of 8 input channels
@@ -71,42 +64,7 @@ struct Wino3H {
         const int ch = ci & 7;
         return ((((size_t)(cog * 4 + w) * NCHUNK + chunk) * 9 + p9) * 2 + term) * VTERM + r * 16 + ch * 2;
     }
-    // the power of two that puts m = max |U| of an output channel into [2^13, 2^14) (m == 0: 1)
-    __host__ __device__ static float scale_for(double m) {
-        if (!(m > 0.0)) return 1.f;
-        int e;
-        frexp(m, &e);                                                  // m = f 2^e, f in [0.5, 1)
-        int k = 14 - e;
-        k = k < -100 ? -100 : (k > 100 ? 100 : k);
-        return (float)ldexp(1.0, k);
-    }
 };
-
-// Host packing: U[pos][co][ci] (double) -> the kernel's fp16 x 2 layout + the per-channel inverse scales.
-// `u_of(co, ci, pos)` returns the value.  inv_scale: 128 floats (goes behind the 128 biases).  L: the layout (Wino3H, or
-// Wino3H16 of trunk15_wino3h16.h: the same terms and scales, another order).
-template <class L = Wino3H, class F>
-inline void wino3h_pack_host(F u_of, std::vector<uint16_t>& out, float* inv_scale) {
-    out.assign(L::UPK_BYTES / 2, 0);
-    for (int co = 0; co < 128; co++) {
-        double m = 0;
-        for (int ci = 0; ci < 128; ci++)
-            for (int pos = 0; pos < 36; pos++) m = std::max(m, std::fabs((double)u_of(co, ci, pos)));
-        const float S = Wino3H::scale_for(m);
-        inv_scale[co] = 1.f / S;
-        for (int ci = 0; ci < 128; ci++)
-            for (int pos = 0; pos < 36; pos++) {
-                const double x = (double)u_of(co, ci, pos) * (double)S;
-                const _Float16 hi = (_Float16)(float)x;
-                const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
-                uint16_t hb, lb;
-                std::memcpy(&hb, &hi, 2);
-                std::memcpy(&lb, &lo, 2);
-                out[L::upk_offset(co, ci, pos, 0) / 2] = hb;
-                out[L::upk_offset(co, ci, pos, 1) / 2] = lb;
-            }
-    }
-}
 
 #ifdef APZ_WINO3H_STAMPS
 __device__ unsigned long long apz_wino3h_stamps[4 * 8 * 12];   // [workgroup 4][wave 8][phase 12]
@@ -147,31 +105,14 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- work items: as trunk15_wino3_kernel (duo mode: blocks b and b + 8 take the two channel halves of the same pairs)
-    const int npairs = (n + 1) >> 1, G_ = (int)gridDim.x, b_ = (int)blockIdx.x;
-    const bool duo = (G_ & 15) == 0;
-    const int pair0 = duo ? ((b_ >> 4) * 8 + (b_ & 7)) : b_;
-    const int pstride = duo ? (G_ >> 1) : G_;
-    const int h_fix = (b_ >> 3) & 1;
-    const int np = pair0 < npairs ? (npairs - pair0 + pstride - 1) / pstride : 0;
-    const int nitems = duo ? np : 2 * np;
-    if (np == 0) return;
-    auto item_pair = [&](int t) { return pair0 + (duo ? t : (t >> 1)) * pstride; };
-    auto item_half = [&](int t) { return duo ? h_fix : (t & 1); };
+    const WinoItems items(n, (int)gridDim.x, (int)blockIdx.x);   // (board pair, channel half) per item
+    const int nitems = items.nitems;
+    if (items.np == 0) return;
 
     const unsigned plane_b = T::GPLANE * 4;
-    const unsigned act_bytes = (unsigned)n * T::C * plane_b;
-    const __amdgpu_buffer_rsrc_t r_res =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RESID ? resid : in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_u =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)T::UPK_BYTES, 0x00020000);
-    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto bstore = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, const f32x4 v) {   // soffset = 0: see trunk15_wino3.h
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, 0);
-    };
+    const unsigned act_bytes = rows16_bytes(n);
+    const __amdgpu_buffer_rsrc_t r_res = wino_rsrc(RESID ? resid : in, act_bytes), r_out = wino_rsrc(out, act_bytes);
+    const __amdgpu_buffer_rsrc_t r_u = wino_rsrc(upk, (unsigned)T::UPK_BYTES);
 
     // ---- staging role: wave w brings planes w (board 0) and w + 8 (board 1) of a chunk into LDS by LDS-DMA
     // (buffer_load_dwordx4 ... lds; lanes 60..63 out of range: row 15 of the tile stays zero).  Inline assembly: hipcc's
@@ -185,7 +126,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
     const unsigned dma_vo = lane < 60 ? lane * 16 : 0x80000000u;
     auto raw_dma = [&](int t, int c, int par) {       // chunk c (clamped) of item t -> raw[par]
         c = c < T::NCHUNK ? c : T::NCHUNK - 1;
-        const int bd0_ = 2 * item_pair(t);
+        const int bd0_ = 2 * items.pair(t);
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int plane = 8 * j + wave;           // board j, channel `wave`
@@ -214,7 +155,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
     // instead of five per load.  Behind the last chunk of the last item the "next" base just runs on (unused data; the buffer
     // descriptor bounds it).
     auto unit_base = [&](int t, int c) {
-        const int cog = 2 * item_half(t) + cc;
+        const int cog = 2 * items.half(t) + cc;
         return (unsigned)(((cog * 4 + blk) * T::NCHUNK + c) * 9) * T::UNIT;
     };
     unsigned ub_cur = 0, ub_nxt = 0;                  // bases of the chunk being multiplied and of the one after it
@@ -352,22 +293,17 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
             asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5"
                 : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]));
         };
-        // (even channel's value, odd channel's value) of one position -> two dwords of fp16 pairs: hi = both values rounded
-        // to fp16, lo = the remainders (exact in fp32: v_fma_mix) rounded to fp16
+        // (even channel's value, odd channel's value) of one position -> its hi and lo words in V
         auto emit = [&](char* vp, float ev, float od) {
-            typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
-            const f16x2_ h2 = {(_Float16)ev, (_Float16)od};                  // v_cvt_pk_f16_f32
-            const unsigned hu = __builtin_bit_cast(unsigned, h2);
-            unsigned lu;
-            asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(ev));
-            asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(od));
+            unsigned hu, lu;
+            f16x2_split(ev, od, hu, lu);
             *reinterpret_cast<unsigned*>(vp) = hu;
             *reinterpret_cast<unsigned*>(vp + T::VTERM) = lu;
         };
 #ifndef APZH_EMIT2
 #define APZH_EMIT2 0
 #endif
-        // two positions at once: the two v_fma_mixlo / v_fma_mixhi pairs interleaved, so that no wait state is needed between a
+        // (APZH_EMIT2) two positions at once: f16x2_split's two v_fma_mixlo / v_fma_mixhi pairs interleaved in ONE asm statement, so that no wait state is needed between a
         // register's low-half write and its high-half write
         auto emit2 = [&](char* vp0, float ev0, float od0, char* vp1, float ev1, float od1) {
             typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
@@ -425,8 +361,8 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
         raw_dma(0, 1, 1);
 
         for (int t = 0; t < nitems; t++) {
-            const int h = item_half(t);
-            const int bd0 = 2 * item_pair(t);
+            const int h = items.half(t);
+            const int bd0 = 2 * items.pair(t);
             const bool two = bd0 + 1 < n;
             // ---- item prologue: raw(0), raw(1) have been requested; V[0] = transform(raw(0))
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -646,11 +582,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
                         float m[6];
 #pragma unroll
                         for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 512];
-                        const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-                        hrow[i][0] = (m[0] + s12) + s34;
-                        hrow[i][1] = __builtin_fmaf(2.f, d34, d12);
-                        hrow[i][2] = __builtin_fmaf(4.f, s34, s12);
-                        hrow[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+                        wino_out_row(m[0], m[1], m[2], m[3], m[4], m[5], hrow[i][0], hrow[i][1], hrow[i][2], hrow[i][3]);
                     }
                     // the next step's residual planes: behind the gather (their registers are free now), in front of this
                     // step's stores (vmcnt counts in issue order: the wait for them must not include those stores)
@@ -662,12 +594,9 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
                     f32x4 y[4];
 #pragma unroll
                     for (int ee = 0; ee < 4; ee++) {
-                        const float s12 = hrow[1][ee] + hrow[2][ee], d12 = hrow[1][ee] - hrow[2][ee];
-                        const float s34 = hrow[3][ee] + hrow[4][ee], d34 = hrow[3][ee] - hrow[4][ee];
-                        y[0][ee] = (hrow[0][ee] + s12) + s34;
-                        y[1][ee] = __builtin_fmaf(2.f, d34, d12);
-                        y[2][ee] = __builtin_fmaf(4.f, s34, s12);
-                        y[3][ee] = __builtin_fmaf(8.f, d34, d12) + hrow[5][ee];
+                        float o0, o1, o2, o3;
+                        wino_out_row(hrow[0][ee], hrow[1][ee], hrow[2][ee], hrow[3][ee], hrow[4][ee], hrow[5][ee], o0, o1, o2, o3);
+                        y[0][ee] = o0, y[1][ee] = o1, y[2][ee] = o2, y[3][ee] = o3;
                     }
 #ifndef APZH_CHK4
 #define APZH_CHK4 0      /* 1: the non-finite check on the four corner outputs of a tile only (see below) instead of all sixteen: 13 vector
@@ -685,13 +614,13 @@ __global__ __launch_bounds__(512) void trunk15_wino3h_kernel(const float* __rest
 #pragma unroll
                         for (int ee = 0; ee < 4; ee++) v[ee] = __builtin_fmaf(y[a][ee], is, bv);
                         if (RESID) v += *reinterpret_cast<const f32x4*>(sp + a * T::SROW);   // (wave-private: written above by this wave)
-                        if (!APZH_CHK4) chk += (v[0] + v[1]) + (v[2] + v[3]);   // an overflow of the fp16 split shows as +-inf / NaN here
+                        if (!APZH_CHK4) chk += wino_sum4(v);
 #pragma unroll
                         for (int ee = 0; ee < 4; ee++) v[ee] = RELU ? fmaxf(v[ee], 0.f) : v[ee];
                         if (gtx == 3) v[3] = 0.f;      // column 15 is the halo column of the rows16 layout
                         *reinterpret_cast<f32x4*>(sp + a * T::SROW) = v;   // (same lane, same addresses as the residual it read)
                     }
-                    nonfinite |= ((chk - chk) != 0.f) ? 1u : 0u;         // 0 for every finite sum; NaN != 0 is true
+                    nonfinite |= wino_nonfinite(chk) ? 1u : 0u;
                 }
                 APZH_STAMP(9)
                 wave_lds_fence();

@@ -3,7 +3,8 @@
 //
 // What stays: the arithmetic (x = hi + lo, two fp16 terms, weights times S[co] = 2^k, 1 / S[co] in the bias FMA, activations
 // unscaled, the overflow word), the work item (board pair x 64 output channels x 36 positions), the grid and duo scheme, eight
-// waves = (32-channel half, 3x3 position block) with 144 accumulators each, and the epilogue, line for line.
+// waves = (32-channel half, 3x3 position block) with 144 accumulators each, and the epilogue (its arithmetic is the shared
+// wino_out_row, wino_sum4 and wino_nonfinite of wino_common.h in both kernels).
 //
 // What changes -- the K packing.  trunk15_wino3h.h contracts k = 16 as 8 channels x the two WEIGHT terms (A = [Whi | Wlo],
 // B = [Vt | Vt]): four products per 8 channels, lo.lo included, and both lane halves of a B fragment read the same 16 bytes.
@@ -33,7 +34,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "trunk15_wino3h.h"
+#include "wino_f16x2.h"
 
 namespace apz {
 
@@ -51,14 +52,12 @@ struct Wino3H16 {
     static constexpr int LDS_BYTES = 2 * V_BYTES;                      // 147456
     static_assert((MQ_FLOATS + STG_FLOATS) * 4 <= LDS_BYTES, "the epilogue area fits over V");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    static_assert(UPK_BYTES == Wino3H::UPK_BYTES, "same weight buffer as trunk15_wino3h.h");
     // byte offset of element (co, ci, pos, term) in the packed weights
     __host__ __device__ static size_t upk_offset(int co, int ci, int pos, int term) {
         const int i = pos / 6, k = pos % 6, ri = i / 3, ki = k / 3, p9 = 3 * (i % 3) + (k % 3);
         const int cog = co >> 5, r = co & 31, chunk = ci >> 4, half = (ci >> 3) & 1, w = 2 * ri + ki;
         return ((((size_t)(cog * 4 + w) * NCHUNK + chunk) * 9 + p9) * 2 + term) * UNIT + half * 512 + r * 16 + (ci & 7) * 2;
     }
-    static float scale_for(double m) { return Wino3H::scale_for(m); }
 };
 
 #ifdef APZ_WINO3H_STAMPS
@@ -86,7 +85,7 @@ __device__ unsigned long long apz_wino3h16_stamps[4 * 8 * 12];   // [workgroup 4
 //                   the maximum into [2^7, 2^8) -- |V| <= 100 max <= 25 600 stays below the fp16 limit, and 22 binades
 //                   below the maximum are still normal fp16.  The raw tile values are multiplied by 2^a before the
 //                   transform, 2^-a goes into the 1 / S of the bias FMA.  2^a and 2^-a are normal floats for
-//                   -64 <= a <= 110; the product 2^-a / S = 2^-(a + k) (S = 2^k from Wino3H::scale_for, k about 18 for
+//                   -64 <= a <= 110; the product 2^-a / S = 2^-(a + k) (S = 2^k from f16x2_scale_for, k about 18 for
 //                   weights of this net, clamped to 100) is an fp32 subnormal from a + k = 127 on, and exact there only
 //                   because this library is built with fp32 denormals enabled (the compiler's default for gfx950;
 //                   no flush-to-zero flag in build.py) and while a + k <= 149.  A maximum of 1e-30 has a = 107: 2^-125
@@ -120,7 +119,7 @@ inline int act_exponent_for(float m) {
     return a < -ACT_EXP_MAX ? -ACT_EXP_MAX : (a > ACT_EXP_MAX ? ACT_EXP_MAX : a);
 }
 
-// a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as Wino3H::scale_for(0)); clamped to [-64, 110]: 2^110 and 2^-110 are
+// a with max |x| 2^a in [2^7, 2^8); 0 for max 0 (as f16x2_scale_for(0)); clamped to [-64, 110]: 2^110 and 2^-110 are
 // normal floats, and maxima down to 2^-103 (1e-31) still reach the window.  (A maximum of +inf -- the launch sets the
 // overflow word for it -- gives -64.)
 __device__ __forceinline__ int wino3h16_dgrad_exponent(float m) {
@@ -163,17 +162,9 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- work items: as trunk15_wino3h_kernel
-    const int npairs = (n + 1) >> 1, G_ = (int)gridDim.x, b_ = (int)blockIdx.x;
-    const bool duo = (G_ & 15) == 0;
-    const int pair0 = duo ? ((b_ >> 4) * 8 + (b_ & 7)) : b_;
-    const int pstride = duo ? (G_ >> 1) : G_;
-    const int h_fix = (b_ >> 3) & 1;
-    const int np = pair0 < npairs ? (npairs - pair0 + pstride - 1) / pstride : 0;
-    const int nitems = duo ? np : 2 * np;
-    if (np == 0) return;
-    auto item_pair = [&](int t) { return pair0 + (duo ? t : (t >> 1)) * pstride; };
-    auto item_half = [&](int t) { return duo ? h_fix : (t & 1); };
+    const WinoItems items(n, (int)gridDim.x, (int)blockIdx.x);   // (board pair, channel half) per item
+    const int nitems = items.nitems;
+    if (items.np == 0) return;
 
     // DGRAD: the input scale 2^a and 2^-a from the partial maxima (the eight wave maxima pass through V[0], which the first
     // item's transform writes only behind its barrier)
@@ -191,35 +182,18 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
         for (int w = 0; w < 8; w++) m = fmaxf(m, lds[w]);
         const int a = __builtin_amdgcn_readfirstlane(wino3h16_dgrad_exponent(m));
         aux_inf = !(m <= 3.4028234664e38f);
-        xsc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
-        xisc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
+        f16x2_pow2_pair(a, xsc, xisc);
     }
-    if constexpr (SCALED) {                           // the host's exponent: a kernel argument, the same in every wave
-        xsc = __builtin_bit_cast(float, (unsigned)(127 + aux_n) << 23);
-        xisc = __builtin_bit_cast(float, (unsigned)(127 - aux_n) << 23);
-    }
+    if constexpr (SCALED) f16x2_pow2_pair(aux_n, xsc, xisc);   // the host's exponent: a kernel argument, the same in every wave
 
     const unsigned plane_b = T::GPLANE * 4;
-    const unsigned act_bytes = (unsigned)n * T::C * plane_b;
-    const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_res =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RESID ? resid : in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_u =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)T::UPK_BYTES, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_st =
-        __builtin_amdgcn_make_buffer_rsrc(STATS ? aux : out, 0, STATS ? (unsigned)n * T::C * 16u : 0u, 0x00020000);
-    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto bstore = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff, const f32x4 v) {   // soffset = 0: see trunk15_wino3.h
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff + soff, 0, 0);
-    };
+    const unsigned act_bytes = rows16_bytes(n);
+    const __amdgpu_buffer_rsrc_t r_in = wino_rsrc(in, act_bytes), r_res = wino_rsrc(RESID ? resid : in, act_bytes);
+    const __amdgpu_buffer_rsrc_t r_out = wino_rsrc(out, act_bytes), r_u = wino_rsrc(upk, (unsigned)T::UPK_BYTES);
+    const __amdgpu_buffer_rsrc_t r_st = wino_rsrc(STATS ? aux : out, STATS ? (unsigned)n * T::C * 16u : 0u);
 
-    // ---- transform role: board tb, channels 4 cq .. 4 cq + 3 of the chunk.  lane -> (tile = bits 0-3: ttx = bits 0-1, tty =
-    // bits 2-3; channel pair cpl = bit 4; channel parity e = bit 5): a board's 16 tiles are one DPP row (halo rows: row_shr /
-    // row_shl by 4 lanes), the tile columns of a tile row are a quad (halo columns: quad_perm), the two channels of a pair sit
-    // 32 lanes apart (v_permlane32_swap_b32 exchanges them).
+    // ---- transform role: board tb, channels 4 cq .. 4 cq + 3 of the chunk; the lane roles (tile, channel pair cpl, channel
+    // parity e) and the transform's passes are wino_f16x2.h's.
     const int tb = wave & 1, cq = wave >> 1;
     const int ttx = lane & 3, tty = (lane >> 2) & 3, tile = lane & 15, cpl = (lane >> 4) & 1, e = lane >> 5;
     const int chl = 4 * cq + 2 * cpl + e;                          // channel of the chunk (0..15)
@@ -236,7 +210,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     const unsigned raw_vo3 = tty == 3 ? 0x80000000u : raw_vo + 3u * 64u;
     f32x4 raw[4];
     auto raw_load = [&](int t, int c) {                            // chunk c of item t -> raw
-        const int bdp = 2 * item_pair(t) + tb;
+        const int bdp = 2 * items.pair(t) + tb;
         const int bd = bdp < n ? bdp : n - 1;
         const unsigned so = (unsigned)(bd * T::C + c * T::CK + 4 * cq) * plane_b;
 #pragma unroll
@@ -246,59 +220,15 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
 
     f32x2 tt[6][2];                                // vertical-pass results: rows 0..5, column pairs (0, 1), (2, 3)
     float oo[6];
-    // B^T over the rows of the 6 x 6 patch (x0 = row -1 .. x5 = row 4), on column pairs
-    auto vpass = [&](int kc) {
-        f32x2 x[6];
-        // rows -1 and 4: row 3 of the tile above, row 0 of the tile below (zero beyond the board: bound_ctrl)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const float r3 = raw[3][2 * kc + j], r0 = raw[0][2 * kc + j];
-            x[0][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r3), 0x114, 0xF, 0xF, true));   // row_shr:4
-            x[5][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r0), 0x104, 0xF, 0xF, true));   // row_shl:4
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) x[r + 1] = f32x2{raw[r][2 * kc], raw[r][2 * kc + 1]};
-        const f32x2 a = fma2(-4.f, x[2], x[4]), b = fma2(-4.f, x[1], x[3]);
-        const f32x2 c = x[4] - x[2], d = x[3] - x[1];
-        tt[0][kc] = fma2(4.f, x[0], fma2(-5.f, x[2], x[4]));
-        tt[1][kc] = a + b;
-        tt[2][kc] = a - b;
-        tt[3][kc] = fma2(2.f, d, c);
-        tt[4][kc] = fma2(-2.f, d, c);
-        tt[5][kc] = fma2(4.f, x[1], fma2(-5.f, x[3], x[5]));
-    };
-    // B^T over the columns of row j: the halo columns (-1 and 4) are the quad neighbours' columns 3 and 0 of the same row
-    // (quad_perm [0,0,1,2] / [1,2,3,3]); v = (v1, v2), (v3, v4), (v0, v5) -> o[0..5]
-    auto col_pass = [&](int j) {
-        const float c3 = tt[j][1][1], c0 = tt[j][0][0];
-        const int l = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c3), 0x90, 0xF, 0xF, true);
-        const int r = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c0), 0xF9, 0xF, 0xF, true);
-        const float v0 = __builtin_bit_cast(float, l), v5 = __builtin_bit_cast(float, (unsigned)r & col16_mask);
-        const f32x2 ab = fma2(-4.f, tt[j][0], tt[j][1]);   // (b, a) = (v3 - 4 v1, v4 - 4 v2)
-        const f32x2 dc = tt[j][1] - tt[j][0];              // (d, c) = (v3 - v1, v4 - v2)
-        oo[0] = __builtin_fmaf(c4l, v0, __builtin_fmaf(-5.f, tt[j][0][1], tt[j][1][1]));
-        oo[3] = __builtin_fmaf(2.f, dc[0], dc[1]);
-        oo[1] = ab[1] + ab[0];
-        oo[4] = __builtin_fmaf(-2.f, dc[0], dc[1]);
-        oo[2] = ab[1] - ab[0];
-        oo[5] = __builtin_fmaf(4.f, tt[j][0][0], __builtin_fmaf(-5.f, tt[j][1][0], v5));
-    };
-    // lanes of the even channel keep o[0..2] and hand o[3..5] to their pair partner (32 lanes up), lanes of the odd channel
-    // the other way round: afterwards (o[k], o[k + 3]) = (even channel's value, odd channel's value) of position k in the even
-    // channel's lanes and of position k + 3 in the odd channel's.  (two wait states after a vector write of an operand)
-    auto exchange = [&]() {
-        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5"
-            : "+v"(oo[0]), "+v"(oo[1]), "+v"(oo[2]), "+v"(oo[3]), "+v"(oo[4]), "+v"(oo[5]));
-    };
-    // (even channel's value, odd channel's value) of one position -> hi = both rounded to fp16, lo = the exact remainders
-    // (v_fma_mix) rounded to fp16
+    // (one-line lambdas, not direct calls: the compiler then simplifies each before it inlines it, which keeps the kernel's
+    // instruction schedule)
+    auto vpass = [&](int kc) { f16x2_vpass(raw, kc, tt); };
+    auto col_pass = [&](int j) { f16x2_col_pass(tt, j, c4l, col16_mask, oo); };
+    auto exchange = [&]() { f16x2_exchange(oo); };
+    // (even channel's value, odd channel's value) of one position -> its hi and lo words in V
     auto emit = [&](char* vp, float ev, float od) {
-        typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
-        const f16x2_ h2 = {(_Float16)ev, (_Float16)od};                  // v_cvt_pk_f16_f32
-        const unsigned hu = __builtin_bit_cast(unsigned, h2);
-        unsigned lu;
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(ev));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(od));
+        unsigned hu, lu;
+        f16x2_split(ev, od, hu, lu);
         *reinterpret_cast<unsigned*>(vp) = hu;
         *reinterpret_cast<unsigned*>(vp + T::VTERM) = lu;
     };
@@ -344,7 +274,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     static_assert(18 % RING == 0 && RING >= 2, "ring slots must tile two chunks");
     f16x8 ah[RING], al[RING];
     auto unit_base = [&](int t, int c) {
-        const int cog = 2 * item_half(t) + cc;
+        const int cog = 2 * items.half(t) + cc;
         return (unsigned)(((cog * 4 + blk) * T::NCHUNK + c) * 18) * T::UNIT;
     };
     unsigned ub_cur = 0, ub_nxt = 0;
@@ -372,8 +302,8 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 
     for (int t = 0; t < nitems; t++) {
-        const int h = item_half(t);
-        const int bd0 = 2 * item_pair(t);
+        const int h = items.half(t);
+        const int bd0 = 2 * items.pair(t);
         const bool two = bd0 + 1 < n;
         // ---- item prologue: raw holds chunk 0 (requested in front of the loop / in the last epilogue step): V[0]
         __syncthreads();                              // the previous item's M / staging (over V) consumed
@@ -442,7 +372,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
         chunk(T::NCHUNK - 2, P0{}, Y{}, N{});         // transforms the last chunk; nothing left to load
         chunk(T::NCHUNK - 1, P1{}, N{}, N{});         // MFMAs only
 
-        // ---- epilogue: as trunk15_wino3h_kernel.  Four steps of 16 output channels = channels 8 s .. 8 s + 7 of BOTH 32-channel
+        // ---- epilogue.  Four steps of 16 output channels = channels 8 s .. 8 s + 7 of BOTH 32-channel
         // halves.  Layout of the 32 x 32 tile: lane (col = lane & 31, hh = lane >> 5), register v: channel (v & 3) + 8 (v >> 2) +
         // 4 hh.  M row (of 16) = 8 cc + channel - 8 s.
         const int cosel = lane >> 5;               // gather role: M row 2 wave + cosel of the step's 16, column lane & 31
@@ -491,11 +421,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                     float m[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 512];
-                    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-                    hrow[i][0] = (m[0] + s12) + s34;
-                    hrow[i][1] = __builtin_fmaf(2.f, d34, d12);
-                    hrow[i][2] = __builtin_fmaf(4.f, s34, s12);
-                    hrow[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+                    wino_out_row(m[0], m[1], m[2], m[3], m[4], m[5], hrow[i][0], hrow[i][1], hrow[i][2], hrow[i][3]);
                 }
                 if (RESID && s + 1 < 4) resid_request(s + 1);
                 const int ch = row_chan(s, co16);
@@ -505,12 +431,9 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                 f32x4 y[4];
 #pragma unroll
                 for (int ee = 0; ee < 4; ee++) {
-                    const float s12 = hrow[1][ee] + hrow[2][ee], d12 = hrow[1][ee] - hrow[2][ee];
-                    const float s34 = hrow[3][ee] + hrow[4][ee], d34 = hrow[3][ee] - hrow[4][ee];
-                    y[0][ee] = (hrow[0][ee] + s12) + s34;
-                    y[1][ee] = __builtin_fmaf(2.f, d34, d12);
-                    y[2][ee] = __builtin_fmaf(4.f, s34, s12);
-                    y[3][ee] = __builtin_fmaf(8.f, d34, d12) + hrow[5][ee];
+                    float o0, o1, o2, o3;
+                    wino_out_row(hrow[0][ee], hrow[1][ee], hrow[2][ee], hrow[3][ee], hrow[4][ee], hrow[5][ee], o0, o1, o2, o3);
+                    y[0][ee] = o0, y[1][ee] = o1, y[2][ee] = o2, y[3][ee] = o3;
                 }
                 float chk = 0.f;
                 float r1[4], r2[4];                  // STATS: the row sums of the tile
@@ -520,7 +443,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
 #pragma unroll
                     for (int ee = 0; ee < 4; ee++) v[ee] = __builtin_fmaf(y[a][ee], is, bv);
                     if (RESID) v += *reinterpret_cast<const f32x4*>(sp + a * T::SROW);   // (wave-private: written above by this wave)
-                    chk += (v[0] + v[1]) + (v[2] + v[3]);   // an overflow of the fp16 split shows as +-inf / NaN here
+                    chk += wino_sum4(v);
 #pragma unroll
                     for (int ee = 0; ee < 4; ee++) v[ee] = RELU ? fmaxf(v[ee], 0.f) : v[ee];
                     if (gtx == 3) v[3] = 0.f;      // column 15 is the halo column of the rows16 layout
@@ -530,7 +453,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3h16_kernel(const float* __re
                         r2[a] = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
                     }
                 }
-                nonfinite |= ((chk - chk) != 0.f) ? 1u : 0u;         // 0 for every finite sum; NaN != 0 is true
+                nonfinite |= wino_nonfinite(chk) ? 1u : 0u;
                 if constexpr (STATS) {
                     if (gty == 3) r1[3] = 0.f, r2[3] = 0.f;          // board row 15 does not exist
                     // the 16 tiles of this (channel, board) are one DPP row: lanes 16 (2 cosel + gbd) .. + 15

@@ -7,19 +7,24 @@
 // the 256 CUs.
 //
 // SAME BITS as trunk15_wino3h16_kernel<RESID, true, WINO3H16_PLAIN / WINO3H16_PLAIN_SCALED> for every output element of every
-// board.  Restated operation for operation:
-//   input transform  raw *= 2^a (SCALED), vpass, col_pass, exchange and emit are that kernel's, with the same lane roles
-//                    (a board's 16 tiles = one DPP row, the tile columns of a row = a quad, a channel pair 32 lanes apart);
+// board.  SHARED with that kernel -- one function each, so this part of the contract holds by construction:
+//   input transform  f16x2_pow2_pair (SCALED: raw *= 2^a), f16x2_vpass, f16x2_col_pass, f16x2_exchange, f16x2_split of
+//                    wino_f16x2.h, with the same lane roles (a board's 16 tiles = one DPP row, the tile columns of a row = a
+//                    quad, a channel pair 32 lanes apart);
+//   output formulas  wino_out_row for the k direction of every row, wino_sum4 for a row of the check sum and
+//                    wino_nonfinite for its test (wino_common.h).
+// Still RESTATED here operation for operation, and held to the batched kernel by the bit-equality tests alone:
 //   accumulation     per (position, 32 output channels): acc = 0, then for the chunks of 16 input channels in ascending
 //                    order  mfma(H, Vlo), mfma(L, Vhi), mfma(H, Vhi)  with v_mfma_f32_32x32x16_f16, channels 0-7 of the
 //                    chunk in lanes 0-31 and 8-15 in lanes 32-63.  A column of the 32 is (board, tile); a column's result
 //                    does not depend on the others, so a lone board's 16 columns carry the batched kernel's values (the
 //                    other 16 columns repeat them and are dropped).  The contraction is never split;
-//   output transform the hrow formulas per row; the rows combine as in trunk15_wino3s.h -- the lower half hands over
-//                    (h0 + s12, d12, s12), the upper (s34, d34, h5), which are exactly the intermediates of the batched
-//                    kernel's y[0..3] -- then v = fma(y, 1 / S (2^-a), bias) + residual, ReLU, column 15 zeroed;
-//   overflow check   chk over the same 16 values of a (channel, tile) in the same tree (row 15 included, its residual 0),
-//                    (chk - chk) != 0, the word raised by a plain store.
+//   row halves       the rows combine as in trunk15_wino3s.h -- the lower half hands over (h0 + s12, d12, s12), the upper
+//                    (s34, d34, h5), which are exactly the intermediates of wino_out_row over the six row results, and
+//                    y[0..3] is finished from them;
+//   tail             v = fma(y, 1 / S (2^-a), bias) + residual, ReLU, column 15 zeroed;
+//   check tree       chk runs over the same 16 values of a (channel, tile), rows in the same order (row 15 included, its
+//                    residual 0); the word is raised by a plain store.
 // Same inputs: rows16 activations, the packed weights upk3h and bias3h of the batched kernel, the overflow word, the layer's
 // static exponent.
 //
@@ -85,22 +90,13 @@ __global__ __launch_bounds__(512) void trunk15_wino3hs_kernel(const float* __res
     if (bd >= n) return;                              // (uniform) the missing second board of an odd batch
 
     float xsc = 1.f, xisc = 1.f;
-    if constexpr (SCALED) {                           // the host's exponent: the same in every launch of the layer
-        xsc = __builtin_bit_cast(float, (unsigned)(127 + act_exp) << 23);
-        xisc = __builtin_bit_cast(float, (unsigned)(127 - act_exp) << 23);
-    }
+    if constexpr (SCALED) f16x2_pow2_pair(act_exp, xsc, xisc);   // the host's exponent: the same in every launch of the layer
 
     const unsigned plane_b = T::GPLANE * 4;
-    const unsigned act_bytes = (unsigned)n * T::C * plane_b;
-    const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_u =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(upk), 0, (unsigned)Wino3H16::UPK_BYTES, 0x00020000);
-    auto bload = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, unsigned soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
+    const __amdgpu_buffer_rsrc_t r_in = wino_rsrc(in, rows16_bytes(n)), r_u = wino_rsrc(upk, (unsigned)Wino3H16::UPK_BYTES);
 
-    // ---- transform role: trunk15_wino3h16_kernel's, with the wave parity naming the chunk of the step instead of the board:
-    // lane -> (tile = bits 0-3: ttx = bits 0-1, tty = bits 2-3; channel pair cpl = bit 4; channel parity e = bit 5)
+    // ---- transform role: trunk15_wino3h16_kernel's (lane roles: wino_f16x2.h), with the wave parity naming the chunk of the
+    // step instead of the board
     const int kcw = wave & 1, cq = wave >> 1;
     const int ttx = lane & 3, tty = (lane >> 2) & 3, tile = lane & 15, cpl = (lane >> 4) & 1, e = lane >> 5;
     const int cpair = 2 * cq + cpl;                                // channel pair (0..7): V half cpair >> 2, dword cpair & 3
@@ -120,60 +116,19 @@ __global__ __launch_bounds__(512) void trunk15_wino3hs_kernel(const float* __res
 
     f32x2 tt[6][2];                                // vertical-pass results: rows 0..5, column pairs (0, 1), (2, 3)
     float oo[6];
-    // B^T over the rows of the 6 x 6 patch (x0 = row -1 .. x5 = row 4), on column pairs
-    auto vpass = [&](const f32x4 (&raw)[4], int kc) {
-        f32x2 x[6];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const float r3 = raw[3][2 * kc + j], r0 = raw[0][2 * kc + j];
-            x[0][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r3), 0x114, 0xF, 0xF, true));   // row_shr:4
-            x[5][j] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r0), 0x104, 0xF, 0xF, true));   // row_shl:4
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) x[r + 1] = f32x2{raw[r][2 * kc], raw[r][2 * kc + 1]};
-        const f32x2 a = fma2(-4.f, x[2], x[4]), b = fma2(-4.f, x[1], x[3]);
-        const f32x2 c = x[4] - x[2], d = x[3] - x[1];
-        tt[0][kc] = fma2(4.f, x[0], fma2(-5.f, x[2], x[4]));
-        tt[1][kc] = a + b;
-        tt[2][kc] = a - b;
-        tt[3][kc] = fma2(2.f, d, c);
-        tt[4][kc] = fma2(-2.f, d, c);
-        tt[5][kc] = fma2(4.f, x[1], fma2(-5.f, x[3], x[5]));
-    };
-    // B^T over the columns of row j: the halo columns are the quad neighbours' columns 3 and 0 of the same row
-    auto col_pass = [&](int j) {
-        const float c3 = tt[j][1][1], c0 = tt[j][0][0];
-        const int l = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c3), 0x90, 0xF, 0xF, true);
-        const int r = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, c0), 0xF9, 0xF, 0xF, true);
-        const float v0 = __builtin_bit_cast(float, l), v5 = __builtin_bit_cast(float, (unsigned)r & col16_mask);
-        const f32x2 ab = fma2(-4.f, tt[j][0], tt[j][1]);   // (b, a) = (v3 - 4 v1, v4 - 4 v2)
-        const f32x2 dc = tt[j][1] - tt[j][0];              // (d, c) = (v3 - v1, v4 - v2)
-        oo[0] = __builtin_fmaf(c4l, v0, __builtin_fmaf(-5.f, tt[j][0][1], tt[j][1][1]));
-        oo[3] = __builtin_fmaf(2.f, dc[0], dc[1]);
-        oo[1] = ab[1] + ab[0];
-        oo[4] = __builtin_fmaf(-2.f, dc[0], dc[1]);
-        oo[2] = ab[1] - ab[0];
-        oo[5] = __builtin_fmaf(4.f, tt[j][0][0], __builtin_fmaf(-5.f, tt[j][1][0], v5));
-    };
-    // even-channel lanes keep o[0..2] and hand o[3..5] to their pair partner 32 lanes up, odd-channel lanes the other way
-    auto exchange = [&]() {
-        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5"
-            : "+v"(oo[0]), "+v"(oo[1]), "+v"(oo[2]), "+v"(oo[3]), "+v"(oo[4]), "+v"(oo[5]));
-    };
-    // (even channel's value, odd channel's value) of one position -> hi = both rounded to fp16, lo = the exact remainders
+    // (a one-line lambda, not a direct call: the compiler then simplifies it before it inlines it, which keeps the SCALED
+    // kernels' instruction schedule)
+    auto vpass = [&](const f32x4 (&raw)[4], int kc) { f16x2_vpass(raw, kc, tt); };
+    // (even channel's value, odd channel's value) of one position -> its hi and lo words in V
     auto emit = [&](char* vp, float ev, float od) {
-        typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
-        const f16x2_ h2 = {(_Float16)ev, (_Float16)od};                  // v_cvt_pk_f16_f32
-        const unsigned hu = __builtin_bit_cast(unsigned, h2);
-        unsigned lu;
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(ev));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(od));
+        unsigned hu, lu;
+        f16x2_split(ev, od, hu, lu);
         *reinterpret_cast<unsigned*>(vp) = hu;
         *reinterpret_cast<unsigned*>(vp + T::VTERM) = lu;
     };
     auto trow = [&](char* vp, int j, int jj) {         // patch row j = row jj of this half
-        col_pass(j);
-        exchange();
+        f16x2_col_pass(tt, j, c4l, col16_mask, oo);
+        f16x2_exchange(oo);
         emit(vp + (jj * 6 + 0) * T::VPOS, oo[0], oo[3]);
         emit(vp + (jj * 6 + 1) * T::VPOS, oo[1], oo[4]);
         emit(vp + (jj * 6 + 2) * T::VPOS, oo[2], oo[5]);
@@ -288,11 +243,7 @@ __global__ __launch_bounds__(512) void trunk15_wino3hs_kernel(const float* __res
             float m[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 512];
-            const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-            hh[i][0] = (m[0] + s12) + s34;
-            hh[i][1] = __builtin_fmaf(2.f, d34, d12);
-            hh[i][2] = __builtin_fmaf(4.f, s34, s12);
-            hh[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+            wino_out_row(m[0], m[1], m[2], m[3], m[4], m[5], hh[i][0], hh[i][1], hh[i][2], hh[i][3]);
         }
 #pragma unroll
         for (int ee = 0; ee < 4; ee++) {
@@ -366,14 +317,14 @@ __global__ __launch_bounds__(512) void trunk15_wino3hs_kernel(const float* __res
 #pragma unroll
         for (int ee = 0; ee < 4; ee++) v[ee] = __builtin_fmaf(y[a][ee], is, bv);
         if (RESID) v += rs[a];
-        chk += (v[0] + v[1]) + (v[2] + v[3]);   // an overflow of the fp16 split shows as +-inf / NaN here
+        chk += wino_sum4(v);
 #pragma unroll
         for (int ee = 0; ee < 4; ee++) v[ee] = fmaxf(v[ee], 0.f);
         if (etx == 3) v[3] = 0.f;               // column 15 is the halo column of the rows16 layout
         if (4 * ety + a < 15) *reinterpret_cast<f32x4*>(out + plane + po + 16 * a) = v;
     }
     // (a plain store: every writer writes the same 1, and the word may live in pinned host memory)
-    if (((chk - chk) != 0.f) && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
+    if (wino_nonfinite(chk) && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
 }
 
 }  // namespace apz

@@ -270,11 +270,7 @@ __global__ __launch_bounds__(256) void trunk15_wino3s_kernel(const float* __rest
             float m[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) m[k] = mp[(6 * i + k) * 256];
-            const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-            hh[i][0] = (m[0] + s12) + s34;
-            hh[i][1] = __builtin_fmaf(2.f, d34, d12);
-            hh[i][2] = __builtin_fmaf(4.f, s34, s12);
-            hh[i][3] = __builtin_fmaf(8.f, d34, d12) + m[5];
+            wino_out_row(m[0], m[1], m[2], m[3], m[4], m[5], hh[i][0], hh[i][1], hh[i][2], hh[i][3]);
         }
 #pragma unroll
         for (int e = 0; e < 4; e++) {

@@ -5,9 +5,8 @@
 // Winograd packing on one core and the upload; these kernels take a few tens of microseconds.  gfx950.
 #pragma once
 #include "trunk15_wino3b.h"
-#include "trunk15_wino3h.h"
 #include "trunk15_wino3h16.h"
-#include "wino_common.h"
+#include "wino_f16x2.h"
 #include <hip/hip_runtime.h>
 
 namespace apz {
@@ -107,7 +106,7 @@ __global__ void pack_wino3b_folded_kernel(const float* __restrict__ w, const dou
 }
 
 // The U of kernel g (one output channel co, thread = input channel ci of a 128-thread workgroup) for the fp16 x 2 kernels:
-// max |U| of the channel over the workgroup, S = Wino3H::scale_for(max), U S as two fp16 terms (both round to nearest even,
+// max |U| of the channel over the workgroup, S = f16x2_scale_for(max), U S as two fp16 terms (both round to nearest even,
 // the remainder in double) at L::upk_offset; bias3h[co] = bias, bias3h[128 + co] = 1 / S
 template <class L>
 __device__ __forceinline__ void pack_wino3h_channel(const double (&g)[3][3], int co, int ci, double bias, unsigned short* __restrict__ up,
@@ -134,18 +133,17 @@ __device__ __forceinline__ void pack_wino3h_channel(const double (&g)[3][3], int
         if (ci < s) red[ci] = fmax(red[ci], red[ci + s]);
         __syncthreads();
     }
-    const float S = Wino3H::scale_for(red[0]);
+    const float S = f16x2_scale_for(red[0]);
     if (ci == 0) {
         bias3h[co] = (float)bias;
         bias3h[128 + co] = 1.f / S;
     }
 #pragma unroll
     for (int pos = 0; pos < 36; pos++) {
-        const double x = u[pos] * (double)S;
-        const _Float16 hi = (_Float16)(float)x;
-        const _Float16 lo = (_Float16)(float)(x - (double)(float)hi);
-        up[L::upk_offset(co, ci, pos, 0) / 2] = __builtin_bit_cast(unsigned short, hi);
-        up[L::upk_offset(co, ci, pos, 1) / 2] = __builtin_bit_cast(unsigned short, lo);
+        unsigned short hb, lb;
+        f16x2_split(u[pos] * (double)S, hb, lb);
+        up[L::upk_offset(co, ci, pos, 0) / 2] = hb;
+        up[L::upk_offset(co, ci, pos, 1) / 2] = lb;
     }
 }
 

@@ -50,10 +50,9 @@
 #include <hip/hip_runtime.h>
 
 #include "wgrad_wino3.h"
+#include "wino_f16x2.h"
 
 namespace apz {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct WgradWino3H {
     static constexpr int C = 128, CO_B = 32, CI_B = 32, BLOCKS = (C / CO_B) * (C / CI_B);   // 16 channel blocks
@@ -83,10 +82,9 @@ __device__ __forceinline__ int wgw3h_exponent(float m) {
 __device__ __forceinline__ void wgw3h_emit2(char* dst, float v0, float v1) {
     // (as asm: left to the compiler, the conversions of values that come out of an FMA are folded into v_fma_mix pairs -- three
     // instructions and a move instead of one)
-    unsigned hu, lu;
+    unsigned hu;
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hu) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lu) : "v"(hu), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lu) : "v"(hu), "v"(v1));
+    const unsigned lu = f16x2_split_lo(hu, v0, v1);
     using T = WgradWino3H;
     *reinterpret_cast<unsigned short*>(dst) = (unsigned short)hu;
     *reinterpret_cast<unsigned short*>(dst + T::POS_BYTES) = (unsigned short)(hu >> 16);
@@ -135,8 +133,7 @@ __global__ __launch_bounds__(512) void wgrad_wino3h_kernel(const float* __restri
         __syncthreads();                              // (the epilogue's staging area covers wm)
         const int a = __builtin_amdgcn_readfirstlane(wgw3h_exponent(m));
         max_inf = !(m <= 3.4028234664e38f);
-        sc = __builtin_bit_cast(float, (unsigned)(127 + a) << 23);
-        isc = __builtin_bit_cast(float, (unsigned)(127 - a) << 23);
+        f16x2_pow2_pair(a, sc, isc);
     }
 
     // ---- MFMA roles: wave = (position group pg: positions 9 pg .. 9 pg + 8) x (output-channel group cc)

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include "trunk15_wino3.h"
 #include "trunk15_wino3h.h"
 #include "trunk15_wino3h16.h"
 
@@ -147,7 +148,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 128; i++) hb[i] = ((rand() % 2000) - 1000) * 1e-4f;
     apz::wino3h_pack_host<TK>(u_of, uk, hb.data() + 128);
     CK(hipMemcpy(upkk, uk.data(), TK::UPK_BYTES, hipMemcpyHostToDevice));
-    apz::wino3h_pack_host(u_of, uh, hb.data() + 128);
+    apz::wino3h_pack_host<apz::Wino3H>(u_of, uh, hb.data() + 128);
     CK(hipMemcpy(upkh, uh.data(), TH::UPK_BYTES, hipMemcpyHostToDevice));
     CK(hipMemcpy(bias, hb.data(), 512, hipMemcpyHostToDevice));
     CK(hipMemcpy(biash, hb.data(), 1024, hipMemcpyHostToDevice));

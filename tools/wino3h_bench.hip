@@ -138,7 +138,7 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(upkb, ub.data(), TB::UPK_BYTES, hipMemcpyHostToDevice));
     std::vector<float> hb(256);
     for (int i = 0; i < 128; i++) hb[i] = ((rand() % 2000) - 1000) * 1e-4f;
-    apz::wino3h_pack_host(u_of, uh, hb.data() + 128);
+    apz::wino3h_pack_host<apz::Wino3H>(u_of, uh, hb.data() + 128);
     CK(hipMemcpy(upkh, uh.data(), TH::UPK_BYTES, hipMemcpyHostToDevice));
     CK(hipMemcpy(bias, hb.data(), 512, hipMemcpyHostToDevice));
     CK(hipMemcpy(biash, hb.data(), 1024, hipMemcpyHostToDevice));
