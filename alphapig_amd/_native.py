@@ -127,7 +127,7 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_layout_convert", "apz_bias_grad", "apz_add", "apz_load_weights_dev",
                "apz_sync", "apz_stream", "apz_set_forward_graphs",
                "apz_device_alloc", "apz_device_free", "apz_memcpy_h2d", "apz_memcpy_d2h",
-               "apz_conv3x3_bench", "apz_layer_io", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows",
+               "apz_conv3x3_bench", "apz_layer_io", "apz_layer_frame", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows",
                "apz_set_trunk_act_exponents", "apz_get_trunk_act_exponents", "apz_calibrate_trunk_planes", "apz_calibrate_trunk_codes",
                "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host"]
 
@@ -285,6 +285,7 @@ def hip():
         "apz_memcpy_d2h": (C.c_int, [vp, vp, vp, C.c_int64]),
         "apz_conv3x3_bench": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
         "apz_layer_io": (C.c_int, [vp, C.c_int, f32p, C.c_int64]),
+        "apz_layer_frame": (C.c_int, [vp, C.c_int, f32p, C.c_int64]),
         "apz_set_profiling": (C.c_int, [vp, C.c_int]),
         "apz_kernel_time_ms": (C.c_int, [vp, C.c_int, f32p]),
         "apz_prewarm": (C.c_int, [vp, C.c_int, C.c_int]),

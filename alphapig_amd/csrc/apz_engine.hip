@@ -33,6 +33,7 @@
 #include "weights_pack.h"
 #include "act_max.h"
 #include "replay.h"
+#include "frame15.h"
 
 namespace {
 
@@ -172,6 +173,10 @@ struct apz_engine {
     std::recursive_mutex submit_lock;
     bool ring = false;      // 15x15 / 128-filter resnet: trunk activations in rows16 layout (trunk15_ring.h)
     bool small8 = false;    // 8x8 boards: conv8_kernel / head8_kernel (conv8_small.h)
+    // Framed engines (csrc/frame15.h): a square board of side frame_s in 6..14 (not 8, not 10) in the top-left corner of the 15x15
+    // frame of a `ring` engine; 0 = not framed.  hw, code_stride, the heads and the tables stay those of the S x S board.
+    int frame_s = 0;
+    float* fplanes = nullptr;   // framed input planes [max_batch][9][15][15]
     float* wfc_raw = nullptr;   // head8_kernel: the policy FullyConnected weight as stored, [hw][4 hw]
     int act_ps = 0, act_rs = 0;
     std::vector<LdsAttr> lds_attrs;   // need_lds: one entry per kernel launched with dynamic LDS so far
@@ -657,9 +662,55 @@ int launch_conv8(apz_engine* e, const ConvLayer& L, const float* in, const float
     return launch_conv8_t<false, false>(e, L, in, nullptr, out, n);
 }
 
+// ---- framed engines (csrc/frame15.h)
+// position codes -> e->fplanes
+int launch_frame_encode(apz_engine* e, const unsigned char* codes, int n) {
+    const long total = (long)n * apz::Frame15::CELLS;
+    hipLaunchKernelGGL(apz::frame_encode_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 8)), dim3(256), 0,
+                       e->stream, codes, e->fplanes, n, e->frame_s, e->code_stride, e->cfg.c_in);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// dense planes [n][c_in][S][S] -> e->fplanes
+int launch_frame_planes(apz_engine* e, const float* planes, int n) {
+    const long nplanes = (long)n * e->cfg.c_in, total = nplanes * apz::Frame15::CELLS;
+    hipLaunchKernelGGL(apz::frame_planes_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 8)), dim3(256), 0,
+                       e->stream, planes, e->fplanes, nplanes, e->frame_s);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// zeroes the off-board cells of the rows16 activation `act` of n boards (128 channels)
+int launch_frame_clear(apz_engine* e, float* act, int n) {
+    const long nplanes = (long)n * apz::Trunk15::C;            // one wavefront per plane, four per workgroup
+    hipLaunchKernelGGL(apz::frame_clear_kernel, dim3((int)std::min<long>((nplanes + 3) / 4, e->num_cu * 64)), dim3(256), 0,
+                       e->stream, act, nplanes, e->frame_s);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// the first layer of a framed engine: framing kernel, the planes form of the stem, clear (unless it is the net's last layer)
+int launch_frame_stem(apz_engine* e, const float* planes, const unsigned char* codes, float* out, int n) {
+    if (int rc = codes ? launch_frame_encode(e, codes, n) : launch_frame_planes(e, planes, n)) return rc;
+    if (int rc = launch_stem15(e, e->convs[0], e->fplanes, out, n)) return rc;
+    return e->convs.size() > 1 ? launch_frame_clear(e, out, n) : APZ_OK;
+}
+
+// a trunk layer of a framed engine: the 15x15 route of the batch, then the clear (skipped behind the net's last layer: the
+// heads read on-board cells only)
+int launch_frame_layer(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    if (int rc = launch_trunk_ring(e, L, in, resid, out, n)) return rc;
+    return &L != &e->convs.back() ? launch_frame_clear(e, out, n) : APZ_OK;
+}
+
 int launch_conv(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     const int H = e->cfg.height, W = e->cfg.width, ct = L.cout / 64;
     if (e->small8) return launch_conv8(e, L, in, resid, out, n);
+    if (e->frame_s) {                   // `in` of the first layer: dense S x S planes
+        if (&L != &e->convs[0]) return launch_frame_layer(e, L, in, resid, out, n);
+        return launch_frame_stem(e, in, nullptr, out, n);
+    }
     if (e->ring && &L != &e->convs[0]) return launch_trunk_ring(e, L, in, resid, out, n);
     if (e->ring) return launch_stem15(e, L, in, out, n);
     if (H == 15 && W == 15) {
@@ -694,7 +745,9 @@ int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** resul
     {
         Timed tm(e, APZ_K_STEM);
         int rc;
-        if (codes && e->small8)
+        if (e->frame_s)                 // (the pair covers the framing kernel, the stem and its clear)
+            rc = launch_frame_stem(e, cur, codes, x, n);
+        else if (codes && e->small8)
             rc = launch_conv8(e, e->convs[0], nullptr, nullptr, x, n, codes);       // the first layer decodes the codes itself
         else if (codes && e->ring && e->cfg.net_kind == APZ_NET_RESNET)
             rc = launch_stem15(e, e->convs[0], nullptr, x, n, codes);
@@ -705,7 +758,7 @@ int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** resul
     }
     if (last >= 1) {
         Timed tm(e, APZ_K_TRUNK);       // all trunk launches of this forward under one event pair
-        tm.launches = last;
+        tm.launches = last;             // (framed engines: the clears are inside the pair and counted with their layers)
         for (int li = 1; li <= last; li++) {
             const ConvLayer& L = e->convs[li];
             if (e->measure_max) {
@@ -771,7 +824,7 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
     }
     {
         Timed tm(e, APZ_K_HEAD_CONV);
-        if (e->ring && e->clast % 32 == 0)
+        if (e->ring && !e->frame_s && e->clast % 32 == 0)
             hipLaunchKernelGGL(apz::head_conv1x1_r16_kernel, dim3(n), dim3(256), 0, e->stream, trunk, e->w6, e->b6,
                                e->featp, e->featv, n, e->clast);
         else
@@ -786,7 +839,9 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
         const int lds = 16 * std::max(4 * hw + 1, ntile * 16) * (int)sizeof(float);
         const int grid = (n + 15) / 16;
         const int tpw = (ntile + 3) / 4;
-        if (tpw <= 1) {
+        // (framed engines take the two-launch form at every size: at 6x6 and 7x7, hw <= 64, the fused form would be a path
+        // no engine has run before)
+        if (tpw <= 1 && !e->frame_s) {
             if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1>, lds)) return rc2;
             hipLaunchKernelGGL(apz::head_fc_kernel<1>, dim3(grid), dim3(256), lds, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw);
@@ -1064,7 +1119,7 @@ void apz_destroy(apz_engine* e) {
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
                    e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
-                   e->wfc_raw, e->amax_dev, e->gather_entries};
+                   e->wfc_raw, e->amax_dev, e->gather_entries, e->fplanes};
     for (void* p : dev)
         if (p) hipFree(p);
     e->w3s.release();
@@ -1089,8 +1144,20 @@ apz_engine* apz_create(const apz_config* cfg) {
         fail(APZ_E_ARG, "bad config (c_in must be 9 or 4)");
         return nullptr;
     }
-    if (!((cfg->height == 15 && cfg->width == 15) || (cfg->height == 8 && cfg->width == 8))) {
-        fail(APZ_E_UNSUPPORTED, "HIP kernels are instantiated for 15x15 and 8x8 boards");
+    if (cfg->height != cfg->width || cfg->height < 6 || cfg->height > 15) {
+        fail(APZ_E_UNSUPPORTED, "boards are square, 6x6 to 15x15 (not 10x10): 15x15 and 8x8 have kernels of their own, the other sizes run "
+                                "the 128-filter residual net on the 15x15 trunk kernels (csrc/frame15.h)");
+        return nullptr;
+    }
+    const bool framed = apz::Frame15::framed_side(cfg->height);
+    if (cfg->height == 10) {
+        fail(APZ_E_UNSUPPORTED, "10x10 boards are not supported: 15x15 and 8x8 have kernels of their own, 6x6, 7x7, 9x9 and 11x11 "
+                                "to 14x14 run the 128-filter residual net on the 15x15 trunk kernels (csrc/frame15.h)");
+        return nullptr;
+    }
+    if (framed && (cfg->net_kind != APZ_NET_RESNET || cfg->n_filter != 128)) {
+        fail(APZ_E_UNSUPPORTED, "boards of 6x6 to 14x14 other than 8x8 and 10x10 run the residual net with 128 filters only (the simple "
+                                "net and 64 / 256 filters exist at 15x15 and 8x8)");
         return nullptr;
     }
     if (cfg->net_kind == APZ_NET_RESNET &&
@@ -1132,7 +1199,8 @@ apz_engine* apz_create(const apz_config* cfg) {
     }
     if ((err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess)
         return bail("hipStreamCreate", err);
-    e->ring = cfg->net_kind == APZ_NET_RESNET && cfg->height == 15 && cfg->width == 15 && cfg->n_filter == 128;
+    e->frame_s = framed ? cfg->height : 0;
+    e->ring = cfg->net_kind == APZ_NET_RESNET && cfg->n_filter == 128 && (framed || (cfg->height == 15 && cfg->width == 15));
     e->small8 = cfg->height == 8 && cfg->width == 8;
     e->act_ps = e->ring ? apz::Trunk15::GPLANE : e->hw;
     e->act_rs = e->ring ? apz::Trunk15::GROW : cfg->width;
@@ -1145,6 +1213,8 @@ apz_engine* apz_create(const apz_config* cfg) {
         if ((err = hipMemset(e->act[i], 0, act_bytes)) != hipSuccess) return bail("hipMemset(act)", err);
     }
     if ((err = hipMalloc((void**)&e->planes, B * 9 * hw * sizeof(float))) != hipSuccess) return bail("hipMalloc", err);
+    if (framed && (err = hipMalloc((void**)&e->fplanes, B * 9 * apz::Frame15::CELLS * sizeof(float))) != hipSuccess)
+        return bail("hipMalloc(framed planes)", err);
     if ((err = hipMalloc((void**)&e->featp, B * 4 * hw * sizeof(float))) != hipSuccess) return bail("hipMalloc", err);
     if ((err = hipMalloc((void**)&e->featv, B * 2 * hw * sizeof(float))) != hipSuccess) return bail("hipMalloc", err);
     if ((err = hipMalloc((void**)&e->probs, B * hw * sizeof(float))) != hipSuccess) return bail("hipMalloc", err);
@@ -2596,6 +2666,27 @@ int apz_layer_io(apz_engine* e, int layer, float* host_out, int64_t count) {
     for (size_t pc = 0; pc < (size_t)e->last_n * C; pc++)
         for (int y = 0; y < H; y++)
             for (int x = 0; x < W; x++) host_out[(pc * H + y) * W + x] = tmp[pc * e->act_ps + y * e->act_rs + x];
+    return APZ_OK;
+}
+
+int apz_layer_frame(apz_engine* e, int layer, float* host_out, int64_t count) {
+    if (!e || !host_out) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    if (!e->ring) return fail(APZ_E_UNSUPPORTED, "layer_frame: engines with rows16 activations only (the 128-filter residual net at 15x15 and at framed sizes)");
+    if (!e->loaded || e->last_n < 1) return fail(APZ_E_STATE, "run a forward first");
+    if (layer < 0 || layer >= (int)e->convs.size()) return fail(APZ_E_ARG, "bad layer");
+    const int64_t need = (int64_t)e->last_n * e->convs[layer].cout * e->act_ps;
+    if (count != need) return fail(APZ_E_ARG, "count must be n*C_out*15*16 = " + std::to_string(need));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    float* buf = nullptr;
+    const bool was = e->profiling;
+    e->profiling = false;
+    ArmOverflowWord arm(e);
+    int rc = run_trunk(e, e->planes, e->last_n, layer, &buf);
+    e->profiling = was;
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(host_out, buf, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return APZ_OK;
 }
 

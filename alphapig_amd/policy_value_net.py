@@ -63,6 +63,8 @@ class PolicyValueNet(object):
                    engine repeat that forward on the exact kernel (never a silently wrong result);
           "bf16x3" three bf16 terms, six products (csrc/trunk15_wino3b.h): round 4's form, kept for comparison;
           "auto"   (default) "f16x2" where such kernels exist (15x15 / 128-filter residual net; 8x8 boards), else "f32".
+        Square boards of 6x6 .. 14x14 other than 8x8 and 10x10 (128-filter residual net only) run framed on the 15x15 kernels and
+        follow the 15x15 rules throughout; HipTrainer / train_step do not support them.
         8x8 boards (round 6): "f16x2" runs every convolution with a multiple of 64 input channels on the fp16 matrix pipe with
         split operands (csrc/conv8_split.h), for EVERY batch size: a board's bits do not depend on the batch there.
         uniform_trunk (default False): with "f16x2" on the 15x15 / 128-filter net, batches of <= 32 boards run the small-batch
@@ -90,8 +92,12 @@ class PolicyValueNet(object):
             raise ValueError("trunk_arith must be 'auto', 'f32', 'f16x2' or 'bf16x3'")
         ring15 = net_kind == "resnet" and self.board_width == 15 and self.board_height == 15 and self._n_filter == 128
         small8 = self.board_width == 8 and self.board_height == 8
+        # square boards of 6x6 .. 14x14 other than 8x8 and 10x10 (refused): the same net framed on the 15x15 kernels (csrc/frame15.h) -- every
+        # arithmetic, uniform_trunk and the activation exponents as at 15x15
+        framed = (net_kind == "resnet" and self._n_filter == 128 and self.board_width == self.board_height and
+                  6 <= self.board_width <= 14 and self.board_width not in (8, 10))
         if trunk_arith == "auto":
-            trunk_arith = "f16x2" if (ring15 or small8) else "f32"
+            trunk_arith = "f16x2" if (ring15 or small8 or framed) else "f32"
         self.trunk_arith = trunk_arith
         if trunk_arith != "f32":                                     # before the weights are loaded: they are packed for it
             self._ck(self.L.apz_set_trunk_arith(self._h, {"bf16x3": 1, "f16x2": 2}[trunk_arith]))
@@ -248,6 +254,13 @@ class PolicyValueNet(object):
         cout = self._n_filter if self.net_kind == "resnet" else weights.SIMPLE_LAYERS[layer][1]
         out = np.empty((n, cout, self.board_height, self.board_width), dtype=np.float32)
         self._ck(self.L.apz_layer_io(self._h, int(layer), as_ptr(out, C.c_float), out.size))
+        return out
+
+    def layer_frame(self, layer, n):
+        """Test hook, nets with padded-row activations (128-filter residual net at 15x15 and at the framed sizes): the raw
+        activation [n, C, 15, 16] of conv layer `layer` for the last forward_planes batch (apz_layer_frame)."""
+        out = np.empty((n, self._n_filter, 15, 16), dtype=np.float32)
+        self._ck(self.L.apz_layer_frame(self._h, int(layer), as_ptr(out, C.c_float), out.size))
         return out
 
     def evaluate_codes(self, codes):

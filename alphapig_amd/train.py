@@ -34,6 +34,21 @@ SIMPLE_CONVS = ("conv1", "conv2", "conv3", "conv4", "conv5", "conv_final")
 DeviceBatch = collections.namedtuple("DeviceBatch", "states pis zs")     # HipTrainer.upload()
 
 
+TRAINABLE_SIDES = (15, 8)
+
+
+def check_trainable_board(params):
+    """ValueError unless the policy head of `params` (fc_3_1_1_bias: one output per cell) belongs to a board the training
+    kernels exist for: 15x15 or 8x8.  The evaluator also runs the other square boards from 6x6 to 14x14 except 10x10 ("framed" on the 15x15
+    trunk kernels, csrc/frame15.h); the training step does not -- the padded-row training kernels take their BatchNorm
+    statistics over all 225 cells of the frame ("Boards smaller than 15x15").  Needs no GPU."""
+    hw = int(np.asarray(params["fc_3_1_1_bias"]).shape[0])
+    side = int(round(hw ** 0.5))
+    if side * side == hw and side not in TRAINABLE_SIDES:
+        raise ValueError("HipTrainer supports 15x15 and 8x8 boards, not %dx%d: the evaluator runs the other 6x6 .. 14x14 boards (not 10x10) framed "
+                         "on the 15x15 kernels, the training step on them does not exist" % (side, side))
+
+
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
                  seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32"):
@@ -51,6 +66,8 @@ class HipTrainer(object):
         only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)"""
         if trunk_arith not in ("f32", "f16x2"):
             raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
+        if "fc_3_1_1_bias" in params:
+            check_trainable_board(params)          # before anything touches the GPU: today's failure would come from the first step
         import torch
         from . import _native, hipconv
         if not torch.cuda.is_available():

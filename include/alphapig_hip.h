@@ -35,7 +35,8 @@ extern "C" {
 #define APZ_NET_RESNET 0     /* policy_value_net_mxnet.py        */
 #define APZ_NET_SIMPLE 1     /* policy_value_net_mxnet_simple.py */
 
-/* kernel classes for apz_kernel_time_ms */
+/* kernel classes for apz_kernel_time_ms (framed engines, see apz_create: APZ_K_STEM includes the framing kernel and the
+ * stem's clear, APZ_K_TRUNK the clears behind the trunk convolutions, counted with their layers) */
 #define APZ_K_STEM 0
 #define APZ_K_TRUNK 1
 #define APZ_K_HEAD_CONV 2
@@ -61,6 +62,15 @@ const char *apz_last_error(void);
 int apz_version(void);
 int apz_device_count(void);
 
+/* Boards: 15x15 and 8x8 (either net, 64 / 128 / 256 filters) have kernels of their own.  Every other square board of side
+ * S in 6 .. 14 except 10 is a "framed" engine (csrc/frame15.h): the residual net with 128 filters, c_in 9 or 4, computed by the 15x15
+ * trunk kernels on a 15x15 frame that holds the board in its top-left S x S window; the off-board cells of every
+ * activation are zeroed after each layer, so the results are those of the S x S net.  Every interface below speaks S x S
+ * (planes [n][c_in][S][S], codes of stride (S*S + 1 + 15) / 16 * 16, S*S probabilities); all inference entry points, the
+ * arithmetics, apz_set_trunk_uniform, the activation exponents and the HIP-graph replay work as at 15x15.  The training
+ * entry points (apz_conv3x3_fwd, apz_wino_*, apz_layout_convert, ...) stay 15x15 / 8x8 only.
+ * APZ_E_UNSUPPORTED (NULL, message in apz_last_error): non-square boards, S < 6, S > 15, 10x10, and at a framed size the simple net
+ * or 64 / 256 filters. */
 apz_engine *apz_create(const apz_config *cfg);
 void apz_destroy(apz_engine *e);
 
@@ -341,6 +351,11 @@ int apz_conv3x3_bench(apz_engine *e, int layer, int n, int iters, int warmup, fl
 /* After a forward of batch n: copy the output activation of conv layer `layer`
  * ([n][C_out][H][W]) to host (per-layer parity tests). */
 int apz_layer_io(apz_engine *e, int layer, float *host_out, int64_t count);
+/* TEST HOOK, engines with padded-row activations (the 128-filter residual net at 15x15 and at framed sizes): the same for
+ * the raw activation [n][C_out][15][16], count = n * C_out * 240.  On a framed engine every cell outside the S x S window
+ * of every layer but the last is exactly +0 (csrc/frame15.h); the last layer's off-board cells hold whatever the
+ * convolution left there (the heads read on-board cells only). */
+int apz_layer_frame(apz_engine *e, int layer, float *host_out, int64_t count);
 /* Per-kernel-class HIP-event timing over subsequent forwards: on = 1 times every forward,
  * on = k > 1 every k-th forward (the event records cost a few us per kernel, so sampled timing
  * keeps the measured run undisturbed); then read out[0] = total ms, out[1] = timed launches

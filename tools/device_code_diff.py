@@ -7,7 +7,7 @@ A tree is a checkout (or an export of one) with alphapig_amd/csrc and include/, 
 under --keep.  Each tree's apz_engine.hip is compiled
 device-only to assembly with the flags of alphapig_amd/build.py; comments and directives are dropped and every kernel gets
 one verdict:
-    identical    the same lines
+    identical    the same lines (basic-block labels compared without the function's index in the module)
     scalar-only  the same number of instructions and the same count per mnemonic, the same sequence of non-scalar
                  instructions once SGPR operands are masked, and the same resource metadata (registers, spills, LDS, scratch)
     different    anything else, a kernel that exists on one side only included
@@ -24,6 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size",
         "private_segment_fixed_size")
 SGPR = re.compile(r"\bs(\d+|\[\d+:\d+\])")
+LOCAL_LABEL = re.compile(r"\.LBB\d+_(\d+)")
 
 
 def assemble(tree, out):
@@ -50,7 +51,8 @@ def kernels(path):
         elif s.startswith(".Lfunc_end"):
             cur = None
         elif s and (not s.startswith(".") or s.endswith(":")):      # instructions and labels; no directives
-            cur.append(s)
+            # .LBB<f>_<b>: f is the function's position in the module, which moves when kernels are added in front of it
+            cur.append(LOCAL_LABEL.sub(r".LBB#_\1", s))
     meta, entry = {}, {}
     for l in lines:
         m = re.match(r"^  (- |  )\.(\w+):\s*(\S+)\s*$", l)          # the kernel level of .amdgpu_metadata (arguments sit deeper)
