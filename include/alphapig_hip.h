@@ -105,7 +105,10 @@ int apz_forward_codes_async(apz_engine *e, const uint8_t *codes_pinned, int n, f
  * wait blocks on that event and copies the slot's results out.  A second batch submitted while
  * the first runs starts the moment the first one's last kernel ends (no host round trip in
  * between).  submit calls are serialised by an internal lock; different slots may be submitted
- * and waited from different host threads. */
+ * and waited from different host threads.  A batch is answered with the weights installed when it
+ * was submitted, whatever is installed before the wait (tests/test_gpu_weight_versions.py), with one
+ * exception: an APZ_ARITH_F16X2 batch that overflowed is repeated by apz_wait on the exact-fp32 kernel
+ * with the weights installed at the time of the WAIT, not those it was submitted under. */
 #define APZ_MAX_SLOTS 4
 int apz_submit_codes(apz_engine *e, int slot, const uint8_t *codes_host, int n);
 int apz_wait(apz_engine *e, int slot, float *probs_host, float *values_host);
