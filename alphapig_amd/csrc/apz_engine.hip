@@ -1,6 +1,6 @@
 // libalphapig_hip.so -- C ABI (include/alphapig_hip.h) over the gfx950 kernels.
-// Host-side glue only: parameter table, BatchNorm folding + weight packing, buffer ownership,
-// launch sequencing on one HIP stream, HIP-event timing hooks.
+// Host-side glue only: parameter table, buffer ownership, launch sequencing on one HIP stream (the BatchNorm
+// fold and weight packing kernels of weights_pack.h included), HIP-event timing hooks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,7 +67,10 @@ struct ConvLayer {
     bool fix_gamma;
     int cin, cin_pad, cout;
     bool residual;          // add the block input before ReLU
-    float* wpk = nullptr;
+    // The packed forms of the layer's weights.  alloc_packed decides from the engine's configuration which of them the
+    // layer has (and zeroes them: the pad slots are never written again), pack_all fills every one that is there with the
+    // kernels of weights_pack.h, for apz_load_weights and apz_load_weights_dev alike.
+    float* wpk = nullptr;   // direct convolution: [cot][c4][tap][lane]; trunk15_ring_kernel layers: [cot][c4][lane][12]
     float* wpk12 = nullptr; // 8x8 boards (conv8_kernel): [cot][c4][lane][12]
     float* upk2 = nullptr;  // trunk15_wino3_kernel: transformed weights G g G^T, [cot][row half][c4][lane][20] (wino_common.h)
     float* upk3s = nullptr; // trunk15_wino3s_kernel: the same values, [cot][wave][c4][piece][lane][4] (WinoPackSmall)
@@ -189,7 +192,8 @@ struct apz_engine {
     float* zeros256 = nullptr;          // bias stand-in for bias-free convolutions (ensure_zeros256)
     double* bn_part = nullptr;                     // apz_bn_fwd / _bwd: per-(channel, batch split) partial sums [256 * BN_SPLITS][2]
     float* wgw_scratch = nullptr;                  // apz_wgrad_wino: partial dU per batch slice
-    double* fold_ws = nullptr;                     // apz_load_weights_dev: scale / shift of one layer (2 x 256 doubles)
+    double* fold_ws = nullptr;                     // pack_all: scale / shift of one layer (2 x cmax doubles)
+    float* stage = nullptr;                        // apz_load_weights: the host tensors, back to back in table order
     float* head_scratch = nullptr;                 // apz_conv1x1_bwd / apz_pv_loss: per-board partial sums
     size_t head_scratch_floats = 0;
     size_t wgw_floats = 0;                         // capacity of wgw_scratch
@@ -290,25 +294,6 @@ void build_tables(apz_engine* e) {
     e->clast = last;
     e->cmax = 0;
     for (auto& l : e->convs) e->cmax = std::max(e->cmax, l.cout);
-}
-
-// scale/shift of an inference BatchNorm folded behind a conv with bias
-void fold_bn(const std::map<std::string, const float*>& P, const std::string& conv, const std::string& bn,
-             const std::string& mean_sfx, const std::string& var_sfx, bool fix_gamma, int cout,
-             std::vector<double>& scale, std::vector<double>& shift) {
-    const float* bias = P.at(conv + "_bias");
-    const float* gamma = P.at(bn + "_gamma");
-    const float* beta = P.at(bn + "_beta");
-    const float* mean = P.at(bn + mean_sfx);
-    const float* var = P.at(bn + var_sfx);
-    scale.resize(cout);
-    shift.resize(cout);
-    for (int o = 0; o < cout; o++) {
-        const double g = fix_gamma ? 1.0 : (double)gamma[o];
-        const double s = g / std::sqrt((double)var[o] + BN_EPS);
-        scale[o] = s;
-        shift[o] = ((double)bias[o] - (double)mean[o]) * s + (double)beta[o];
-    }
 }
 
 template <typename T>
@@ -914,8 +899,8 @@ int act_scale_buffers(apz_engine* e) {
 
 // The largest |a| the layer's weights allow: 2^-a goes into 1 / S[co] = 2^-k of the bias FMA, and 2^-(a + k) must be a
 // normal float for every output channel (the subnormal case is exact only while fp32 denormals are enabled: see the DGRAD
-// comment in trunk15_wino3h16.h).  Reads the layer's 1 / S from the device: the device-side weight refresh computes them
-// there.  Synchronous.
+// comment in trunk15_wino3h16.h).  Reads the layer's 1 / S from the device: the packing kernels compute them there.
+// Synchronous.
 int clamp_act_exponent(apz_engine* e, const ConvLayer& L, int a, int* out) {
     a = std::max(-apz::ACT_EXP_MAX, std::min(apz::ACT_EXP_MAX, a));
     if (a != 0 && L.bias3h) {
@@ -1084,6 +1069,142 @@ void build_perms(int N, std::vector<int>& ps, std::vector<int>& pp) {
     }
 }
 
+// ---- weights: apz_load_weights and apz_load_weights_dev share everything below
+
+typedef std::map<std::string, const float*> ParamPtrs;
+
+// name -> pointer of the caller's table (host or device pointers alike); every parameter of the net must be there, at its size
+int check_param_table(apz_engine* e, const char* const* names, const void* const* ptrs, const int64_t* sizes, int n, ParamPtrs& P) {
+    std::map<std::string, int64_t> S;
+    for (int i = 0; i < n; i++) {
+        P[names[i]] = (const float*)ptrs[i];
+        S[names[i]] = sizes[i];
+    }
+    for (auto& p : e->params) {
+        auto it = S.find(p.name);
+        if (it == S.end()) return fail(APZ_E_ARG, "missing parameter " + p.name);
+        if (it->second != p.size)
+            return fail(APZ_E_ARG, "parameter " + p.name + " has " + std::to_string(it->second) + " elements, expected " +
+                                       std::to_string(p.size));
+    }
+    return APZ_OK;
+}
+
+// Zeroed on the engine's stream, in front of the first packing kernels: those write the value slots of a layout only, and
+// the forward kernels load the pad slots next to them with 16-byte reads.  Keeps a buffer it finds (a first load that failed
+// half way is repeated).
+template <typename T>
+int alloc_zeroed(apz_engine* e, T** dst, size_t bytes) {
+    if (*dst) return APZ_OK;
+    HIP_TRY(hipMalloc((void**)dst, bytes));
+    HIP_TRY(hipMemsetAsync(*dst, 0, bytes, e->stream));
+    return APZ_OK;
+}
+
+// Every weight buffer the engine's configuration needs (net, ring, small8, frame_s through ring, trunk_arith -- fixed from
+// the first load on: apz_set_trunk_arith), sized by the layouts' own constants, plus the fold scratch and the staging
+// buffer of apz_load_weights.  The first apz_load_weights calls it; nothing else allocates a weight buffer.
+int alloc_packed(apz_engine* e) {
+    int rc = APZ_OK;
+    auto get = [&](auto** dst, size_t bytes) {
+        if (rc == APZ_OK) rc = alloc_zeroed(e, dst, bytes);
+    };
+    const bool f16x2 = e->trunk_arith == APZ_ARITH_F16X2;
+    static_assert(apz::Wino3H16::UPK_BYTES == apz::Wino3H::UPK_BYTES, "both f16x2 kernels share the layer's upk3h buffer");
+    for (auto& L : e->convs) {
+        const bool wino = e->ring && &L != &e->convs[0];     // a 128 -> 128 layer of the 15x15 trunk kernels
+        const size_t frags = (size_t)(L.cout / 16) * (L.cin_pad / 4) * 64;
+        get(&L.wpk, frags * (wino ? 12 : 9) * sizeof(float));
+        get(&L.bias, L.cout * sizeof(float));
+        if (e->small8) get(&L.wpk12, frags * 12 * sizeof(float));
+        if (e->small8 && f16x2 && apz::Conv8H::supports(L.cin, L.cout)) {
+            get(&L.wpk8h, apz::Conv8H::pk_bytes(L.cin, L.cout));
+            get(&L.bias8h, 2 * (size_t)L.cout * sizeof(float));
+        }
+        if (wino) {
+            get(&L.upk2, apz::WinoPack::UPK_FLOATS * sizeof(float));
+            get(&L.upk3s, apz::WinoPackSmall::UPK_FLOATS * sizeof(float));
+        }
+        if (wino && e->trunk_arith == APZ_ARITH_BF16X3) get(&L.upk3b, apz::Wino3B::UPK_BYTES);
+        if (wino && f16x2) {
+            get(&L.upk3h, apz::Wino3H::UPK_BYTES);
+            get(&L.bias3h, apz::Wino3H::BIAS_FLOATS * sizeof(float));
+        }
+    }
+    const size_t C = e->clast, hw = e->hw;
+    get(&e->w6, 6 * C * sizeof(float));
+    get(&e->b6, 6 * sizeof(float));
+    get(&e->wfc_pk, ((hw + 15) / 16) * ((hw + 7) / 8) * 64 * 8 * sizeof(float));
+    get(&e->bfc, hw * sizeof(float));
+    get(&e->wv, 2 * hw * sizeof(float));
+    get(&e->bv, sizeof(float));
+    if (e->small8) get(&e->wfc_raw, hw * 4 * hw * sizeof(float));
+    get(&e->fold_ws, 2 * (size_t)e->cmax * sizeof(double));
+    size_t floats = 0;
+    for (auto& p : e->params) floats += (size_t)p.size;
+    get(&e->stage, floats * sizeof(float));
+    return rc;
+}
+
+// Raw parameters (DEVICE pointers) -> every packed buffer of the engine, queued on `st`: per layer the BatchNorm fold, then
+// one packer per form the layer has; the heads (two 1x1 conv_act, fix_gamma default, folded into one [6][C] matrix) and the
+// FullyConnected layers last.  fold_ws is reused from layer to layer: the stream orders its users.
+int pack_all(apz_engine* e, const ParamPtrs& P, hipStream_t st) {
+    double* scale = e->fold_ws;
+    double* shift = e->fold_ws + e->cmax;
+    auto fold = [&](const std::string& conv, const std::string& bn, const std::string& mean_sfx, const std::string& var_sfx,
+                    bool fix_gamma, int cout, float* bias_out) {
+        hipLaunchKernelGGL(apz::fold_bn_kernel, dim3((cout + 63) / 64), dim3(64), 0, st, P.at(conv + "_bias"),
+                           fix_gamma ? (const float*)nullptr : P.at(bn + "_gamma"), P.at(bn + "_beta"), P.at(bn + mean_sfx),
+                           P.at(bn + var_sfx), scale, shift, bias_out, cout, (double)BN_EPS);
+    };
+    for (auto& L : e->convs) {
+        fold(L.name, L.bn, L.mean_sfx, L.var_sfx, L.fix_gamma, L.cout, L.bias);
+        const float* w = P.at(L.name + "_weight");   // [cout][cin][3][3]
+        const int n4 = L.cin_pad / 4, ncot = L.cout / 16;
+        const int total = ncot * n4 * 9 * 64;
+        const dim3 direct_grid(std::min((total + 255) / 256, 2048));
+        hipLaunchKernelGGL(apz::pack_direct_kernel, direct_grid, dim3(256), 0, st, w, scale, L.wpk, L.cin, n4, ncot,
+                           (int)(L.upk2 != nullptr));
+        if (L.upk2)
+            hipLaunchKernelGGL(apz::pack_wino_folded_kernel, dim3(128 * 128 / 256), dim3(256), 0, st, w, scale, L.upk2, L.upk3s);
+        if (L.upk3b)
+            hipLaunchKernelGGL(apz::pack_wino3b_folded_kernel, dim3(128 * 128 / 256), dim3(256), 0, st, w, scale,
+                               (unsigned short*)L.upk3b);
+        if (L.upk3h) {
+            if (e->f16x2_k8)
+                hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H>, dim3(128), dim3(128), 0, st, w, scale, shift,
+                                   (unsigned short*)L.upk3h, L.bias3h);
+            else
+                hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H16>, dim3(128), dim3(128), 0, st, w, scale, shift,
+                                   (unsigned short*)L.upk3h, L.bias3h);
+        }
+        if (L.wpk12)
+            hipLaunchKernelGGL(apz::pack_direct_kernel, direct_grid, dim3(256), 0, st, w, scale, L.wpk12, L.cin, n4, ncot, 1);
+        if (L.wpk8h)
+            hipLaunchKernelGGL(apz::pack_conv8h_kernel, dim3(L.cout), dim3(256), 0, st, w, scale, shift, (unsigned short*)L.wpk8h,
+                               L.bias8h, L.cin, L.cout);
+        HIP_TRY(hipGetLastError());
+    }
+    const int C = e->clast, hw = e->hw;
+    fold("conv3_1_1", "conv3_1_1", "_mean", "_var", true, 4, nullptr);
+    hipLaunchKernelGGL(apz::pack_head_conv_kernel, dim3((4 * C + 255) / 256), dim3(256), 0, st, P.at("conv3_1_1_weight"), scale,
+                       shift, e->w6, e->b6, 4, 0, C);
+    fold("conv3_2_1", "conv3_2_1", "_mean", "_var", true, 2, nullptr);
+    hipLaunchKernelGGL(apz::pack_head_conv_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, st, P.at("conv3_2_1_weight"), scale,
+                       shift, e->w6, e->b6, 2, 4, C);
+    const int ntile = (hw + 15) / 16, KG = (hw + 7) / 8;
+    hipLaunchKernelGGL(apz::pack_fc_kernel, dim3(std::min((ntile * KG * 512 + 255) / 256, 2048)), dim3(256), 0, st,
+                       P.at("fc_3_1_1_weight"), e->wfc_pk, hw, ntile, KG);
+    HIP_TRY(hipGetLastError());
+    if (e->wfc_raw)     // head8_kernel reads the policy FullyConnected weight as stored
+        HIP_TRY(hipMemcpyAsync(e->wfc_raw, P.at("fc_3_1_1_weight"), (size_t)hw * 4 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->bfc, P.at("fc_3_1_1_bias"), hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->wv, P.at("fc_3_2_1_weight"), 2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->bv, P.at("fc_3_2_1_bias"), sizeof(float), hipMemcpyDeviceToDevice, st));
+    return APZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1118,7 +1239,7 @@ void apz_destroy(apz_engine* e) {
     }
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
-                   e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws,
+                   e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws, e->stage,
                    e->wfc_raw, e->amax_dev, e->gather_entries, e->fplanes};
     for (void* p : dev)
         if (p) hipFree(p);
@@ -1253,176 +1374,24 @@ int apz_load_weights(apz_engine* e, const char* const* names, const float* const
     if (!e || !names || !ptrs || !sizes) return fail(APZ_E_ARG, "null argument");
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
-    std::map<std::string, const float*> P;
-    std::map<std::string, int64_t> S;
-    for (int i = 0; i < n; i++) {
-        P[names[i]] = ptrs[i];
-        S[names[i]] = sizes[i];
-    }
-    for (auto& p : e->params) {
-        auto it = S.find(p.name);
-        if (it == S.end()) return fail(APZ_E_ARG, "missing parameter " + p.name);
-        if (it->second != p.size)
-            return fail(APZ_E_ARG, "parameter " + p.name + " has " + std::to_string(it->second) + " elements, expected " +
-                                       std::to_string(p.size));
-    }
+    ParamPtrs host, dev;
+    if (int rc = check_param_table(e, names, (const void* const*)ptrs, sizes, n, host)) return rc;
+    // drained: no forward reads the weights any more, and a device-side refresh on another stream (which the engine's
+    // stream was ordered behind) is through with fold_ws
     HIP_TRY(hipStreamSynchronize(e->stream));
-    drop_forward_graphs(e);              // (weight buffers may move)
-    std::vector<double> scale, shift;
-    for (auto& L : e->convs) {
-        fold_bn(P, L.name, L.bn, L.mean_sfx, L.var_sfx, L.fix_gamma, L.cout, scale, shift);
-        const float* w = P.at(L.name + "_weight");   // [cout][cin][3][3]
-        const int n4 = L.cin_pad / 4, ncot = L.cout / 16;
-        // trunk15_ring_kernel layers: [cot][c4][lane][12] (three 16-byte loads per lane and ci4 step);
-        // everything else: [cot][c4][tap][lane]
-        const bool x4 = e->ring && &L != &e->convs[0];
-        std::vector<float> pk((size_t)ncot * n4 * 64 * (x4 ? 12 : 9), 0.f), bias(L.cout);
-        for (int cot = 0; cot < ncot; cot++)
-            for (int c4 = 0; c4 < n4; c4++)
-                for (int tap = 0; tap < 9; tap++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int co = cot * 16 + (lane & 15), ci = c4 * 4 + (lane >> 4);
-                        float v = 0.f;
-                        if (ci < L.cin) v = (float)((double)w[((size_t)co * L.cin + ci) * 9 + tap] * scale[co]);
-                        if (x4)
-                            pk[(((size_t)cot * n4 + c4) * 64 + lane) * 12 + tap] = v;
-                        else
-                            pk[(((size_t)cot * n4 + c4) * 9 + tap) * 64 + lane] = v;
-                    }
-        for (int o = 0; o < L.cout; o++) bias[o] = (float)shift[o];
-        int rc = upload(&L.wpk, pk);
-        if (rc) return rc;
-        rc = upload(&L.bias, bias);
-        if (rc) return rc;
-        if (e->small8) {                // conv8_kernel: the nine taps of a lane side by side, [cot][c4][lane][12]
-            std::vector<float> pk12((size_t)ncot * n4 * 64 * 12, 0.f);
-            for (int cot = 0; cot < ncot; cot++)
-                for (int c4 = 0; c4 < n4; c4++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int co = cot * 16 + (lane & 15), ci = c4 * 4 + (lane >> 4);
-                        if (ci >= L.cin) continue;
-                        for (int tap = 0; tap < 9; tap++)
-                            pk12[(((size_t)cot * n4 + c4) * 64 + lane) * 12 + tap] =
-                                (float)((double)w[((size_t)co * L.cin + ci) * 9 + tap] * scale[co]);
-                    }
-            rc = upload(&L.wpk12, pk12);
-            if (rc) return rc;
-            if (e->trunk_arith == APZ_ARITH_F16X2 && apz::Conv8H::supports(L.cin, L.cout)) {
-                // the same folded weights, per output channel times a power of two, as two fp16 terms: conv8_split.h
-                std::vector<uint16_t> pkh;
-                std::vector<float> b8;
-                apz::conv8h_pack_host(w, scale.data(), shift.data(), L.cin, L.cout, pkh, b8);
-                if (!L.wpk8h) HIP_TRY(hipMalloc(&L.wpk8h, apz::Conv8H::pk_bytes(L.cin, L.cout)));
-                HIP_TRY(hipMemcpy(L.wpk8h, pkh.data(), apz::Conv8H::pk_bytes(L.cin, L.cout), hipMemcpyHostToDevice));
-                rc = upload(&L.bias8h, b8);
-                if (rc) return rc;
-            }
-        }
-        if (x4) {
-            // F(4x4,3x3) Winograd weights U[pos = 6i+k][co][ci] = (G g G^T)[i][k] of the BN-folded kernel g, in double,
-            // rounded once; packed [cot 8][row half 2][c4 32][lane 64][20] (wino_common.h)
-            static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6},
-                                           {-1.0 / 6, 1.0 / 6, -1.0 / 6}, {1.0 / 24, 1.0 / 12, 1.0 / 6},
-                                           {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-            std::vector<float> up2(apz::WinoPack::UPK_FLOATS, 0.f), up3s(apz::WinoPackSmall::UPK_FLOATS, 0.f);
-            for (int co = 0; co < 128; co++)
-                for (int ci = 0; ci < 128; ci++) {
-                    double g[3][3], t[6][3];
-                    for (int a = 0; a < 3; a++)
-                        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-                    for (int i = 0; i < 6; i++)
-                        for (int b = 0; b < 3; b++) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-                    const int cot = co >> 4, jj = co & 15, qq = ci & 3, c4 = ci >> 2;
-                    for (int i = 0; i < 6; i++)
-                        for (int k = 0; k < 6; k++) {
-                            const double u = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
-                            const int half = i / 3;
-                            up2[((((size_t)cot * 2 + half) * 32 + c4) * 64 + (qq * 16 + jj)) * 20 + (i - 3 * half) * 6 + k] = (float)u;
-                            up3s[apz::WinoPackSmall::index(co, ci, 6 * i + k)] = (float)u;
-                        }
-                }
-            rc = upload(&L.upk2, up2);
-            if (rc) return rc;
-            rc = upload(&L.upk3s, up3s);
-            if (rc) return rc;
-            if (e->trunk_arith == APZ_ARITH_BF16X3) {
-                // the same U as three bf16 terms (round to nearest even, the remainder taken in double): trunk15_wino3b.h
-                std::vector<uint16_t> ub;
-                apz::wino3b_pack_host(
-                    [&](int co, int ci, int pos) {
-                        double g[3][3], t[3];
-                        for (int a = 0; a < 3; a++)
-                            for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-                        const int i = pos / 6, k = pos % 6;
-                        for (int b = 0; b < 3; b++) t[b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-                        return t[0] * G[k][0] + t[1] * G[k][1] + t[2] * G[k][2];
-                    },
-                    ub);
-                if (!L.upk3b) HIP_TRY(hipMalloc(&L.upk3b, apz::Wino3B::UPK_BYTES));
-                HIP_TRY(hipMemcpy(L.upk3b, ub.data(), apz::Wino3B::UPK_BYTES, hipMemcpyHostToDevice));
-            }
-            if (e->trunk_arith == APZ_ARITH_F16X2) {
-                // the same U, per output channel times a power of two, as two fp16 terms: trunk15_wino3h.h
-                std::vector<uint16_t> uh;
-                std::vector<float> b3(apz::Wino3H::BIAS_FLOATS);
-                for (int o = 0; o < 128; o++) b3[o] = (float)shift[o];
-                auto u_of = [&](int co, int ci, int pos) {
-                    double g[3][3], t[3];
-                    for (int a = 0; a < 3; a++)
-                        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-                    const int i = pos / 6, k = pos % 6;
-                    for (int b = 0; b < 3; b++) t[b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-                    return t[0] * G[k][0] + t[1] * G[k][1] + t[2] * G[k][2];
-                };
-                static_assert(apz::Wino3H16::UPK_BYTES == apz::Wino3H::UPK_BYTES, "both f16x2 kernels share the layer's upk3h buffer");
-                if (e->f16x2_k8) apz::wino3h_pack_host<apz::Wino3H>(u_of, uh, b3.data() + 128);
-                else apz::wino3h_pack_host<apz::Wino3H16>(u_of, uh, b3.data() + 128);
-                if (!L.upk3h) HIP_TRY(hipMalloc(&L.upk3h, apz::Wino3H::UPK_BYTES));
-                HIP_TRY(hipMemcpy(L.upk3h, uh.data(), apz::Wino3H::UPK_BYTES, hipMemcpyHostToDevice));
-                rc = upload(&L.bias3h, b3);
-                if (rc) return rc;
-            }
-        }
+    drop_forward_graphs(e);
+    if (!e->loaded)
+        if (int rc = alloc_packed(e)) return rc;
+    // the host tensors go to the staging buffer (allocated once: no hipMalloc / hipFree per load, which would stall every
+    // engine on the device), and from there through the kernels every refresh runs
+    size_t off = 0;
+    for (auto& p : e->params) {
+        HIP_TRY(hipMemcpyAsync(e->stage + off, host.at(p.name), (size_t)p.size * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        dev[p.name] = e->stage + off;
+        off += (size_t)p.size;
     }
-    // heads: two 1x1 conv_act (fix_gamma default) folded into one [6][C] matrix
-    {
-        const int C = e->clast, hw = e->hw;
-        std::vector<float> w6((size_t)6 * C), b6(6);
-        fold_bn(P, "conv3_1_1", "conv3_1_1", "_mean", "_var", true, 4, scale, shift);
-        const float* wp = P.at("conv3_1_1_weight");
-        for (int o = 0; o < 4; o++) {
-            for (int c = 0; c < C; c++) w6[(size_t)o * C + c] = (float)((double)wp[o * C + c] * scale[o]);
-            b6[o] = (float)shift[o];
-        }
-        fold_bn(P, "conv3_2_1", "conv3_2_1", "_mean", "_var", true, 2, scale, shift);
-        const float* wq = P.at("conv3_2_1_weight");
-        for (int o = 0; o < 2; o++) {
-            for (int c = 0; c < C; c++) w6[(size_t)(4 + o) * C + c] = (float)((double)wq[o * C + c] * scale[o]);
-            b6[4 + o] = (float)shift[o];
-        }
-        const float* wfc = P.at("fc_3_1_1_weight");   // [hw][4*hw]
-        const int K = 4 * hw, KS = hw, ntile = (hw + 15) / 16;
-        // head_fc_kernel: [tile][trip of 8 k-steps][lane][8], zero past KS and past hw outputs
-        const int KG = (KS + 7) / 8;
-        std::vector<float> pk((size_t)ntile * KG * 64 * 8, 0.f);
-        for (int nt = 0; nt < ntile; nt++)
-            for (int s = 0; s < KS; s++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int o = nt * 16 + (lane & 15), k = 4 * s + (lane >> 4);
-                    if (o < hw) pk[((((size_t)nt * KG + (s >> 3)) * 64 + lane) << 3) + (s & 7)] = wfc[(size_t)o * K + k];
-                }
-        std::vector<float> bfc(P.at("fc_3_1_1_bias"), P.at("fc_3_1_1_bias") + hw);
-        std::vector<float> wv(P.at("fc_3_2_1_weight"), P.at("fc_3_2_1_weight") + 2 * hw);
-        std::vector<float> bv(P.at("fc_3_2_1_bias"), P.at("fc_3_2_1_bias") + 1);
-        int rc;
-        if (e->small8) {
-            std::vector<float> raw(wfc, wfc + (size_t)hw * K);
-            if ((rc = upload(&e->wfc_raw, raw))) return rc;
-        }
-        if ((rc = upload(&e->w6, w6)) || (rc = upload(&e->b6, b6)) || (rc = upload(&e->wfc_pk, pk)) ||
-            (rc = upload(&e->bfc, bfc)) || (rc = upload(&e->wv, wv)) || (rc = upload(&e->bv, bv)))
-            return rc;
-    }
+    if (int rc = pack_all(e, dev, e->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
     e->loaded = true;
     // the activation exponents are engine state and survive the load; the new 1 / S may only narrow their range
     for (auto& L : e->convs)
@@ -1698,8 +1667,9 @@ struct StreamScope {      // run the engine's launch helpers on a caller-supplie
 };
 }  // namespace
 
-// The same as apz_load_weights for tensors that already live in DEVICE memory (the trainer's): folding and packing run
-// as kernels on `stream` (APZ_ENGINE_STREAM: the engine's own), and the engine's stream waits for them.
+// The same as apz_load_weights for tensors that already live in DEVICE memory (the trainer's): pack_all runs on `stream`
+// (APZ_ENGINE_STREAM: the engine's own) without a host synchronisation, and the engine's stream waits for it.  The buffers
+// are those of the engine's first apz_load_weights.
 int apz_load_weights_dev(apz_engine* e, const char* const* names, const void* const* dev_ptrs, const int64_t* sizes, int n,
                          void* stream) {
     if (!e || !names || !dev_ptrs || !sizes) return fail(APZ_E_ARG, "null argument");
@@ -1707,108 +1677,30 @@ int apz_load_weights_dev(apz_engine* e, const char* const* names, const void* co
     drop_forward_graphs(e);
     HIP_TRY(hipSetDevice(e->cfg.device));
     if (!e->loaded) return fail(APZ_E_STATE, "apz_load_weights_dev refreshes a loaded engine: call apz_load_weights first");
-    std::map<std::string, const float*> P;
-    std::map<std::string, int64_t> S;
-    for (int i = 0; i < n; i++) {
-        P[names[i]] = (const float*)dev_ptrs[i];
-        S[names[i]] = sizes[i];
-    }
-    for (auto& p : e->params) {
-        auto it = S.find(p.name);
-        if (it == S.end()) return fail(APZ_E_ARG, "missing parameter " + p.name);
-        if (it->second != p.size)
-            return fail(APZ_E_ARG, "parameter " + p.name + " has " + std::to_string(it->second) + " elements, expected " +
-                                       std::to_string(p.size));
-    }
-    // everything that can fail without having touched the weights comes first: shapes, scratch
-    for (auto& L : e->convs)
-        if (L.cout > 256) return fail(APZ_E_UNSUPPORTED, "load_weights_dev: more than 256 channels");
-    if (!e->fold_ws) HIP_TRY(hipMalloc((void**)&e->fold_ws, 2 * 256 * sizeof(double)));
+    ParamPtrs P;
+    if (int rc = check_param_table(e, names, dev_ptrs, sizes, n, P)) return rc;
     hipStream_t engine_stream = e->stream;
-    {
-        StreamScope sc(e, stream);
-        hipStream_t st = e->stream;
-        if (st != engine_stream) {      // forwards already queued on the engine's stream still read the old weights
+    StreamScope sc(e, stream);
+    hipStream_t st = e->stream;
+    if (st != engine_stream) {      // forwards already queued on the engine's stream still read the old weights
+        hipEvent_t ev = get_event(e);
+        HIP_TRY(hipEventRecord(ev, engine_stream));
+        HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+        e->free_events.push_back(ev);
+    }
+    // From here on packing kernels are queued on `st`: whatever happens below, the engine's stream must end up
+    // ordered behind them (a half-refreshed evaluator that ALSO races the packing kernels would be worse).
+    struct Closing {
+        apz_engine* e;
+        hipStream_t st, engine_stream;
+        ~Closing() {
+            if (st == engine_stream) return;
             hipEvent_t ev = get_event(e);
-            HIP_TRY(hipEventRecord(ev, engine_stream));
-            HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+            if (hipEventRecord(ev, st) == hipSuccess) hipStreamWaitEvent(engine_stream, ev, 0);
             e->free_events.push_back(ev);
         }
-        // From here on packing kernels are queued on `st`: whatever happens below, the engine's stream must end up
-        // ordered behind them (a half-refreshed evaluator that ALSO races the packing kernels would be worse).
-        struct Closing {
-            apz_engine* e;
-            hipStream_t st, engine_stream;
-            ~Closing() {
-                if (st == engine_stream) return;
-                hipEvent_t ev = get_event(e);
-                if (hipEventRecord(ev, st) == hipSuccess) hipStreamWaitEvent(engine_stream, ev, 0);
-                e->free_events.push_back(ev);
-            }
-        } closing{e, st, engine_stream};
-        double* scale = e->fold_ws;
-        double* shift = e->fold_ws + 256;
-        auto fold = [&](const std::string& conv, const std::string& bn, const std::string& mean_sfx, const std::string& var_sfx,
-                        bool fix_gamma, int cout, float* bias_out) {
-            hipLaunchKernelGGL(apz::fold_bn_kernel, dim3((cout + 63) / 64), dim3(64), 0, st, P.at(conv + "_bias"),
-                               fix_gamma ? (const float*)nullptr : P.at(bn + "_gamma"), P.at(bn + "_beta"), P.at(bn + mean_sfx),
-                               P.at(bn + var_sfx), scale, shift, bias_out, cout, (double)BN_EPS);
-        };
-        for (auto& L : e->convs) {
-            fold(L.name, L.bn, L.mean_sfx, L.var_sfx, L.fix_gamma, L.cout, L.bias);
-            const float* w = P.at(L.name + "_weight");
-            const int n4 = L.cin_pad / 4, ncot = L.cout / 16;
-            const bool x4 = e->ring && &L != &e->convs[0];
-            const int total = ncot * n4 * 9 * 64;
-            hipLaunchKernelGGL(apz::pack_direct_kernel, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, w, scale, L.wpk,
-                               L.cin, n4, ncot, (int)x4);
-            if (x4)
-                hipLaunchKernelGGL(apz::pack_wino_folded_kernel, dim3(128 * 128 / 256), dim3(256), 0, st, w, scale, L.upk2, L.upk3s);
-            if (x4 && e->trunk_arith == APZ_ARITH_BF16X3) {
-                if (!L.upk3b) HIP_TRY(hipMalloc(&L.upk3b, apz::Wino3B::UPK_BYTES));
-                hipLaunchKernelGGL(apz::pack_wino3b_folded_kernel, dim3(128 * 128 / 256), dim3(256), 0, st, w, scale,
-                                   (unsigned short*)L.upk3b);
-            }
-            if (x4 && e->trunk_arith == APZ_ARITH_F16X2) {
-                if (!L.upk3h) HIP_TRY(hipMalloc(&L.upk3h, apz::Wino3H::UPK_BYTES));
-                if (!L.bias3h) HIP_TRY(hipMalloc(&L.bias3h, apz::Wino3H::BIAS_FLOATS * sizeof(float)));
-                if (e->f16x2_k8)
-                    hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H>, dim3(128), dim3(128), 0, st, w, scale, shift,
-                                       (unsigned short*)L.upk3h, L.bias3h);
-                else
-                    hipLaunchKernelGGL(apz::pack_wino3h_folded_kernel<apz::Wino3H16>, dim3(128), dim3(128), 0, st, w, scale, shift,
-                                       (unsigned short*)L.upk3h, L.bias3h);
-            }
-            if (e->small8 && L.wpk12)
-                hipLaunchKernelGGL(apz::pack_direct_kernel, dim3(std::min((total + 255) / 256, 2048)), dim3(256), 0, st, w, scale,
-                                   L.wpk12, L.cin, n4, ncot, 1);
-            if (e->small8 && e->trunk_arith == APZ_ARITH_F16X2 && apz::Conv8H::supports(L.cin, L.cout)) {
-                if (!L.wpk8h) HIP_TRY(hipMalloc(&L.wpk8h, apz::Conv8H::pk_bytes(L.cin, L.cout)));
-                if (!L.bias8h) HIP_TRY(hipMalloc(&L.bias8h, 2 * (size_t)L.cout * sizeof(float)));
-                hipLaunchKernelGGL(apz::pack_conv8h_kernel, dim3(L.cout), dim3(256), 0, st, w, scale, shift, (unsigned short*)L.wpk8h,
-                                   L.bias8h, L.cin, L.cout);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        const int C = e->clast, hw = e->hw;
-        fold("conv3_1_1", "conv3_1_1", "_mean", "_var", true, 4, nullptr);
-        hipLaunchKernelGGL(apz::pack_head_conv_kernel, dim3((4 * C + 255) / 256), dim3(256), 0, st, P.at("conv3_1_1_weight"), scale,
-                           shift, e->w6, e->b6, 4, 0, C);
-        fold("conv3_2_1", "conv3_2_1", "_mean", "_var", true, 2, nullptr);
-        hipLaunchKernelGGL(apz::pack_head_conv_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, st, P.at("conv3_2_1_weight"), scale,
-                           shift, e->w6, e->b6, 2, 4, C);
-        const int ntile = (hw + 15) / 16, KG = (hw + 7) / 8;
-        hipLaunchKernelGGL(apz::pack_fc_kernel, dim3(std::min((ntile * KG * 512 + 255) / 256, 2048)), dim3(256), 0, st,
-                           P.at("fc_3_1_1_weight"), e->wfc_pk, hw, ntile, KG);
-        HIP_TRY(hipGetLastError());
-        if (e->small8 && e->wfc_raw)
-            HIP_TRY(hipMemcpyAsync(e->wfc_raw, P.at("fc_3_1_1_weight"), (size_t)hw * 4 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(e->bfc, P.at("fc_3_1_1_bias"), hw * sizeof(float), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(e->wv, P.at("fc_3_2_1_weight"), 2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(e->bv, P.at("fc_3_2_1_bias"), sizeof(float), hipMemcpyDeviceToDevice, st));
-        // (`closing` orders the engine's stream behind all of the above: forwards queued from now on see the new weights)
-    }
-    return APZ_OK;
+    } closing{e, st, engine_stream};
+    return pack_all(e, P, st);   // (`closing` orders the engine's stream behind it: forwards queued from now on see the new weights)
 }
 
 int apz_conv3x3_pack(apz_engine* e, const void* w_dev, int cin, int cout, int transpose_flip, void* wpk_dev,

@@ -48,26 +48,9 @@ struct Conv8H {
     static bool supports(int cin, int cout) { return cin % 64 == 0 && cout % 16 == 0; }
 };
 
-// Host packing: w [cout][cin][9] fp32, scale [cout] (folded BatchNorm) -> the kernel's layout + bias8h = [cout bias][cout 1/S]
-inline void conv8h_pack_host(const float* w, const double* scale, const double* shift, int cin, int cout, std::vector<uint16_t>& out,
-                             std::vector<float>& bias8h) {
-    out.assign(Conv8H::pk_bytes(cin, cout) / 2, 0);
-    bias8h.assign(2 * (size_t)cout, 0.f);
-    for (int co = 0; co < cout; co++) {
-        double m = 0;
-        for (int i = 0; i < cin * 9; i++) m = std::max(m, std::fabs((double)w[(size_t)co * cin * 9 + i] * scale[co]));
-        const float S = f16x2_scale_for(m);
-        bias8h[co] = (float)shift[co];
-        bias8h[cout + co] = 1.f / S;
-        for (int ci = 0; ci < cin; ci++)
-            for (int tap = 0; tap < 9; tap++)
-                f16x2_split((double)w[((size_t)co * cin + ci) * 9 + tap] * scale[co] * (double)S,
-                            out[Conv8H::pk_index(co, ci, tap, 0, cin)], out[Conv8H::pk_index(co, ci, tap, 1, cin)]);
-    }
-}
-
-// The same on the device (the trainer's refresh path): one workgroup of 256 threads per output channel, a thread walks the
-// input channels tid, tid + 256, ... twice (the channel's maximum first, then the two terms).
+// Packing: w [cout][cin][9] fp32, scale / shift [cout] (folded BatchNorm, weights_pack.h) -> the kernel's layout + bias8h =
+// [cout bias][cout 1/S], S = f16x2_scale_for(max |w scale| of the channel).  One workgroup of 256 threads per output channel,
+// a thread walks the input channels tid, tid + 256, ... twice (the channel's maximum first, then the two terms).
 __global__ void pack_conv8h_kernel(const float* __restrict__ w, const double* __restrict__ scale, const double* __restrict__ shift,
                                    unsigned short* __restrict__ pk, float* __restrict__ bias8h, int cin, int cout) {
     const int co = blockIdx.x, tid = threadIdx.x;

@@ -7,8 +7,8 @@
 // bytes, a third fewer LDS fragment reads and half the split's vector instructions (round 6; profiles/r06_wino3h.md).
 //
 // Range.  fp16 holds 6.1e-5 .. 65504 in normal numbers, so both operands are placed by powers of two:
-//   * weights: U = G g G^T of output channel co is multiplied by S[co] = 2^k chosen on the host / by the device packer
-//     (f16x2_scale_for) so that max |U S| sits in [2^13, 2^14); the epilogue multiplies by 1 / S[co] (exact) inside the bias FMA.
+//   * weights: U = G g G^T of output channel co is multiplied by S[co] = 2^k chosen by the packer (weights_pack.h,
+//     f16x2_scale_for) so that max |U S| sits in [2^13, 2^14); the epilogue multiplies by 1 / S[co] (exact) inside the bias FMA.
 //   * activations: V = B^T d B is NOT scaled.  |V| <= 100 max|d|: post-ReLU activations up to 655 are representable;
 //     values below 2^-3 keep an absolute error of 2^-25.  An input that does overflow gives +-inf / NaN in the
 //     accumulators; the epilogue checks every pre-ReLU value (a NaN would otherwise be clamped to 0 silently) and raises

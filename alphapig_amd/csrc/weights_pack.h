@@ -1,8 +1,10 @@
-// BatchNorm folding and weight packing ON THE DEVICE: the same maps apz_load_weights applies on the host (double
-// arithmetic, rounded once), for weights that already live in device memory -- the trainer's tensors after an
-// optimiser step (policy_value_net_mxnet.py:295-297: the reference copies the new parameters into its predict
-// modules after every step).  The host path costs a device -> host copy of every tensor, 16 ms of folding and
-// Winograd packing on one core and the upload; these kernels take a few tens of microseconds.  gfx950.
+// BatchNorm folding and weight packing, the one implementation: every evaluator weight goes through these kernels
+// (double arithmetic, rounded once).  apz_load_weights stages the host tensors in device memory and runs them;
+// apz_load_weights_dev runs them on tensors that already live there -- the trainer's after an optimiser step
+// (policy_value_net_mxnet.py:295-297: the reference copies the new parameters into its predict modules after every
+// step), a few tens of microseconds.  The kernels write the value slots of a layout only: the pad slots (taps 9..11 of
+// the [12] forms, 18..19 of upk2's [20], what WinoPackSmall::index leaves out) are zero from the allocation
+// (apz_engine.hip, alloc_packed).  gfx950.
 #pragma once
 #include "trunk15_wino3b.h"
 #include "trunk15_wino3h16.h"
@@ -41,35 +43,50 @@ __global__ void pack_direct_kernel(const float* __restrict__ w, const double* __
     }
 }
 
-// F(4x4,3x3) Winograd weights of the 128 -> 128 trunk shape, U[6i+k][co][ci] = (G g G^T)[i][k] of the folded kernel, in
-// double, rounded once, in trunk15_wino3.h's layout (wino_common.h: [cot 8][row half 2][c4 32][lane 64][20]).  One thread
-// per (co, ci).
+// the 3x3 kernel (co, ci) of the 128 -> 128 trunk shape with the BatchNorm scale folded in
+__device__ __forceinline__ void folded_kernel(const float* __restrict__ w, const double* __restrict__ scale, int co, int ci,
+                                              double (&g)[3][3]) {
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
+}
+
+// F(4x4,3x3) Winograd weights of one 3x3 kernel g: u[6i+k] = (G g G^T)[i][k] in double (t = G g first, then t G^T) -- the
+// one copy every packer below rounds from
+__device__ __forceinline__ void wino_u_of(const double (&g)[3][3], double (&u)[36]) {
+    const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    double t[6][3];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int k = 0; k < 6; k++) u[6 * i + k] = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
+}
+
+// U of the folded 128 -> 128 trunk layer, rounded once, in trunk15_wino3.h's layout (wino_common.h: [cot 8][row half 2]
+// [c4 32][lane 64][20]) and, up3s != NULL, in trunk15_wino3s.h's (WinoPackSmall).  One thread per (co, ci).
 __global__ void pack_wino_folded_kernel(const float* __restrict__ w, const double* __restrict__ scale, float* __restrict__ up2,
                                         float* __restrict__ up3s) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= 128 * 128) return;
     const int co = idx >> 7, ci = idx & 127;
-    const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    double g[3][3], t[6][3];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
+    double g[3][3], u[36];
+    folded_kernel(w, scale, co, ci, g);
+    wino_u_of(g, u);
     const int cot = co >> 4, jj = co & 15;
     const int qq = ci & 3, c4 = ci >> 2;
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-            const double u = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
             const int pass = i / 3;
-            up2[((((size_t)cot * 2 + pass) * 32 + c4) * 64 + (qq * 16 + jj)) * 20 + (i - 3 * pass) * 6 + k] = (float)u;
-            if (up3s) up3s[WinoPackSmall::index(co, ci, 6 * i + k)] = (float)u;
+            up2[((((size_t)cot * 2 + pass) * 32 + c4) * 64 + (qq * 16 + jj)) * 20 + (i - 3 * pass) * 6 + k] = (float)u[6 * i + k];
+            if (up3s) up3s[WinoPackSmall::index(co, ci, 6 * i + k)] = (float)u[6 * i + k];
         }
 }
 
@@ -78,31 +95,21 @@ __global__ void pack_wino3b_folded_kernel(const float* __restrict__ w, const dou
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= 128 * 128) return;
     const int co = idx >> 7, ci = idx & 127;
-    const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    double g[3][3], t[6][3];
+    double g[3][3], u[36];
+    folded_kernel(w, scale, co, ci, g);
+    wino_u_of(g, u);
 #pragma unroll
-    for (int a = 0; a < 3; a++)
+    for (int pos = 0; pos < 36; pos++) {
+        double rem = u[pos];
 #pragma unroll
-        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            double rem = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
-#pragma unroll
-            for (int term = 0; term < 3; term++) {
-                unsigned u = __builtin_bit_cast(unsigned, (float)rem);
-                if ((u & 0x7f800000u) != 0x7f800000u) u += 0x7fffu + ((u >> 16) & 1u);
-                u &= 0xffff0000u;
-                up[Wino3B::upk_offset(co, ci, 6 * i + k, term) / 2] = (unsigned short)(u >> 16);
-                rem -= (double)__builtin_bit_cast(float, u);
-            }
+        for (int term = 0; term < 3; term++) {
+            unsigned b = __builtin_bit_cast(unsigned, (float)rem);
+            if ((b & 0x7f800000u) != 0x7f800000u) b += 0x7fffu + ((b >> 16) & 1u);
+            b &= 0xffff0000u;
+            up[Wino3B::upk_offset(co, ci, pos, term) / 2] = (unsigned short)(b >> 16);
+            rem -= (double)__builtin_bit_cast(float, b);
         }
+    }
 }
 
 // The U of kernel g (one output channel co, thread = input channel ci of a 128-thread workgroup) for the fp16 x 2 kernels:
@@ -111,21 +118,11 @@ __global__ void pack_wino3b_folded_kernel(const float* __restrict__ w, const dou
 template <class L>
 __device__ __forceinline__ void pack_wino3h_channel(const double (&g)[3][3], int co, int ci, double bias, unsigned short* __restrict__ up,
                                                     float* __restrict__ bias3h) {
-    const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    double t[6][3], u[36];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
+    double u[36];
+    wino_u_of(g, u);
     double m = 0.0;
 #pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            u[6 * i + k] = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
-            m = fmax(m, fabs(u[6 * i + k]));
-        }
+    for (int pos = 0; pos < 36; pos++) m = fmax(m, fabs(u[pos]));
     __shared__ double red[128];
     red[ci] = m;
     __syncthreads();
@@ -154,10 +151,7 @@ __global__ void pack_wino3h_folded_kernel(const float* __restrict__ w, const dou
                                           unsigned short* __restrict__ up, float* __restrict__ bias3h) {
     const int co = blockIdx.x, ci = threadIdx.x;
     double g[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) g[a][b] = (double)w[((size_t)co * 128 + ci) * 9 + a * 3 + b] * scale[co];
+    folded_kernel(w, scale, co, ci, g);
     pack_wino3h_channel<L>(g, co, ci, shift[co], up, bias3h);
 }
 

@@ -80,7 +80,11 @@ const char *apz_param_name(apz_engine *e, int i);
 int64_t apz_param_size(apz_engine *e, int i);
 /* Load RAW parameters (conv weight/bias, BN gamma/beta/moving stats, FC weight/bias) from
  * host float32 arrays; every table entry must be supplied.  BatchNorm (eps 1e-3,
- * fix_gamma semantics per layer) is folded into conv weights/biases inside. */
+ * fix_gamma semantics per layer) is folded into conv weights/biases inside.
+ * Synchronous: drains the engine's stream, copies the tensors into an engine-owned staging buffer in device memory, folds
+ * and packs them there with the kernels apz_load_weights_dev runs (csrc/weights_pack.h: one implementation, the same
+ * bits from both), and returns when the weights are in place.  The first call allocates the packed buffers and the
+ * staging buffer for the engine's configuration (apz_set_trunk_arith comes before it); later calls allocate nothing. */
 int apz_load_weights(apz_engine *e, const char *const *names, const float *const *host_ptrs,
                      const int64_t *sizes, int n);
 
@@ -296,9 +300,10 @@ int apz_colsum(apz_engine *e, const void *in_dev, void *out_dev, int rows, int c
  *   apz_add                  y += x (count floats): the meeting point of the trunk and skip gradients
  * conv1x1_bwd: dx gets zero pad cells; accumulate_dx != 0 adds to what dx already holds (second head). */
 /* apz_load_weights for tensors that already live in device memory (policy_value_net_mxnet.py:295-297: after an
- * optimiser step the new parameters go into the predict modules): BatchNorm folding and every packing of
- * apz_load_weights as kernels on `stream`; forwards queued afterwards use the new weights.  Same name / size table as
- * apz_load_weights; the engine must have been loaded once from the host. */
+ * optimiser step the new parameters go into the predict modules): the fold and pack kernels of apz_load_weights,
+ * queued on `stream` without a copy and without a host synchronisation; forwards queued afterwards use the new weights.
+ * Same name / size table, same checks and same resulting bits as apz_load_weights; the engine must have been loaded once
+ * from the host (that call allocates the buffers this one fills). */
 int apz_load_weights_dev(apz_engine *e, const char *const *names, const void *const *dev_ptrs, const int64_t *sizes,
                          int n, void *stream);
 /* Device replay buffer (alphapig_amd/replay.py, csrc/replay.h): the ring keeps what the self-play exchange delivers --

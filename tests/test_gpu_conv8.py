@@ -89,7 +89,8 @@ def test_codes_entry_point_equals_planes_entry_point(c_in, arith):
 def test_device_side_weight_refresh_packs_the_same_bits(arith):
     """apz_load_weights_dev (the trainer's refresh after every step, policy_value_net_mxnet.py:295-297) packs conv8's
     weight layout (f16x2: conv8h's two-term layout and its per-channel scales as well) and head8's FullyConnected matrix
-    with kernels; apz_load_weights does it on the host.  Same weights in, same evaluator out."""
+    with kernels; apz_load_weights runs the same kernels on a staged copy of the host tensors.  Same weights in, same
+    bits out."""
     torch = pytest.importorskip("torch")
     from alphapig_amd.policy_value_net import PolicyValueNet
     prm = weights.init_params("simple", 8, 8, 9, seed=19, style="bench")
@@ -102,8 +103,8 @@ def test_device_side_weight_refresh_packs_the_same_bits(arith):
     dev = {k: torch.tensor(v, device="cuda") for k, v in prm.items()}
     b.load_device_params(dev)
     pb, vb = b.forward_planes(planes)
-    np.testing.assert_allclose(pb, pa, rtol=0, atol=1e-6)       # folding in double on the host vs in double on the device: last-bit effects only
-    np.testing.assert_allclose(vb, va, rtol=0, atol=1e-6)
+    np.testing.assert_array_equal(pb, pa)                       # both loaders fold and pack with the kernels of weights_pack.h
+    np.testing.assert_array_equal(vb, va)
     a.close()
     b.close()
 

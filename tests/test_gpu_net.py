@@ -561,9 +561,10 @@ def test_split_trunk_10_blocks_512_boards_and_launch_shapes(kind, arith):
 @pytest.mark.parametrize("arith", ["f16x2", "bf16x3"])
 def test_split_weights_packed_on_the_device_equal_the_host_pack(arith):
     """The trainer's refresh path (apz_load_weights_dev, policy_value_net_mxnet.py:295-297) packs the split terms of
-    U = G g G^T (two fp16 terms of U S[co] and the per-channel scales / three bf16 terms) with a kernel; the constructor
-    packs them on the host.  Same double arithmetic, same rounding: the two evaluators give identical bits -- also after
-    the weights change."""
+    U = G g G^T (two fp16 terms of U S[co] and the per-channel scales / three bf16 terms) with the kernels of
+    weights_pack.h from the trainer's device tensors; the constructor and set_params (apz_load_weights) stage the host
+    tensors on the device and run the same kernels.  One packing implementation: the two evaluators give identical bits
+    -- also after the weights change."""
     torch = pytest.importorskip("torch")
     from alphapig_amd.policy_value_net import PolicyValueNet
     prm = weights.init_params("resnet", 15, 15, 9, 3, 128, seed=31, style="bench")
@@ -578,7 +579,7 @@ def test_split_weights_packed_on_the_device_equal_the_host_pack(arith):
         np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
     o = net_ref.forward(prm, planes[:16], "resnet", 3, np.float64)
     np.testing.assert_allclose(a[0][:16], o[0], rtol=0, atol=LOGIT_ATOL)
-    host.set_params(prm2)                                       # and the host path again, on the other weights
+    host.set_params(prm2)                                       # and from host tensors again, on the other weights
     tensors2 = {k: torch.tensor(np.ascontiguousarray(v, dtype=np.float32), device="cuda") for k, v in prm2.items()}
     dev.load_device_params(tensors2)
     for x, y in zip(host.forward_with_logits(planes), dev.forward_with_logits(planes)):
@@ -587,6 +588,30 @@ def test_split_weights_packed_on_the_device_equal_the_host_pack(arith):
         host._ck(host.L.apz_set_trunk_arith(host._h, 0))
     host.close()
     dev.close()
+
+
+@pytest.mark.parametrize("kind,side,blocks,boards", [("resnet", 15, 1, (2, 34)), ("simple", 8, 0, (4,))])
+def test_a_reload_reuses_the_engines_buffers_and_gives_a_fresh_engines_bits(kind, side, blocks, boards):
+    """apz_load_weights allocates the packed buffers (zeroed: the packing kernels never write the pad slots) and its
+    staging buffer at the first load and reuses them afterwards.  set_params(A), (B), (A) on one engine leaves nothing of
+    B behind: logits and values equal those of an engine constructed on A, through the small-batch and the batched
+    kernels (2 and 34 boards at 15x15) and on the 8x8 kernels."""
+    from alphapig_amd.policy_value_net import PolicyValueNet
+    kw = dict(batch_size=64, n_blocks=blocks, n_filter=128, net_kind=kind, trunk_arith="f16x2")
+    prm_a = weights.init_params(kind, side, side, 9, blocks, 128, seed=51, style="bench")
+    prm_b = weights.init_params(kind, side, side, 9, blocks, 128, seed=52, style="bench")
+    _, planes = random_positions(max(boards), side, seed=91)
+    fresh = PolicyValueNet(side, side, model_params=prm_a, **kw)
+    reloaded = PolicyValueNet(side, side, model_params=prm_a, **kw)
+    reloaded.set_params(prm_b)
+    assert not np.array_equal(reloaded.forward_with_logits(planes)[0], fresh.forward_with_logits(planes)[0])
+    reloaded.set_params(prm_a)
+    for n in boards:
+        want, got = fresh.forward_with_logits(planes[:n]), reloaded.forward_with_logits(planes[:n])
+        np.testing.assert_array_equal(got[0], want[0], err_msg="logits, %d boards" % n)
+        np.testing.assert_array_equal(got[3], want[3], err_msg="values, %d boards" % n)
+    fresh.close()
+    reloaded.close()
 
 
 @pytest.mark.gpu

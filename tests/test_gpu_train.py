@@ -576,8 +576,8 @@ def test_policy_update_on_the_hip_trainer():
 @pytest.mark.parametrize("kind,side,blocks,nf", [("resnet", 15, 3, 128), ("simple", 8, 0, 128), ("resnet", 8, 2, 64)])
 def test_device_side_weight_refresh_equals_host_load(kind, side, blocks, nf):
     """apz_load_weights_dev (BatchNorm folding, direct / Winograd / head / FC packing as kernels on the trainer's
-    device tensors) against apz_load_weights from the host: the two evaluators answer alike, and the device-loaded one
-    hands back the same parameter table."""
+    device tensors) against apz_load_weights from the host (the same kernels on a staged copy of the host tensors): the
+    two evaluators answer with the same bits, and the device-loaded one hands back the same parameter table."""
     from alphapig_amd import weights
     from alphapig_amd.policy_value_net import PolicyValueNet
     rs = np.random.RandomState(3)
@@ -592,14 +592,14 @@ def test_device_side_weight_refresh_equals_host_load(kind, side, blocks, nf):
     p_host, v_host = host.policy_value(states)
     p_dev, v_dev = dev.policy_value(states)
     assert np.abs(p_other - p_host).max() > 1e-4                     # the refresh changed something
-    # same double-precision maps; the device code contracts a*b+c into fma, so single results may differ by an ulp
-    np.testing.assert_allclose(p_dev, p_host, rtol=0, atol=2e-7)
-    np.testing.assert_allclose(v_dev, v_host, rtol=0, atol=2e-6)
+    # one fold and pack implementation behind both loaders (built with -ffp-contract=off: no fused multiply-add either)
+    np.testing.assert_array_equal(p_dev, p_host)
+    np.testing.assert_array_equal(v_dev, v_host)
     got = dev.params()
     assert set(got) == set(prm)
     for k in prm:
         np.testing.assert_array_equal(got[k], prm[k].astype(np.float32), err_msg=k)
-    # a missing or mis-sized tensor is refused like on the host path
+    # a missing or mis-sized tensor is refused as apz_load_weights refuses it (one table check)
     bad = dict(tensors)
     bad.pop("fc_3_1_1_bias")
     with pytest.raises(Exception):
