@@ -215,18 +215,16 @@ struct apz_engine {
     // APZ_ARITH_F16X2: trunk15_wino3h_kernel raises a word when an activation left the fp16 range (a non-finite output);
     // the words live in pinned host memory, one per submission slot + one for the synchronous entry points; the entry
     // point that collects a forward's results looks at its word and repeats the forward on the exact-fp32 kernel.
+    // Which word a forward raises, and everything else that holds for one forward only, is its FwdMode: not engine state.
     unsigned* ovf_host = nullptr;            // [APZ_MAX_SLOTS + 1]
     unsigned* ovf_dev = nullptr;             // the same words as the device sees them
-    unsigned* ovf_cur = nullptr;             // (device pointer) the word of the forward being queued
-    bool force_f32 = false;                  // the repeat of an overflowed forward
     // APZ_ARITH_F16X2, batches > 32: trunk15_wino3h16_kernel (16-channel chunks, three products); APZ_F16X2_K8=1 in the
     // environment at engine creation selects its predecessor trunk15_wino3h_kernel instead (A/B measurements)
     bool f16x2_k8 = false;
     long ovf_repeats = 0;                    // forwards repeated so far (apz_trunk_overflows)
     // static activation exponents (apz_set_trunk_act_exponents ...): max |input| of every trunk convolution, measured by
-    // act_absmax_kernel during a calibration forward or the exact repeat of an overflowed one
+    // act_absmax_kernel during a calibration forward or the exact repeat of an overflowed one (FwdMode::measure_max)
     bool act_auto = false;                   // apz_set_act_scale_auto: an overflow lowers the exponents
-    bool measure_max = false;                // run_trunk: measure (set around exact-fp32 forwards only)
     float* amax_dev = nullptr;               // [trunk layer][ActMax::MAX_PARTS] partial maxima
     float* amax_host = nullptr;              // ... pinned copy, valid after the stream synchronisation behind the forward
     int trunk_kernel = APZ_TRUNK_WINOGRAD;   // or APZ_TRUNK_DIRECT (trunk15_ring_kernel): apz_test_select_trunk, tests only
@@ -241,6 +239,25 @@ struct apz_engine {
 };
 
 namespace {
+
+// What holds for ONE forward (or one re-run of the trunk) and for nothing after it: built by the entry point, passed down
+// to the launchers by const reference.  The persistent configuration stays in apz_engine; trunk_route() reads both.
+struct FwdMode {
+    unsigned* ovf = nullptr;     // (device pointer) the overflow word this forward raises; null = not armed
+    bool exact = false;          // exact fp32 whatever trunk_arith: the repeat of an overflowed forward, calibration's measuring pass
+    bool measure_max = false;    // max |x| in front of every trunk convolution (exact forwards only)
+    bool batched = false;        // the batched form at every batch size: calibration's proving pass (or e->no_small_trunk)
+    bool untimed = false;        // no event pairs whatever e->profiling says: the layer bench and the layer read-backs
+};
+
+// The mode of a forward that raises overflow word `idx` (a slot's, or APZ_MAX_SLOTS: the synchronous entry points'); other
+// arithmetics than APZ_ARITH_F16X2 have no words.  Who reads the word afterwards zeroes e->ovf_host[idx] first; prewarm, the
+// layer bench and the read-backs arm it too (the f16x2 kernels need one) and nobody reads what they raise.
+FwdMode armed(const apz_engine* e, int idx) {
+    FwdMode m;
+    if (e->trunk_arith == APZ_ARITH_F16X2 && e->ovf_dev) m.ovf = e->ovf_dev + idx;
+    return m;
+}
 
 void add_param(apz_engine* e, const std::string& n, int64_t sz) { e->params.push_back({n, sz}); }
 
@@ -315,6 +332,15 @@ hipEvent_t get_event(apz_engine* e) {
     return ev;
 }
 
+// `waiter` waits for everything queued on `source` so far (a pooled event; the host does not wait)
+hipError_t stream_wait(apz_engine* e, hipStream_t waiter, hipStream_t source) {
+    hipEvent_t ev = get_event(e);
+    hipError_t he = hipEventRecord(ev, source);
+    if (he == hipSuccess) he = hipStreamWaitEvent(waiter, ev, 0);
+    e->free_events.push_back(ev);
+    return he;
+}
+
 // Brackets one or MORE consecutive launches of one kernel class with a single event pair: an event between
 // two kernels costs a barrier packet + cache maintenance (~0.1 ms each under load), so the 20 trunk launches of
 // a sampled forward share one pair and their average duration is elapsed / launches.
@@ -323,8 +349,8 @@ struct Timed {
     int cls;
     int launches = 1;
     hipEvent_t a = nullptr, b = nullptr;
-    Timed(apz_engine* e_, int cls_, bool always = false) : e(e_), cls(cls_) {
-        if (e->profiling && (e->prof_now || always)) {
+    Timed(apz_engine* e_, int cls_, bool always = false, bool untimed = false) : e(e_), cls(cls_) {
+        if (e->profiling && !untimed && (e->prof_now || always)) {
             a = get_event(e);
             b = get_event(e);
             hipEventRecord(a, e->stream);
@@ -414,9 +440,7 @@ int launch_conv_r(apz_engine* e, const ConvLayer& L, const float* in, const floa
 
 template <int H, int W, int CT>
 int launch_conv_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    // the stem of the ring path hands its output to trunk15_ring.h in rows16 layout
-    const bool to16 = e->ring && &L == &e->convs[0];
-    const int ps = to16 ? e->act_ps : H * W, rs = to16 ? e->act_rs : W;
+    const int ps = H * W, rs = W;       // (dense planes in and out: nets with rows16 activations never come here)
     // Small batches (BASELINE config 2: 64 concurrent games = 32 boards per launch): one workgroup per board leaves most
     // CUs idle and every workgroup streams the layer's whole weight set (2.4 MB at 256 x 256) through one CU's L2 port.
     // Then each board goes to CT workgroups of 64 output channels (gridDim.y): same arithmetic per output element, in
@@ -510,7 +534,7 @@ int launch_wino3b_t(apz_engine* e, const ConvLayer& L, const float* in, const fl
 // (SCALED, K16 only: the form with the layer's static input exponent, launched for L.act_exp != 0 and never otherwise --
 // an engine without exponents runs the same code objects as before they existed)
 template <bool RESID, bool K16, bool SCALED = false>
-int launch_wino3h_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_wino3h_t(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     static_assert(K16 || !SCALED, "only the 16-channel kernel has a scaled form");
     using T = typename std::conditional<K16, apz::Wino3H16, apz::Wino3H>::type;
     constexpr int FORM = SCALED ? apz::WINO3H16_PLAIN_SCALED : apz::WINO3H16_PLAIN;
@@ -520,11 +544,11 @@ int launch_wino3h_t(apz_engine* e, const ConvLayer& L, const float* in, const fl
         if (int rc = need_lds(e, kern, T::LDS_BYTES)) return rc;
         if constexpr (K16)
             hipLaunchKernelGGL((apz::trunk15_wino3h16_kernel<RESID, true, FORM>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
-                               in + off, (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur,
+                               in + off, (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, m.ovf,
                                nullptr, SCALED ? L.act_exp : 0);
         else
             hipLaunchKernelGGL((apz::trunk15_wino3h_kernel<RESID, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream, in + off,
-                               (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, e->ovf_cur);
+                               (const void*)L.upk3h, L.bias3h, RESID ? resid + off : nullptr, out + off, nb, m.ovf);
         return APZ_OK;
     });
 }
@@ -532,57 +556,16 @@ int launch_wino3h_t(apz_engine* e, const ConvLayer& L, const float* in, const fl
 // The small-batch form of the 16-channel split kernel (apz_set_trunk_uniform): 1 .. 32 boards, eight workgroups per board,
 // the batched kernel's weights, bias, overflow word and exponent -- and its bits (csrc/trunk15_wino3hs.h)
 template <bool RESID, bool SCALED>
-int launch_wino3hs_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_wino3hs_t(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Wino3HS;
     unsigned epoch;
     if (int rc = e->w3hs.prepare(e->stream, &epoch)) return rc;
     if (int rc = need_lds(e, (const void*)apz::trunk15_wino3hs_kernel<RESID, SCALED>, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((apz::trunk15_wino3hs_kernel<RESID, SCALED>), dim3(T::grid(n)), dim3(512), T::LDS_BYTES, e->stream, in,
-                       (const void*)L.upk3h, L.bias3h, RESID ? resid : nullptr, out, n, e->ovf_cur, SCALED ? L.act_exp : 0,
+                       (const void*)L.upk3h, L.bias3h, RESID ? resid : nullptr, out, n, m.ovf, SCALED ? L.act_exp : 0,
                        e->w3hs.slabs, e->w3hs.tickets, epoch);
     HIP_TRY(hipGetLastError());
     return APZ_OK;
-}
-
-// The routes of a 15x15 trunk layer, first match wins; each launcher's template arguments name its kernel
-int launch_trunk_wino3(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    // uniform: f16x2, <= 32 boards on the small-batch form of the 16-channel kernel
-    if (e->uniform_trunk && e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur && !e->f16x2_k8 &&
-        n <= apz::Wino3S::MAX_BOARDS && !e->no_small_trunk) {
-        if (L.act_exp != 0) {
-            if (resid) return launch_wino3hs_t<true, true>(e, L, in, resid, out, n);
-            return launch_wino3hs_t<false, true>(e, L, in, resid, out, n);
-        }
-        if (resid) return launch_wino3hs_t<true, false>(e, L, in, resid, out, n);
-        return launch_wino3hs_t<false, false>(e, L, in, resid, out, n);
-    }
-    // batched f16x2: the 8-channel kernel (APZ_F16X2_K8), the scaled 16-channel kernel, the 16-channel kernel
-    if (e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.upk3h && e->ovf_cur &&
-        (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
-        if (e->f16x2_k8) {
-            if (resid) return launch_wino3h_t<true, false>(e, L, in, resid, out, n);
-            return launch_wino3h_t<false, false>(e, L, in, resid, out, n);
-        }
-        if (L.act_exp != 0) {
-            if (resid) return launch_wino3h_t<true, true, true>(e, L, in, resid, out, n);
-            return launch_wino3h_t<false, true, true>(e, L, in, resid, out, n);
-        }
-        if (resid) return launch_wino3h_t<true, true>(e, L, in, resid, out, n);
-        return launch_wino3h_t<false, true>(e, L, in, resid, out, n);
-    }
-    // batched bf16x3
-    if (e->trunk_arith == APZ_ARITH_BF16X3 && L.upk3b && (n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk)) {
-        if (resid) return launch_wino3b_t<true>(e, L, in, resid, out, n);
-        return launch_wino3b_t<false>(e, L, in, resid, out, n);
-    }
-    // exact fp32: small, quarter or batched by the number of boards (launch_wino3_t)
-    if (resid) return launch_wino3_t<true, true>(e, in, L.upk2, L.bias, resid, out, n, L.upk3s);
-    return launch_wino3_t<false, true>(e, in, L.upk2, L.bias, nullptr, out, n, L.upk3s);
-}
-
-int launch_trunk_ring(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    if (e->trunk_kernel == APZ_TRUNK_WINOGRAD && L.upk2) return launch_trunk_wino3(e, L, in, resid, out, n);
-    return launch_trunk_ring_t<4>(e, L, in, resid, out, n);   // the direct convolution: in-tree cross-check of the Winograd kernel
 }
 
 template <int C4, int CIN, bool CODES>
@@ -624,27 +607,68 @@ int launch_conv8_t(apz_engine* e, const ConvLayer& L, const float* in, const flo
 
 // ... with split operands on the fp16 matrix pipe (conv8_split.h): same items, same grids
 template <bool RESID>
-int launch_conv8h_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+int launch_conv8h_t(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     using T = apz::Conv8H;
     const long items = (long)n * (L.cout / 16);
     const int grid = (int)std::min<long>(items, 2L * e->num_cu);
     if (int rc = need_lds(e, (const void*)apz::conv8h_kernel<RESID>, T::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((apz::conv8h_kernel<RESID>), dim3(grid), dim3(256), T::LDS_BYTES, e->stream, in, (const void*)L.wpk8h,
-                       L.bias8h, resid, out, n, L.cin, L.cout, 1, e->ovf_cur);
+                       L.bias8h, resid, out, n, L.cin, L.cout, 1, m.ovf);
     HIP_TRY(hipGetLastError());
     return APZ_OK;
 }
 
-int launch_conv8(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n,
-                 const unsigned char* codes = nullptr) {
-    if (L.cout % 16 || !L.wpk12) return fail(APZ_E_UNSUPPORTED, "conv8: C_out must be a multiple of 16");
-    if (!codes && e->trunk_arith == APZ_ARITH_F16X2 && !e->force_f32 && L.wpk8h && e->ovf_cur) {
-        if (resid) return launch_conv8h_t<true>(e, L, in, resid, out, n);
-        return launch_conv8h_t<false>(e, L, in, nullptr, out, n);
+// The kernel of a 15x15 trunk convolution or of an 8x8 board: DESIGN.md section 4, "Which arithmetic a batch gets"
+enum class Route {
+    F16X2_SMALL,   // trunk15_wino3hs_kernel: f16x2, <= 32 boards (apz_set_trunk_uniform)
+    F16X2_K8,      // trunk15_wino3h_kernel: batched f16x2, 8-channel chunks (APZ_F16X2_K8=1)
+    F16X2_K16,     // trunk15_wino3h16_kernel: batched f16x2
+    BF16X3,        // trunk15_wino3b_kernel: batched bf16x3
+    EXACT,         // trunk15_wino3s_kernel / trunk15_wino3_kernel: exact fp32; small, quarter or batched by launch_wino3_t
+    DIRECT,        // trunk15_ring_kernel: the direct convolution, in-tree cross-check of the Winograd kernels
+    CONV8H,        // conv8h_kernel: 8x8 boards, f16x2
+    CONV8          // conv8_kernel: 8x8 boards, exact fp32
+};
+
+// (engine configuration, layer, batch size, mode) -> kernel, first match wins: the one place that decides it
+Route trunk_route(const apz_engine* e, const ConvLayer& L, int n, const FwdMode& m) {
+    // the f16x2 kernels raise a word: a forward without one (and the exact repeat, and a measuring pass) runs exact fp32
+    const bool f16x2 = e->trunk_arith == APZ_ARITH_F16X2 && !m.exact && m.ovf;
+    if (e->small8) return f16x2 && L.wpk8h ? Route::CONV8H : Route::CONV8;     // one kernel family for every batch size
+    if (e->trunk_kernel != APZ_TRUNK_WINOGRAD || !L.upk2) return Route::DIRECT;
+    const bool batched = n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk || m.batched;
+    if (f16x2 && L.upk3h) {
+        if (batched) return e->f16x2_k8 ? Route::F16X2_K8 : Route::F16X2_K16;
+        if (e->uniform_trunk && !e->f16x2_k8) return Route::F16X2_SMALL;
     }
-    if (codes) return launch_conv8_t<false, true>(e, L, (const float*)codes, nullptr, out, n);
-    if (resid) return launch_conv8_t<true, false>(e, L, in, resid, out, n);
-    return launch_conv8_t<false, false>(e, L, in, nullptr, out, n);
+    if (e->trunk_arith == APZ_ARITH_BF16X3 && L.upk3b && batched) return Route::BF16X3;
+    return Route::EXACT;
+}
+
+// SCALED: the forms with the layer's static input exponent, F16X2_SMALL and F16X2_K16 only, launched for L.act_exp != 0 and
+// never otherwise -- an engine without exponents runs the same code objects as before they existed
+template <bool RESID, bool SCALED>
+int launch_routed_t(apz_engine* e, const FwdMode& m, Route r, const ConvLayer& L, const float* in, const float* resid, float* out,
+                    int n) {
+    switch (r) {
+        case Route::F16X2_SMALL: return launch_wino3hs_t<RESID, SCALED>(e, m, L, in, resid, out, n);
+        case Route::F16X2_K8: return launch_wino3h_t<RESID, false>(e, m, L, in, resid, out, n);
+        case Route::F16X2_K16: return launch_wino3h_t<RESID, true, SCALED>(e, m, L, in, resid, out, n);
+        case Route::BF16X3: return launch_wino3b_t<RESID>(e, L, in, resid, out, n);
+        case Route::EXACT: return launch_wino3_t<RESID, true>(e, in, L.upk2, L.bias, resid, out, n, m.batched ? nullptr : L.upk3s);
+        case Route::DIRECT: return launch_trunk_ring_t<4>(e, L, in, resid, out, n);
+        case Route::CONV8H: return launch_conv8h_t<RESID>(e, m, L, in, resid, out, n);
+        case Route::CONV8: return launch_conv8_t<RESID, false>(e, L, in, resid, out, n);
+    }
+}
+
+// one convolution on the kernel of its route; resid == nullptr: no residual input
+int launch_routed(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    if (e->small8 && (L.cout % 16 || !L.wpk12)) return fail(APZ_E_UNSUPPORTED, "conv8: C_out must be a multiple of 16");
+    const Route r = trunk_route(e, L, n, m);
+    const bool scaled = (r == Route::F16X2_SMALL || r == Route::F16X2_K16) && L.act_exp != 0;
+    if (resid) return (scaled ? launch_routed_t<true, true> : launch_routed_t<true, false>)(e, m, r, L, in, resid, out, n);
+    return (scaled ? launch_routed_t<false, true> : launch_routed_t<false, false>)(e, m, r, L, in, nullptr, out, n);
 }
 
 // ---- framed engines (csrc/frame15.h)
@@ -675,29 +699,9 @@ int launch_frame_clear(apz_engine* e, float* act, int n) {
     return APZ_OK;
 }
 
-// the first layer of a framed engine: framing kernel, the planes form of the stem, clear (unless it is the net's last layer)
-int launch_frame_stem(apz_engine* e, const float* planes, const unsigned char* codes, float* out, int n) {
-    if (int rc = codes ? launch_frame_encode(e, codes, n) : launch_frame_planes(e, planes, n)) return rc;
-    if (int rc = launch_stem15(e, e->convs[0], e->fplanes, out, n)) return rc;
-    return e->convs.size() > 1 ? launch_frame_clear(e, out, n) : APZ_OK;
-}
-
-// a trunk layer of a framed engine: the 15x15 route of the batch, then the clear (skipped behind the net's last layer: the
-// heads read on-board cells only)
-int launch_frame_layer(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    if (int rc = launch_trunk_ring(e, L, in, resid, out, n)) return rc;
-    return &L != &e->convs.back() ? launch_frame_clear(e, out, n) : APZ_OK;
-}
-
-int launch_conv(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+// the generic convolution (conv3x3_mfma.h): every layer of the nets that have no kernel family of their own
+int launch_conv_generic(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
     const int H = e->cfg.height, W = e->cfg.width, ct = L.cout / 64;
-    if (e->small8) return launch_conv8(e, L, in, resid, out, n);
-    if (e->frame_s) {                   // `in` of the first layer: dense S x S planes
-        if (&L != &e->convs[0]) return launch_frame_layer(e, L, in, resid, out, n);
-        return launch_frame_stem(e, in, nullptr, out, n);
-    }
-    if (e->ring && &L != &e->convs[0]) return launch_trunk_ring(e, L, in, resid, out, n);
-    if (e->ring) return launch_stem15(e, L, in, out, n);
     if (H == 15 && W == 15) {
         if (ct == 2) return launch_conv_t<15, 15, 2>(e, L, in, resid, out, n);
         if (ct == 1) return launch_conv_t<15, 15, 1>(e, L, in, resid, out, n);
@@ -710,7 +714,49 @@ int launch_conv(apz_engine* e, const ConvLayer& L, const float* in, const float*
     return fail(APZ_E_UNSUPPORTED, "conv3x3: unsupported board size / channel count");
 }
 
-// e->measure_max: max |x| of the rows16 tensor `in` (n boards, 128 channels), the input of trunk layer li >= 1, as
+// How the engine's first layer is queued, by the kernel family of its net
+enum class FirstLayer {
+    FRAMED,    // framed engines: framing kernel (from codes or dense S x S planes), the planes form of the stem, clear
+    CONV8,     // 8x8 boards: conv8_kernel, which decodes position codes itself
+    STEM15,    // 15x15 / 128-filter residual net: stem15_kernel, which decodes position codes itself
+    GENERIC    // every other net: the generic convolution, dense planes only
+};
+
+FirstLayer first_layer(const apz_engine* e) {
+    if (e->frame_s) return FirstLayer::FRAMED;
+    if (e->small8) return FirstLayer::CONV8;
+    return e->ring ? FirstLayer::STEM15 : FirstLayer::GENERIC;
+}
+
+// forward_from_codes: the first layer reads the position codes itself (no planes buffer)
+bool stem_takes_codes(const apz_engine* e) { return first_layer(e) != FirstLayer::GENERIC; }
+
+// layer 0 of n boards into `out`; codes != nullptr (stem_takes_codes(e) only): the position codes instead of `planes`
+int launch_first_layer(apz_engine* e, const FwdMode& m, const float* planes, const unsigned char* codes, float* out, int n) {
+    const ConvLayer& L = e->convs[0];
+    switch (first_layer(e)) {
+        case FirstLayer::FRAMED:
+            if (int rc = codes ? launch_frame_encode(e, codes, n) : launch_frame_planes(e, planes, n)) return rc;
+            if (int rc = launch_stem15(e, L, e->fplanes, out, n)) return rc;
+            return e->convs.size() > 1 ? launch_frame_clear(e, out, n) : APZ_OK;     // (the heads read on-board cells only)
+        case FirstLayer::CONV8:
+            if (!codes) return launch_routed(e, m, L, planes, nullptr, out, n);
+            if (L.cout % 16 || !L.wpk12) return fail(APZ_E_UNSUPPORTED, "conv8: C_out must be a multiple of 16");
+            return launch_conv8_t<false, true>(e, L, (const float*)codes, nullptr, out, n);
+        case FirstLayer::STEM15: return launch_stem15(e, L, planes, out, n, codes);
+        case FirstLayer::GENERIC: return launch_conv_generic(e, L, planes, nullptr, out, n);
+    }
+}
+
+// a layer behind the first
+int launch_conv(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
+    if (!e->small8 && !e->ring) return launch_conv_generic(e, L, in, resid, out, n);
+    if (int rc = launch_routed(e, m, L, in, resid, out, n)) return rc;
+    // framed engines: the off-board cells zero again (skipped behind the net's last layer: the heads read on-board cells only)
+    return e->frame_s && &L != &e->convs.back() ? launch_frame_clear(e, out, n) : APZ_OK;
+}
+
+// m.measure_max: max |x| of the rows16 tensor `in` (n boards, 128 channels), the input of trunk layer li >= 1, as
 // partials in row li - 1 of e->amax_dev
 int launch_act_max(apz_engine* e, int li, const float* in, int n) {
     const long n4 = (long)n * 128 * (apz::Trunk15::GPLANE / 4);
@@ -721,55 +767,45 @@ int launch_act_max(apz_engine* e, int li, const float* in, int n) {
     return APZ_OK;
 }
 
-// runs conv layers [0, upto] on e->planes; returns the buffer holding layer `upto`'s output
-int run_trunk(apz_engine* e, const float* planes, int n, int upto, float** result, const unsigned char* codes = nullptr) {
+// runs conv layers [0, upto] on `planes` (or `codes`: launch_first_layer); returns the buffer holding layer `upto`'s output
+int run_trunk(apz_engine* e, const FwdMode& m, const float* planes, const unsigned char* codes, int n, int upto, float** result) {
     float *x = e->act[0], *t = e->act[1], *y = e->act[2];
-    const float* cur = planes;
+    const float* cur = x;
     const int nl = (int)e->convs.size();
     const int last = std::min(upto, nl - 1);
     {
-        Timed tm(e, APZ_K_STEM);
-        int rc;
-        if (e->frame_s)                 // (the pair covers the framing kernel, the stem and its clear)
-            rc = launch_frame_stem(e, cur, codes, x, n);
-        else if (codes && e->small8)
-            rc = launch_conv8(e, e->convs[0], nullptr, nullptr, x, n, codes);       // the first layer decodes the codes itself
-        else if (codes && e->ring && e->cfg.net_kind == APZ_NET_RESNET)
-            rc = launch_stem15(e, e->convs[0], nullptr, x, n, codes);
-        else
-            rc = launch_conv(e, e->convs[0], cur, nullptr, x, n);
-        if (rc) return rc;
-        cur = x;
+        Timed tm(e, APZ_K_STEM, false, m.untimed);       // (framed engines: the pair covers the framing kernel, the stem and its clear)
+        if (int rc = launch_first_layer(e, m, planes, codes, x, n)) return rc;
     }
     if (last >= 1) {
-        Timed tm(e, APZ_K_TRUNK);       // all trunk launches of this forward under one event pair
+        Timed tm(e, APZ_K_TRUNK, false, m.untimed);      // all trunk launches of this forward under one event pair
         tm.launches = last;             // (framed engines: the clears are inside the pair and counted with their layers)
         for (int li = 1; li <= last; li++) {
             const ConvLayer& L = e->convs[li];
-            if (e->measure_max) {
+            if (m.measure_max) {
                 int rc = launch_act_max(e, li, L.residual ? t : x, n);
                 if (rc) return rc;
             }
             if (e->cfg.net_kind == APZ_NET_RESNET) {
                 if (!L.residual) {          // convA: x -> t
-                    int rc = launch_conv(e, L, x, nullptr, t, n);
+                    int rc = launch_conv(e, m, L, x, nullptr, t, n);
                     if (rc) return rc;
                     cur = t;
                 } else {                    // convB: t (+x) -> y ; then y becomes the block output
-                    int rc = launch_conv(e, L, t, x, y, n);
+                    int rc = launch_conv(e, m, L, t, x, y, n);
                     if (rc) return rc;
                     std::swap(x, y);
                     cur = x;
                 }
             } else {
                 float* dst = (cur == x) ? t : x;
-                int rc = launch_conv(e, L, cur, nullptr, dst, n);
+                int rc = launch_conv(e, m, L, cur, nullptr, dst, n);
                 if (rc) return rc;
                 cur = dst;
             }
         }
     }
-    if (e->measure_max && last >= 1)
+    if (m.measure_max && last >= 1)
         HIP_TRY(hipMemcpyAsync(e->amax_host, e->amax_dev, (size_t)last * apz::ActMax::MAX_PARTS * sizeof(float), hipMemcpyDeviceToHost,
                                e->stream));
     *result = const_cast<float*>(cur);
@@ -783,10 +819,8 @@ void drop_forward_graphs(apz_engine* e) {
 }
 
 // codes_dev != nullptr (stem_takes_codes(e) only): the position codes instead of `planes`
-bool stem_takes_codes(const apz_engine* e) { return (e->ring && e->cfg.net_kind == APZ_NET_RESNET) || e->small8; }
-
-int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* values, float* logits,
-                float* vlogits, const unsigned char* codes_dev = nullptr) {
+int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsigned char* codes_dev, int n, float* probs,
+                float* values, float* logits = nullptr, float* vlogits = nullptr) {
     if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
@@ -796,7 +830,7 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
     // measured window (two records per ~2 ms forward, at the forward's edges where the slot's `done` event sits anyway)
     Timed whole(e, APZ_K_FORWARD, true);
     float* trunk = nullptr;
-    int rc = run_trunk(e, planes, n, (int)e->convs.size() - 1, &trunk, codes_dev);
+    int rc = run_trunk(e, m, planes, codes_dev, n, (int)e->convs.size() - 1, &trunk);
     if (rc) return rc;
     const int hw = e->hw;
     if (e->small8) {                    // both 1x1 convolutions, both FullyConnected layers, softmax and tanh in one launch
@@ -849,10 +883,10 @@ int forward_dev(apz_engine* e, const float* planes, int n, float* probs, float* 
 
 // The forward of n boards from their position codes: the stem decodes them itself where it can, else they are expanded
 // into e->planes first
-int forward_from_codes(apz_engine* e, const unsigned char* codes_dev, int n, float* probs, float* values) {
-    if (stem_takes_codes(e)) return forward_dev(e, nullptr, n, probs, values, nullptr, nullptr, codes_dev);
+int forward_from_codes(apz_engine* e, const FwdMode& m, const unsigned char* codes_dev, int n, float* probs, float* values) {
+    if (stem_takes_codes(e)) return forward_dev(e, m, nullptr, codes_dev, n, probs, values);
     if (int rc = apz_encode_planes(e, codes_dev, n, e->cfg.c_in, e->planes)) return rc;
-    return forward_dev(e, e->planes, n, probs, values, nullptr, nullptr);
+    return forward_dev(e, m, e->planes, nullptr, n, probs, values);
 }
 
 // The tail of the synchronous host entry points: e->probs / e->values of n boards through the pinned staging buffers to
@@ -868,15 +902,21 @@ int collect_to_host(apz_engine* e, int n, float* probs_host, float* values_host)
     return APZ_OK;
 }
 
-// APZ_ARITH_F16X2: arms the synchronous overflow word for the scope (entry points that run trunk layers without collecting a
-// forward's results -- prewarm, the layer bench, apz_layer_io: the word is raised and nobody reads it)
-struct ArmOverflowWord {
-    apz_engine* e;
-    explicit ArmOverflowWord(apz_engine* e_) : e(e_) {
-        if (e->trunk_arith == APZ_ARITH_F16X2 && e->ovf_dev) e->ovf_cur = e->ovf_dev + APZ_MAX_SLOTS;
-    }
-    ~ArmOverflowWord() { e->ovf_cur = nullptr; }
-};
+// The head of the synchronous host entry points: the caller's planes / position codes of n boards through the pinned
+// staging buffer into e->planes / e->codes, queued on the engine's stream
+int stage_planes(apz_engine* e, const float* planes_host, int n) {
+    const size_t bytes = (size_t)n * e->cfg.c_in * e->hw * sizeof(float);
+    std::memcpy(e->h_planes, planes_host, bytes);
+    HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, bytes, hipMemcpyHostToDevice, e->stream));
+    return APZ_OK;
+}
+
+int stage_codes(apz_engine* e, const uint8_t* codes_host, int n) {
+    const size_t bytes = (size_t)n * e->code_stride;
+    std::memcpy(e->h_codes, codes_host, bytes);
+    HIP_TRY(hipMemcpyAsync(e->codes, e->h_codes, bytes, hipMemcpyHostToDevice, e->stream));
+    return APZ_OK;
+}
 
 // ---- static activation exponents of the f16x2 trunk kernel
 // APZ_OK where they exist: the 15x15 / 128-filter residual net, APZ_ARITH_F16X2, the 16-channel kernel
@@ -953,22 +993,21 @@ int lower_act_exponents(apz_engine* e, int n) {
 }
 
 // The exact-fp32 repeat of an overflowed forward of n boards; with apz_set_act_scale_auto on it measures the trunk inputs
-// on the way and lowers the exponents behind it.  Returns with the stream drained.
+// on the way and lowers the exponents behind it.  Returns with the stream drained.  `run(mode)` queues the forward.
 template <class F>
 int repeat_exact(apz_engine* e, int n, F run) {
-    const bool measure = e->act_auto && e->amax_dev && n > 0;
-    e->force_f32 = true;
-    e->measure_max = measure;
-    int rc = run();
-    e->measure_max = false;
-    e->force_f32 = false;
+    FwdMode m;
+    m.exact = true;
+    m.measure_max = e->act_auto && e->amax_dev && n > 0;
+    int rc = run(m);
     e->ovf_repeats++;
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    return measure ? lower_act_exponents(e, n) : APZ_OK;
+    return m.measure_max ? lower_act_exponents(e, n) : APZ_OK;
 }
 
-// one measuring forward of n boards on the exact-fp32 kernels (`run` queues it), then the exponents from the maxima
+// one measuring forward of n boards on the exact-fp32 kernels (`run(mode)` stages and queues it), then the exponents from
+// the maxima
 template <class F>
 int calibrate_trunk(apz_engine* e, int n, float* layer_max_out, int count, F run) {
     if (int rc = act_scale_supported(e)) return rc;
@@ -979,12 +1018,9 @@ int calibrate_trunk(apz_engine* e, int n, float* layer_max_out, int count, F run
     if (count == 0) return APZ_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
     if (int rc = act_scale_buffers(e)) return rc;
-    e->force_f32 = true;                          // (no overflow word armed either: nothing here counts as an overflow)
-    e->measure_max = true;
-    int rc = run();
-    e->measure_max = false;
-    e->force_f32 = false;
-    if (rc) return rc;
+    FwdMode measuring;                            // (no overflow word armed: nothing here counts as an overflow)
+    measuring.exact = measuring.measure_max = true;
+    if (int rc = run(measuring)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     resolve_pending(e);
     std::vector<float> m(count);
@@ -1006,13 +1042,10 @@ int calibrate_trunk(apz_engine* e, int n, float* layer_max_out, int count, F run
     // The maxima are taken behind the ReLU, which turns a NaN into 0: a layer whose exact-fp32 sums are inf - inf shows a
     // maximum of 0, not a non-finite one.  So the new exponents prove themselves on their own batch: the same forward on
     // the f16x2 kernel (whatever the batch size), whose non-finite check sits in front of the ReLU, must not raise the word.
-    const bool small_was = e->no_small_trunk;
-    e->no_small_trunk = true;
+    FwdMode proving = armed(e, APZ_MAX_SLOTS);
+    proving.batched = true;
     e->ovf_host[APZ_MAX_SLOTS] = 0;
-    e->ovf_cur = e->ovf_dev + APZ_MAX_SLOTS;
-    rc = run();
-    e->ovf_cur = nullptr;
-    e->no_small_trunk = small_was;
+    const int rc = run(proving);
     hipError_t he = hipStreamSynchronize(e->stream);
     resolve_pending(e);
     const bool raised = e->ovf_host[APZ_MAX_SLOTS] != 0;
@@ -1027,23 +1060,29 @@ int calibrate_trunk(apz_engine* e, int n, float* layer_max_out, int count, F run
     return APZ_OK;
 }
 
-// APZ_ARITH_F16X2: forward_dev with the overflow word `idx` armed.  `again` != nullptr: the forward is collected here --
-// wait for the stream, look at the word and, if an activation left the fp16 range, run `again` (the same forward, which
-// then takes the exact-fp32 trunk kernel).  Other arithmetics: plain forward_dev.
+// The forward of the synchronous entry points: `run(mode)` queues it with the synchronous overflow word armed.
+// APZ_ARITH_F16X2: collected here -- wait for the stream, look at the word and, if an activation left the fp16 range, run
+// the same forward again on the exact-fp32 trunk kernel.  Other arithmetics: queued, nothing more.
 template <class F>
-int forward_guarded(apz_engine* e, int idx, int n, F run, bool collect) {
-    if (e->trunk_arith != APZ_ARITH_F16X2 || !e->ovf_host) return run();
-    e->ovf_host[idx] = 0;
-    e->ovf_cur = e->ovf_dev + idx;
-    int rc = run();
-    e->ovf_cur = nullptr;
-    if (rc || !collect) return rc;
+int forward_guarded(apz_engine* e, int n, F run) {
+    const FwdMode m = armed(e, APZ_MAX_SLOTS);
+    if (!m.ovf) return run(m);
+    unsigned& word = e->ovf_host[APZ_MAX_SLOTS];
+    word = 0;
+    if (int rc = run(m)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->ovf_host[idx]) {
-        e->ovf_host[idx] = 0;
+    if (word) {
+        word = 0;
         return repeat_exact(e, n, run);
     }
     return APZ_OK;
+}
+
+// ... of n boards into e->probs / e->values, and those to the caller
+template <class F>
+int forward_to_host(apz_engine* e, int n, F run, float* probs_host, float* values_host) {
+    if (int rc = forward_guarded(e, n, run)) return rc;
+    return collect_to_host(e, n, probs_host, values_host);
 }
 
 // dihedral index tables (train_mxnet.py:115-135) on square boards
@@ -1406,10 +1445,10 @@ int apz_forward(apz_engine* e, const void* planes_dev, int n, void* probs_dev, v
     EngineLock guard(e->submit_lock);
     HIP_TRY(hipSetDevice(e->cfg.device));
     // (APZ_ARITH_F16X2: returns with the stream drained -- the overflow word has to be read before the results are used)
-    return forward_guarded(e, APZ_MAX_SLOTS, n, [&]() {
-        return forward_dev(e, (const float*)planes_dev, n, (float*)probs_dev, (float*)values_dev, (float*)logits_dev,
+    return forward_guarded(e, n, [&](const FwdMode& m) {
+        return forward_dev(e, m, (const float*)planes_dev, nullptr, n, (float*)probs_dev, (float*)values_dev, (float*)logits_dev,
                            (float*)vlogits_dev);
-    }, true);
+    });
 }
 
 int apz_forward_host(apz_engine* e, const float* planes_host, int n, float* probs_host, float* values_host) {
@@ -1418,12 +1457,9 @@ int apz_forward_host(apz_engine* e, const float* planes_host, int n, float* prob
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
-    const size_t pin = (size_t)n * e->cfg.c_in * e->hw * sizeof(float);
-    std::memcpy(e->h_planes, planes_host, pin);
-    HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, pin, hipMemcpyHostToDevice, e->stream));
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() { return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr); }, true);
-    if (rc) return rc;
-    return collect_to_host(e, n, probs_host, values_host);
+    if (int rc = stage_planes(e, planes_host, n)) return rc;
+    return forward_to_host(e, n, [&](const FwdMode& m) { return forward_dev(e, m, e->planes, nullptr, n, e->probs, e->values); },
+                           probs_host, values_host);
 }
 
 int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, float* probs_pinned,
@@ -1437,7 +1473,7 @@ int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, f
     const size_t hw = e->hw;
     HIP_TRY(hipMemcpyAsync(e->codes, codes_pinned, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
     // (APZ_ARITH_F16X2: the forward is collected here, see forward_guarded -- the copies below are queued behind it)
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() { return forward_from_codes(e, e->codes, n, e->probs, e->values); }, true);
+    int rc = forward_guarded(e, n, [&](const FwdMode& m) { return forward_from_codes(e, m, e->codes, n, e->probs, e->values); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(probs_pinned, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(values_pinned, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1449,14 +1485,10 @@ int apz_forward_codes_host(apz_engine* e, const uint8_t* codes_host, int n, floa
     EngineLock guard(e->submit_lock);
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
-    std::memcpy(e->h_codes, codes_host, (size_t)n * e->code_stride);
-    int rc = apz_forward_codes_async(e, e->h_codes, n, e->h_probs, e->h_values);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    resolve_pending(e);
-    std::memcpy(probs_host, e->h_probs, (size_t)n * e->hw * sizeof(float));
-    std::memcpy(values_host, e->h_values, n * sizeof(float));
-    return APZ_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (int rc = stage_codes(e, codes_host, n)) return rc;
+    return forward_to_host(e, n, [&](const FwdMode& m) { return forward_from_codes(e, m, e->codes, n, e->probs, e->values); },
+                           probs_host, values_host);
 }
 
 // batches above this are a handful of long kernels: nothing to gain from a graph
@@ -1486,16 +1518,10 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     }
     std::memcpy(sl.h_codes, codes_host, (size_t)n * e->code_stride);
     // (the codes are read straight from the pinned slot)
-    auto launch_all = [&]() { return forward_from_codes(e, sl.d_codes, n, sl.d_probs, sl.d_values); };
+    const FwdMode m = armed(e, slot);                         // the slot's overflow word: read by apz_wait
+    if (m.ovf) e->ovf_host[slot] = 0;
+    auto launch_all = [&]() { return forward_from_codes(e, m, sl.d_codes, n, sl.d_probs, sl.d_values); };
     int rc = APZ_OK;
-    if (e->trunk_arith == APZ_ARITH_F16X2 && e->ovf_host) {   // the slot's overflow word: read by apz_wait
-        e->ovf_host[slot] = 0;
-        e->ovf_cur = e->ovf_dev + slot;
-    }
-    struct Disarm {
-        apz_engine* e;
-        ~Disarm() { e->ovf_cur = nullptr; }
-    } disarm{e};
     const long key = ((long)slot << 32) | (long)n;
     const bool graphable = e->use_graphs && !e->profiling && n <= FWD_GRAPH_MAX_BOARDS && e->loaded;
     auto it = graphable ? e->fwd_graphs.find(key) : e->fwd_graphs.end();
@@ -1505,8 +1531,9 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     } else if (graphable && ++e->fwd_seen[key] >= 3 && !e->w3s.near_wrap() && !e->w3hs.near_wrap()) {
         // (third use: every lazy allocation / attribute / ticket reset of this shape has happened outside the capture --
         // need_lds is per kernel, and the two plain submissions before this one launched the kernels the capture launches:
-        // whatever changes the route of a batch size (weights, arithmetic, exponents, uniform, the test selection) goes
-        // through drop_forward_graphs, which starts the count again)
+        // a submission's mode is armed(e, slot) every time, so its kernels follow from what trunk_route and first_layer read
+        // of the engine (weights, arithmetic, exponents, uniform, the test selection), and every setter of that goes through
+        // drop_forward_graphs, which starts the count again)
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
@@ -1550,7 +1577,7 @@ int apz_wait(apz_engine* e, int slot, float* probs_host, float* values_host) {
         // an activation of this batch left the fp16 range (trunk15_wino3h.h): the same batch again on the exact-fp32 kernel
         EngineLock guard(e->submit_lock);
         e->ovf_host[slot] = 0;
-        int rc = repeat_exact(e, sl.n, [&]() { return forward_from_codes(e, sl.d_codes, sl.n, sl.d_probs, sl.d_values); });
+        int rc = repeat_exact(e, sl.n, [&](const FwdMode& m) { return forward_from_codes(e, m, sl.d_codes, sl.n, sl.d_probs, sl.d_values); });
         if (rc) return rc;
     }
     std::memcpy(probs_host, sl.h_probs, (size_t)sl.n * e->hw * sizeof(float));
@@ -1655,11 +1682,7 @@ struct StreamScope {      // run the engine's launch helpers on a caller-supplie
         // The training entry points share per-engine scratch (head_scratch, bn_part, fold_ws, wgw_scratch, wino_scratch,
         // adam_tab).  Calls on ONE stream are ordered by the stream; a caller that switches streams gets the new stream
         // ordered behind everything queued on the previous one, so two streams never work on the scratch at once.
-        if (e->scratch_stream_valid && e->scratch_stream != e->stream) {
-            hipEvent_t ev = get_event(e);
-            if (hipEventRecord(ev, e->scratch_stream) == hipSuccess) hipStreamWaitEvent(e->stream, ev, 0);
-            e->free_events.push_back(ev);
-        }
+        if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
         e->scratch_stream = e->stream;
         e->scratch_stream_valid = true;
     }
@@ -1682,22 +1705,15 @@ int apz_load_weights_dev(apz_engine* e, const char* const* names, const void* co
     hipStream_t engine_stream = e->stream;
     StreamScope sc(e, stream);
     hipStream_t st = e->stream;
-    if (st != engine_stream) {      // forwards already queued on the engine's stream still read the old weights
-        hipEvent_t ev = get_event(e);
-        HIP_TRY(hipEventRecord(ev, engine_stream));
-        HIP_TRY(hipStreamWaitEvent(st, ev, 0));
-        e->free_events.push_back(ev);
-    }
+    // forwards already queued on the engine's stream still read the old weights
+    if (st != engine_stream) HIP_TRY(stream_wait(e, st, engine_stream));
     // From here on packing kernels are queued on `st`: whatever happens below, the engine's stream must end up
     // ordered behind them (a half-refreshed evaluator that ALSO races the packing kernels would be worse).
     struct Closing {
         apz_engine* e;
         hipStream_t st, engine_stream;
         ~Closing() {
-            if (st == engine_stream) return;
-            hipEvent_t ev = get_event(e);
-            if (hipEventRecord(ev, st) == hipSuccess) hipStreamWaitEvent(engine_stream, ev, 0);
-            e->free_events.push_back(ev);
+            if (st != engine_stream) (void)stream_wait(e, engine_stream, st);
         }
     } closing{e, st, engine_stream};
     return pack_all(e, P, st);   // (`closing` orders the engine's stream behind it: forwards queued from now on see the new weights)
@@ -2417,18 +2433,11 @@ int apz_forward_dev_host(apz_engine* e, const void* planes_dev, int n, float* pr
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
-    if (after_stream != APZ_ENGINE_STREAM && (hipStream_t)after_stream != e->stream) {
-        hipEvent_t ev = get_event(e);
-        hipError_t he = hipEventRecord(ev, (hipStream_t)after_stream);
-        if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev, 0);
-        e->free_events.push_back(ev);
-        HIP_TRY(he);
-    }
-    int rc = forward_guarded(e, APZ_MAX_SLOTS, n, [&]() {
-        return forward_dev(e, (const float*)planes_dev, n, e->probs, e->values, nullptr, nullptr);
-    }, true);
-    if (rc) return rc;
-    return collect_to_host(e, n, probs_host, values_host);
+    if (after_stream != APZ_ENGINE_STREAM && (hipStream_t)after_stream != e->stream)
+        HIP_TRY(stream_wait(e, e->stream, (hipStream_t)after_stream));
+    return forward_to_host(e, n, [&](const FwdMode& m) {
+        return forward_dev(e, m, (const float*)planes_dev, nullptr, n, e->probs, e->values);
+    }, probs_host, values_host);
 }
 
 int apz_prewarm(apz_engine* e, int n, int iters) {
@@ -2438,9 +2447,9 @@ int apz_prewarm(apz_engine* e, int n, int iters) {
     if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
     HIP_TRY(hipSetDevice(e->cfg.device));
     // e->codes is zero-filled at creation and only ever overwritten with valid codes: any content is a legal input
-    ArmOverflowWord arm(e);
+    const FwdMode m = armed(e, APZ_MAX_SLOTS);   // (raised, and nobody reads it)
     for (int i = 0; i < iters; i++)
-        if (int rc = forward_from_codes(e, e->codes, n, e->probs, e->values)) return rc;
+        if (int rc = forward_from_codes(e, m, e->codes, n, e->probs, e->values)) return rc;
     return APZ_OK;
 }
 
@@ -2494,15 +2503,13 @@ int apz_conv3x3_bench(apz_engine* e, int layer, int n, int iters, int warmup, fl
     if (layer < 0 || layer >= (int)e->convs.size() || n < 1 || n > e->cfg.max_batch || iters < 1 || warmup < 0)
         return fail(APZ_E_ARG, "bad layer / batch / iteration count");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    const bool was = e->profiling;
-    e->profiling = false;
-    ArmOverflowWord arm(e);
+    FwdMode m = armed(e, APZ_MAX_SLOTS);          // (raised, and nobody reads it)
+    m.untimed = true;
     // produce this layer's real input from the planes resident in e->planes
     const float* in = e->planes;
     if (layer > 0) {
         float* prev = nullptr;
-        int rc = run_trunk(e, e->planes, n, layer - 1, &prev);
-        if (rc) { e->profiling = was; return rc; }
+        if (int rc = run_trunk(e, m, e->planes, nullptr, n, layer - 1, &prev)) return rc;
         in = prev;
     }
     const ConvLayer& L = e->convs[layer];
@@ -2513,41 +2520,46 @@ int apz_conv3x3_bench(apz_engine* e, int layer, int n, int iters, int warmup, fl
     if (L.residual)
         for (int i = 0; i < 3; i++)
             if (e->act[i] != in && e->act[i] != out) resid = e->act[i];
+    auto launch = [&]() { return layer > 0 ? launch_conv(e, m, L, in, resid, out, n) : launch_first_layer(e, m, in, nullptr, out, n); };
     hipEvent_t a = get_event(e), b = get_event(e);   // pooled, destroyed with the engine
     int rc = APZ_OK;
-    for (int i = 0; i < warmup && !rc; i++) rc = launch_conv(e, L, in, resid, out, n);
+    for (int i = 0; i < warmup && !rc; i++) rc = launch();
     hipError_t he = hipEventRecord(a, e->stream);
-    for (int i = 0; i < iters && !rc; i++) rc = launch_conv(e, L, in, resid, out, n);
+    for (int i = 0; i < iters && !rc; i++) rc = launch();
     if (he == hipSuccess) he = hipEventRecord(b, e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     float ms = 0.f;
     if (he == hipSuccess) he = hipEventElapsedTime(&ms, a, b);
     e->free_events.push_back(a);
     e->free_events.push_back(b);
-    e->profiling = was;
     if (he != hipSuccess) return fail(APZ_E_HIP, std::string("conv bench timing: ") + hipGetErrorString(he));
     if (rc) return rc;
     ms_out[0] = ms / iters;
     return APZ_OK;
 }
 
+namespace {
+// apz_layer_io / apz_layer_frame: the trunk of the last forward's batch again on the planes resident in e->planes, up to
+// `layer`, whose output of `count` = n*C_out*plane floats is then in *buf
+int rerun_to_layer(apz_engine* e, int layer, int64_t count, int plane, const char* plane_name, float** buf) {
+    if (!e->loaded || e->last_n < 1) return fail(APZ_E_STATE, "run a forward first");
+    if (layer < 0 || layer >= (int)e->convs.size()) return fail(APZ_E_ARG, "bad layer");
+    const int64_t need = (int64_t)e->last_n * e->convs[layer].cout * plane;
+    if (count != need) return fail(APZ_E_ARG, std::string("count must be n*C_out*") + plane_name + " = " + std::to_string(need));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    FwdMode m = armed(e, APZ_MAX_SLOTS);          // (raised, and nobody reads it)
+    m.untimed = true;
+    return run_trunk(e, m, e->planes, nullptr, e->last_n, layer, buf);
+}
+}  // namespace
+
 int apz_layer_io(apz_engine* e, int layer, float* host_out, int64_t count) {
     if (!e || !host_out) return fail(APZ_E_ARG, "null argument");
     EngineLock guard(e->submit_lock);
-    if (!e->loaded || e->last_n < 1) return fail(APZ_E_STATE, "run a forward first");
-    if (layer < 0 || layer >= (int)e->convs.size()) return fail(APZ_E_ARG, "bad layer");
-    const int64_t need = (int64_t)e->last_n * e->convs[layer].cout * e->hw;
-    if (count != need) return fail(APZ_E_ARG, "count must be n*C_out*H*W = " + std::to_string(need));
-    HIP_TRY(hipSetDevice(e->cfg.device));
     float* buf = nullptr;
-    const bool was = e->profiling;
-    e->profiling = false;
-    ArmOverflowWord arm(e);
-    int rc = run_trunk(e, e->planes, e->last_n, layer, &buf);
-    e->profiling = was;
-    if (rc) return rc;
+    if (int rc = rerun_to_layer(e, layer, count, e->hw, "H*W", &buf)) return rc;
     if (!e->ring) {
-        HIP_TRY(hipMemcpyAsync(host_out, buf, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(host_out, buf, count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         return APZ_OK;
     }
@@ -2565,19 +2577,9 @@ int apz_layer_frame(apz_engine* e, int layer, float* host_out, int64_t count) {
     if (!e || !host_out) return fail(APZ_E_ARG, "null argument");
     EngineLock guard(e->submit_lock);
     if (!e->ring) return fail(APZ_E_UNSUPPORTED, "layer_frame: engines with rows16 activations only (the 128-filter residual net at 15x15 and at framed sizes)");
-    if (!e->loaded || e->last_n < 1) return fail(APZ_E_STATE, "run a forward first");
-    if (layer < 0 || layer >= (int)e->convs.size()) return fail(APZ_E_ARG, "bad layer");
-    const int64_t need = (int64_t)e->last_n * e->convs[layer].cout * e->act_ps;
-    if (count != need) return fail(APZ_E_ARG, "count must be n*C_out*15*16 = " + std::to_string(need));
-    HIP_TRY(hipSetDevice(e->cfg.device));
     float* buf = nullptr;
-    const bool was = e->profiling;
-    e->profiling = false;
-    ArmOverflowWord arm(e);
-    int rc = run_trunk(e, e->planes, e->last_n, layer, &buf);
-    e->profiling = was;
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(host_out, buf, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = rerun_to_layer(e, layer, count, e->act_ps, "15*16", &buf)) return rc;
+    HIP_TRY(hipMemcpyAsync(host_out, buf, count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return APZ_OK;
 }
@@ -2651,21 +2653,18 @@ int apz_set_act_scale_auto(apz_engine* e, int on) {
 int apz_calibrate_trunk_planes(apz_engine* e, const float* planes_host, int n, float* layer_max_out, int count) {
     if (!e || !planes_host) return fail(APZ_E_ARG, "null argument");
     EngineLock guard(e->submit_lock);
-    return calibrate_trunk(e, n, layer_max_out, count, [&]() -> int {
-        const size_t pin = (size_t)n * e->cfg.c_in * e->hw * sizeof(float);
-        std::memcpy(e->h_planes, planes_host, pin);
-        HIP_TRY(hipMemcpyAsync(e->planes, e->h_planes, pin, hipMemcpyHostToDevice, e->stream));
-        return forward_dev(e, e->planes, n, e->probs, e->values, nullptr, nullptr);
+    return calibrate_trunk(e, n, layer_max_out, count, [&](const FwdMode& m) -> int {
+        if (int rc = stage_planes(e, planes_host, n)) return rc;
+        return forward_dev(e, m, e->planes, nullptr, n, e->probs, e->values);
     });
 }
 
 int apz_calibrate_trunk_codes(apz_engine* e, const uint8_t* codes_host, int n, float* layer_max_out, int count) {
     if (!e || !codes_host) return fail(APZ_E_ARG, "null argument");
     EngineLock guard(e->submit_lock);
-    return calibrate_trunk(e, n, layer_max_out, count, [&]() -> int {
-        std::memcpy(e->h_codes, codes_host, (size_t)n * e->code_stride);
-        HIP_TRY(hipMemcpyAsync(e->codes, e->h_codes, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
-        return forward_from_codes(e, e->codes, n, e->probs, e->values);
+    return calibrate_trunk(e, n, layer_max_out, count, [&](const FwdMode& m) -> int {
+        if (int rc = stage_codes(e, codes_host, n)) return rc;
+        return forward_from_codes(e, m, e->codes, n, e->probs, e->values);
     });
 }
 
