@@ -129,7 +129,8 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_device_alloc", "apz_device_free", "apz_memcpy_h2d", "apz_memcpy_d2h",
                "apz_conv3x3_bench", "apz_layer_io", "apz_layer_frame", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows",
                "apz_set_trunk_act_exponents", "apz_get_trunk_act_exponents", "apz_calibrate_trunk_planes", "apz_calibrate_trunk_codes",
-               "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host"]
+               "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host",
+               "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys"]
 
 
 def _one_hip_runtime():
@@ -300,6 +301,9 @@ def hip():
         "apz_set_trunk_uniform": (C.c_int, [vp, C.c_int]),
         "apz_replay_gather": (C.c_int, [vp, vp, vp, vp, C.c_int64, i32p, C.c_int, C.c_int, vp, vp, vp, vp]),
         "apz_forward_dev_host": (C.c_int, [vp, vp, C.c_int, f32p, f32p, vp]),
+        "apz_set_leaf_symmetry": (C.c_int, [vp, C.c_int, C.c_uint64]),
+        "apz_get_leaf_symmetry": (C.c_int, [vp, i32p, _ptr(C.c_uint64)]),
+        "apz_leaf_symmetry_keys": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_uint64, u8p]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -45,6 +45,31 @@ def get_equi_data(play_data, board_height, board_width):
     return out
 
 
+def leaf_symmetry_keys(codes, seed, hw=None):
+    """codes uint8 [n, stride] of a square board (stride = (S*S + 1 + 15) // 16 * 16; hw = S*S, read off the stride where
+    that names one board) -> uint8 [n]: the image index k = 0 .. 7 (this module's order; 6 is the identity) on which the
+    evaluator's leaf symmetry "keyed" evaluates each row.  A function of (seed, the row's S*S + 1 bytes) only;
+    include/alphapig_hip.h has the formula (apz_leaf_symmetry_keys: the arithmetic the kernel runs, compiled for the host,
+    no GPU needed)."""
+    from . import _native
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    if c.ndim != 2:
+        raise ValueError("codes must be [n, stride]")
+    n, stride = c.shape
+    if hw is None:
+        sides = [s for s in range(1, 256) if (s * s + 1 + 15) // 16 * 16 == stride]
+        if len(sides) != 1:             # (boards of side 1 .. 5 share their strides: pass hw)
+            raise ValueError("a code stride of %d bytes does not name one square board: pass hw" % stride)
+        hw = sides[0] * sides[0]
+    k = np.zeros(max(n, 1), dtype=np.uint8)
+    L = _native.hip()
+    rc = L.apz_leaf_symmetry_keys(c.ctypes.data_as(C.POINTER(C.c_uint8)), n, int(hw), stride, int(seed) & (2 ** 64 - 1),
+                                  k.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc < 0:
+        raise ValueError("apz_leaf_symmetry_keys: " + L.apz_last_error().decode())
+    return k[:n]
+
+
 def augment8_gpu(net, planes, pis):
     """planes float32 [n, C, H, W], pis float32 [n, H*W] -> ([8n, C, H, W], [8n, H*W]) on the
     evaluator's GPU; rows 8i..8i+7 are the eight images of tuple i in the reference order."""

@@ -34,6 +34,7 @@
 #include "act_max.h"
 #include "replay.h"
 #include "frame15.h"
+#include "leaf_sym.h"
 
 namespace {
 
@@ -145,6 +146,17 @@ struct apz_engine {
     float *planes = nullptr, *featp = nullptr, *featv = nullptr, *probs = nullptr, *values = nullptr, *fc_logits = nullptr;
     unsigned char* codes = nullptr;
     int *perm_s = nullptr, *perm_p = nullptr;
+    // apz_set_leaf_symmetry (csrc/leaf_sym.h): what forward_codes_sym puts around forward_from_codes.  APZ_SYM_NONE: nothing.
+    int sym_mode = APZ_SYM_NONE;
+    uint64_t sym_seed = 0;
+    int* perm_pinv = nullptr;                // [8][hw]: perm_pinv[k][perm_p[k][p]] = p, uploaded by the first call that turns a mode on
+    // the forward's own input and output under a mode: the image codes, the head's answers on them and the boards' keys --
+    // one set per submission slot + one for the synchronous entry points (index APZ_MAX_SLOTS), allocated at first use,
+    // max_batch rows each.  Never e->codes / e->probs / e->values, which the entry points themselves stage through.
+    struct SymStage {
+        unsigned char *codes = nullptr, *k = nullptr;
+        float *probs = nullptr, *values = nullptr;
+    } sym[APZ_MAX_SLOTS + 1];
     // host pinned staging (apz_forward_host)
     float *h_planes = nullptr, *h_probs = nullptr, *h_values = nullptr;
     unsigned char* h_codes = nullptr;
@@ -889,6 +901,60 @@ int forward_from_codes(apz_engine* e, const FwdMode& m, const unsigned char* cod
     return forward_dev(e, m, e->planes, nullptr, n, probs, values);
 }
 
+// mean8 runs 8 n boards in one forward: APZ_OK if the engine's buffers hold them
+int sym_batch_ok(const apz_engine* e, int n) {
+    if (e->sym_mode == APZ_SYM_MEAN8 && (long)n * 8 > e->cfg.max_batch)
+        return fail(APZ_E_ARG, "leaf symmetry mean8 evaluates 8 boards per position: 8 * " + std::to_string(n) + " = " +
+                                   std::to_string((long)n * 8) + " boards exceed max_batch = " + std::to_string(e->cfg.max_batch));
+    return APZ_OK;
+}
+
+// What every entry point that forwards position codes for a caller queues: forward_from_codes, under a leaf symmetry
+// between sym_expand_kernel and sym_fold_kernel (csrc/leaf_sym.h) -- the forward reads the images from, and answers into,
+// staging set `stage` (a slot, or APZ_MAX_SLOTS: the synchronous entry points), and the fold writes the caller's probs /
+// values.  The trunk route sees the forward's real size: n (keyed) or 8 n (mean8).  APZ_SYM_NONE: a direct call.
+int forward_codes_sym(apz_engine* e, const FwdMode& m, int stage, const unsigned char* codes_dev, int n, float* probs, float* values) {
+    if (e->sym_mode == APZ_SYM_NONE) return forward_from_codes(e, m, codes_dev, n, probs, values);
+    if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
+    if (int rc = sym_batch_ok(e, n)) return rc;
+    if (n == 0) return APZ_OK;
+    const bool mean8 = e->sym_mode == APZ_SYM_MEAN8;
+    const int images = mean8 ? 8 * n : n;
+    apz_engine::SymStage& st = e->sym[stage];
+    const size_t B = e->cfg.max_batch;
+    if (!st.codes) HIP_TRY(hipMalloc((void**)&st.codes, B * e->code_stride));
+    if (!st.probs) HIP_TRY(hipMalloc((void**)&st.probs, B * e->hw * sizeof(float)));
+    if (!st.values) HIP_TRY(hipMalloc((void**)&st.values, B * sizeof(float)));
+    if (!st.k) HIP_TRY(hipMalloc((void**)&st.k, B));
+    {
+        // (sampled profiling: forward_dev decides per forward whether its kernels are timed, so this pair follows the
+        // PREVIOUS forward's decision and the fold's pair this one's; with apz_set_profiling(1) both are always timed)
+        Timed tm(e, APZ_K_ENCODE, false, m.untimed);
+        const dim3 grid(apz::LeafSym::expand_grid(n)), block(apz::LeafSym::THREADS);
+        if (mean8)
+            hipLaunchKernelGGL(apz::sym_expand_kernel<true>, grid, block, 0, e->stream, codes_dev, e->perm_p, st.codes, st.k, n,
+                               e->hw, e->code_stride, e->sym_seed);
+        else
+            hipLaunchKernelGGL(apz::sym_expand_kernel<false>, grid, block, 0, e->stream, codes_dev, e->perm_p, st.codes, st.k, n,
+                               e->hw, e->code_stride, e->sym_seed);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = forward_from_codes(e, m, st.codes, images, st.probs, st.values)) return rc;
+    {
+        Timed tm(e, APZ_K_ENCODE, false, m.untimed);
+        const long total = (long)n * e->hw;
+        const dim3 grid((int)std::min<long>((total + 255) / 256, e->num_cu * 8)), block(256);
+        if (mean8)
+            hipLaunchKernelGGL(apz::sym_fold_kernel<true>, grid, block, 0, e->stream, st.probs, st.values, st.k, e->perm_pinv, probs,
+                               values, n, e->hw);
+        else
+            hipLaunchKernelGGL(apz::sym_fold_kernel<false>, grid, block, 0, e->stream, st.probs, st.values, st.k, e->perm_pinv, probs,
+                               values, n, e->hw);
+        HIP_TRY(hipGetLastError());
+    }
+    return APZ_OK;
+}
+
 // The tail of the synchronous host entry points: e->probs / e->values of n boards through the pinned staging buffers to
 // the caller.  Returns with the stream drained.
 int collect_to_host(apz_engine* e, int n, float* probs_host, float* values_host) {
@@ -1003,7 +1069,8 @@ int repeat_exact(apz_engine* e, int n, F run) {
     e->ovf_repeats++;
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    return m.measure_max ? lower_act_exponents(e, n) : APZ_OK;
+    // (the boards the repeat's own forward ran: n, or 8 n under APZ_SYM_MEAN8 -- forward_dev left them in last_n)
+    return m.measure_max ? lower_act_exponents(e, e->last_n) : APZ_OK;
 }
 
 // one measuring forward of n boards on the exact-fp32 kernels (`run(mode)` stages and queues it), then the exponents from
@@ -1282,6 +1349,12 @@ void apz_destroy(apz_engine* e) {
                    e->wfc_raw, e->amax_dev, e->gather_entries, e->fplanes};
     for (void* p : dev)
         if (p) hipFree(p);
+    if (e->perm_pinv) hipFree(e->perm_pinv);
+    for (auto& st : e->sym) {
+        void* stage[] = {st.codes, st.k, st.probs, st.values};
+        for (void* p : stage)
+            if (p) hipFree(p);
+    }
     e->w3s.release();
     e->w3hs.release();
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1469,11 +1542,12 @@ int apz_forward_codes_async(apz_engine* e, const uint8_t* codes_pinned, int n, f
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (e->cfg.c_in != 9 && e->cfg.c_in != 4) return fail(APZ_E_STATE, "bad c_in");
     if (n == 0) return APZ_OK;
+    if (int rc = sym_batch_ok(e, n)) return rc;
     HIP_TRY(hipSetDevice(e->cfg.device));
     const size_t hw = e->hw;
     HIP_TRY(hipMemcpyAsync(e->codes, codes_pinned, (size_t)n * e->code_stride, hipMemcpyHostToDevice, e->stream));
     // (APZ_ARITH_F16X2: the forward is collected here, see forward_guarded -- the copies below are queued behind it)
-    int rc = forward_guarded(e, n, [&](const FwdMode& m) { return forward_from_codes(e, m, e->codes, n, e->probs, e->values); });
+    int rc = forward_guarded(e, n, [&](const FwdMode& m) { return forward_codes_sym(e, m, APZ_MAX_SLOTS, e->codes, n, e->probs, e->values); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(probs_pinned, e->probs, n * hw * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(values_pinned, e->values, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1485,9 +1559,10 @@ int apz_forward_codes_host(apz_engine* e, const uint8_t* codes_host, int n, floa
     EngineLock guard(e->submit_lock);
     if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
     if (n == 0) return APZ_OK;
+    if (int rc = sym_batch_ok(e, n)) return rc;
     HIP_TRY(hipSetDevice(e->cfg.device));
     if (int rc = stage_codes(e, codes_host, n)) return rc;
-    return forward_to_host(e, n, [&](const FwdMode& m) { return forward_from_codes(e, m, e->codes, n, e->probs, e->values); },
+    return forward_to_host(e, n, [&](const FwdMode& m) { return forward_codes_sym(e, m, APZ_MAX_SLOTS, e->codes, n, e->probs, e->values); },
                            probs_host, values_host);
 }
 
@@ -1502,6 +1577,7 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     HIP_TRY(hipSetDevice(e->cfg.device));
     apz_engine::Slot& sl = e->slots[slot];
     if (sl.busy) return fail(APZ_E_STATE, "slot still in flight: call apz_wait first");
+    if (int rc = sym_batch_ok(e, n)) return rc;
     const size_t B = e->cfg.max_batch, hw = e->hw;
     if (!sl.h_codes) {
         // Zero-copy slots: the 240-B/leaf codes and the 904-B/leaf results live in pinned,
@@ -1520,14 +1596,14 @@ int apz_submit_codes(apz_engine* e, int slot, const uint8_t* codes_host, int n) 
     // (the codes are read straight from the pinned slot)
     const FwdMode m = armed(e, slot);                         // the slot's overflow word: read by apz_wait
     if (m.ovf) e->ovf_host[slot] = 0;
-    auto launch_all = [&]() { return forward_from_codes(e, m, sl.d_codes, n, sl.d_probs, sl.d_values); };
+    auto launch_all = [&]() { return forward_codes_sym(e, m, slot, sl.d_codes, n, sl.d_probs, sl.d_values); };
     int rc = APZ_OK;
     const long key = ((long)slot << 32) | (long)n;
     const bool graphable = e->use_graphs && !e->profiling && n <= FWD_GRAPH_MAX_BOARDS && e->loaded;
     auto it = graphable ? e->fwd_graphs.find(key) : e->fwd_graphs.end();
     if (it != e->fwd_graphs.end()) {
         HIP_TRY(hipGraphLaunch(it->second, e->stream));
-        e->last_n = n;
+        e->last_n = e->sym_mode == APZ_SYM_MEAN8 ? 8 * n : n;
     } else if (graphable && ++e->fwd_seen[key] >= 3 && !e->w3s.near_wrap() && !e->w3hs.near_wrap()) {
         // (third use: every lazy allocation / attribute / ticket reset of this shape has happened outside the capture --
         // need_lds is per kernel, and the two plain submissions before this one launched the kernels the capture launches:
@@ -1577,7 +1653,7 @@ int apz_wait(apz_engine* e, int slot, float* probs_host, float* values_host) {
         // an activation of this batch left the fp16 range (trunk15_wino3h.h): the same batch again on the exact-fp32 kernel
         EngineLock guard(e->submit_lock);
         e->ovf_host[slot] = 0;
-        int rc = repeat_exact(e, sl.n, [&](const FwdMode& m) { return forward_from_codes(e, m, sl.d_codes, sl.n, sl.d_probs, sl.d_values); });
+        int rc = repeat_exact(e, sl.n, [&](const FwdMode& m) { return forward_codes_sym(e, m, slot, sl.d_codes, sl.n, sl.d_probs, sl.d_values); });
         if (rc) return rc;
     }
     std::memcpy(probs_host, sl.h_probs, (size_t)sl.n * e->hw * sizeof(float));
@@ -2697,6 +2773,48 @@ int apz_set_trunk_uniform(apz_engine* e, int on) {
         e->fwd_seen.clear();                      // ... and the next capture waits until this route's lazy set-up has happened
     }
     e->uniform_trunk = on != 0;
+    return APZ_OK;
+}
+
+int apz_set_leaf_symmetry(apz_engine* e, int mode, uint64_t seed) {
+    if (!e) return fail(APZ_E_ARG, "null engine");
+    if (mode != APZ_SYM_NONE && mode != APZ_SYM_KEYED && mode != APZ_SYM_MEAN8)
+        return fail(APZ_E_ARG, "leaf symmetry mode must be APZ_SYM_NONE (0), APZ_SYM_KEYED (1) or APZ_SYM_MEAN8 (2), not " +
+                                   std::to_string(mode));
+    EngineLock guard(e->submit_lock);
+    if (!e->perm_p || e->cfg.height != e->cfg.width) return fail(APZ_E_UNSUPPORTED, "leaf symmetry needs a square board");
+    if (e->code_stride > apz::LeafSym::MAX_STRIDE || e->code_stride % 16)     // (sym_expand_kernel's LDS row, its 16-byte loads)
+        return fail(APZ_E_UNSUPPORTED, "leaf symmetry: the code row does not fit the expand kernel");
+    for (const auto& sl : e->slots)
+        if (sl.busy) return fail(APZ_E_STATE, "leaf symmetry: a slot is still in flight: call apz_wait first");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (mode != APZ_SYM_NONE && !e->perm_pinv) {
+        std::vector<int> ps, pp;
+        build_perms(e->cfg.height, ps, pp);
+        std::vector<int> inv(pp.size());
+        for (int k = 0; k < 8; k++)
+            for (int p = 0; p < e->hw; p++) inv[(size_t)k * e->hw + pp[(size_t)k * e->hw + p]] = p;
+        if (int rc = upload(&e->perm_pinv, inv)) return rc;
+    }
+    drop_forward_graphs(e);                       // a captured launch sequence holds the other mode's launches and the old seed
+    e->sym_mode = mode;
+    e->sym_seed = seed;
+    return APZ_OK;
+}
+
+int apz_get_leaf_symmetry(apz_engine* e, int* mode, uint64_t* seed) {
+    if (!e || !mode || !seed) return fail(APZ_E_ARG, "null argument");
+    EngineLock guard(e->submit_lock);
+    *mode = e->sym_mode;
+    *seed = e->sym_seed;
+    return APZ_OK;
+}
+
+int apz_leaf_symmetry_keys(const uint8_t* codes_host, int n, int hw, int stride, uint64_t seed, uint8_t* k_out) {
+    if (n < 0 || hw < 1 || stride <= hw) return fail(APZ_E_ARG, "leaf symmetry keys: need n >= 0, hw >= 1 and stride > hw");
+    if (n > 0 && (!codes_host || !k_out)) return fail(APZ_E_ARG, "null argument");
+    for (int b = 0; b < n; b++)
+        k_out[b] = (uint8_t)apz::leaf_sym_key(seed, codes_host + (size_t)b * stride, hw, 0, 1, [](uint64_t sum) { return sum; });
     return APZ_OK;
 }
 

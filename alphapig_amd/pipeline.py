@@ -14,6 +14,9 @@ kl_targ, check_freq, pure_mcts_playout_num, game_batch_num, play_batch_size, sgf
                        host for the rows a mini-batch draws.  "device": the same ring in the trainer's device memory, the
                        mini-batch gathered there by a kernel and handed to the trainer and the KL monitor without crossing
                        PCIe.  Same draws, same mini-batch bits in all three; square boards only for the last two.
+    leaf_symmetry, arena_symmetry, symmetry_seed
+                       the dihedral leaf symmetry ("none", "keyed", "mean8": PolicyValueNet) of the self-play evaluator and
+                       of the evaluator the arena plays with, and the seed of "keyed" (default: the run's seed)
 
 One `game batch` of the reference = ONE self-play game followed by a policy update; here a batch
 collects `play_batch_size` games from the engine, which keeps `concurrent_games` running so that
@@ -78,7 +81,7 @@ from . import checkpoint, dist, sgf
 from .arena import Arena, win_ratio
 from .augment import get_equi_data
 from .game import Board, Game
-from .policy_value_net import EvaluatorError, PolicyValueNet
+from .policy_value_net import EvaluatorError, PolicyValueNet, check_leaf_symmetry
 from .selfplay import SelfPlayEngine, episodes_to_tuples
 from .train import policy_update
 
@@ -181,6 +184,23 @@ class TrainPipeline(object):
         # small-batch f16x2 kernel, so that a game's bits do not depend on how many games share a forward
         # (PolicyValueNet's uniform_trunk).  The trainer's internal evaluator is not concerned.
         self.uniform_trunk = bool(conf.get("uniform_trunk", False))
+        # leaf_symmetry / arena_symmetry ("none" (default), "keyed", "mean8": PolicyValueNet's leaf_symmetry): how the
+        # self-play evaluator / the evaluator the arena plays with use the eight dihedral images of a position;
+        # symmetry_seed: the seed of "keyed", by default the run's.  An evaluator that is asked for a mode other than "none"
+        # needs set_leaf_symmetry (ValueError otherwise); with "none" it is never called.  Where the arena plays with the
+        # self-play evaluator itself (lock step), it holds arena_symmetry for the arena's duration only.
+        self.leaf_symmetry = check_leaf_symmetry(conf.get("leaf_symmetry", "none"), "leaf_symmetry")
+        self.arena_symmetry = check_leaf_symmetry(conf.get("arena_symmetry", "none"), "arena_symmetry")
+        self.symmetry_seed = int(conf.get("symmetry_seed", seed))
+        for net, mode, key in ((policy_value_net, self.leaf_symmetry, "leaf_symmetry"),
+                               (eval_net if eval_net is not None else policy_value_net, self.arena_symmetry, "arena_symmetry")):
+            if net is not None and mode != "none" and not hasattr(net, "set_leaf_symmetry"):
+                raise ValueError("%s=%r needs an evaluator with set_leaf_symmetry; %r has none" % (key, mode, net))
+        if (self.async_update and self.arena_symmetry != self.leaf_symmetry and policy_value_net is not None and
+                trainer is not None and (eval_net is None or eval_net is policy_value_net)):
+            raise ValueError("arena_symmetry=%r differs from leaf_symmetry=%r, and the asynchronous schedule's arena would play "
+                             "with the self-play evaluator while it is in use: pass eval_net" %
+                             (self.arena_symmetry, self.leaf_symmetry))
         # replay: what the replay buffer stores (module docstring)
         self.replay = conf.get("replay", "tuples")
         if self.replay not in ("tuples", "compact", "device"):
@@ -242,7 +262,10 @@ class TrainPipeline(object):
         self.policy_value_net = policy_value_net or PolicyValueNet(
             self.board_width, self.board_height, max(self.batch_size, (concurrent + 1) // 2),
             n_blocks=conf.get("n_blocks", 10), n_filter=conf.get("n_filter", 128), model_params=init_model,
-            device=device, seed=seed, uniform_trunk=self.uniform_trunk)
+            device=device, seed=seed, uniform_trunk=self.uniform_trunk, leaf_symmetry=self.leaf_symmetry,
+            symmetry_seed=self.symmetry_seed)
+        if self._custom_net and self.leaf_symmetry != "none":
+            self.policy_value_net.set_leaf_symmetry(self.leaf_symmetry, self.symmetry_seed)
         self.engine = SelfPlayEngine(self.policy_value_net, self.board_width, self.board_height, self.n_in_row,
                                      n_games=concurrent, n_playout=self.n_playout, c_puct=self.c_puct,
                                      temp=self.temp, base_seed=seed, pipeline=2,
@@ -432,9 +455,22 @@ class TrainPipeline(object):
 
     def policy_evaluate(self, n_games=None, net=None):
         """train_mxnet.py:242-263: win ratio of the current net against pure MCTS."""
-        res = Arena(net or self.policy_value_net, self.board_width, self.board_height, self.n_in_row,
-                    n_playout=self.n_playout, c_puct=self.c_puct, pure_mcts_playout_num=self.pure_mcts_playout_num,
-                    base_seed=len(self.history)).play(n_games or self.eval_games)
+        net = net or self.policy_value_net
+        # the arena's evaluator holds arena_symmetry while the arena plays, and what it held before afterwards (the self-play
+        # evaluator of the lock-step schedule: between two run_steps calls no slot is in flight)
+        held = getattr(net, "leaf_symmetry", "none")
+        switch = held != self.arena_symmetry
+        if switch and not hasattr(net, "set_leaf_symmetry"):
+            raise ValueError("arena_symmetry=%r needs an evaluator with set_leaf_symmetry; %r has none" % (self.arena_symmetry, net))
+        if switch:
+            net.set_leaf_symmetry(self.arena_symmetry, self.symmetry_seed)
+        try:
+            res = Arena(net, self.board_width, self.board_height, self.n_in_row,
+                        n_playout=self.n_playout, c_puct=self.c_puct, pure_mcts_playout_num=self.pure_mcts_playout_num,
+                        base_seed=len(self.history)).play(n_games or self.eval_games)
+        finally:
+            if switch:
+                net.set_leaf_symmetry(held, self.symmetry_seed)
         return win_ratio(res)
 
     def run(self):
@@ -515,6 +551,8 @@ class TrainPipeline(object):
                "training_data": list(self._training_data), "history": list(self.history),
                "checkpoint_selfplay": self.checkpoint_selfplay,
                "eval_trunk_overflows": self._eval_overflows0 + (int(net.trunk_overflows()) if hasattr(net, "trunk_overflows") else 0)}
+        if self.leaf_symmetry != "none" or self.arena_symmetry != "none":     # (a run without them writes what it always wrote)
+            out.update(leaf_symmetry=self.leaf_symmetry, arena_symmetry=self.arena_symmetry, symmetry_seed=self.symmetry_seed)
         if hasattr(net, "trunk_act_exponents"):
             try:
                 out["act_exponents"] = [int(a) for a in net.trunk_act_exponents()]
@@ -560,7 +598,15 @@ class TrainPipeline(object):
                                  (path, k, state["conf"].get(k), k, mine))
         if bool(state["async_update"]) != self.async_update:
             raise ValueError("the checkpoint %s was written with async_update=%r" % (path, state["async_update"]))
-        part = "selfplay_rank%d" % self.rank
+        # (a checkpoint from before the leaf symmetries, or of a run without them, has no such keys: "none")
+        for k in ("leaf_symmetry", "arena_symmetry"):
+            if state.get(k, "none") != getattr(self, k):
+                raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
+                                 (path, k, state.get(k, "none"), k, getattr(self, k)))
+        if "symmetry_seed" in state and int(state["symmetry_seed"]) != self.symmetry_seed:
+            raise ValueError("the checkpoint %s was written with symmetry_seed=%r, this pipeline has symmetry_seed=%r" %
+                             (path, state["symmetry_seed"], self.symmetry_seed))
+        part ="selfplay_rank%d" % self.rank
         if not checkpoint.has_part(path, part):
             raise ValueError("the checkpoint %s has no part %s" % (path, part))
         self.engine.load_state(checkpoint.read_part(path, part))

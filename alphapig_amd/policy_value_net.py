@@ -19,6 +19,14 @@ from . import _native, weights
 from ._native import ApzConfig, as_ptr
 
 KERNEL_CLASSES = {"stem": 0, "trunk": 1, "head_conv": 2, "head_fc": 3, "encode": 4, "forward": 5}
+LEAF_SYMMETRIES = {"none": 0, "keyed": 1, "mean8": 2}        # APZ_SYM_*
+
+
+def check_leaf_symmetry(mode, what="leaf_symmetry"):
+    """-> mode, one of LEAF_SYMMETRIES; anything else is a ValueError (raised before any native call)."""
+    if not isinstance(mode, str) or mode not in LEAF_SYMMETRIES:
+        raise ValueError("%s must be 'none', 'keyed' or 'mean8', not %r" % (what, mode))
+    return mode
 
 
 class EvaluatorError(RuntimeError):
@@ -53,7 +61,7 @@ def act_exponent_for(m, k_min=None, k_max=None):
 class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
-                 uniform_trunk=False):
+                 uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -71,7 +79,17 @@ class PolicyValueNet(object):
         form of the f16x2 kernel (csrc/trunk15_wino3hs.h, bit-equal to the batched kernel) instead of the exact-fp32 one, so
         a position's bits no longer depend on how many boards share its forward (apz_set_trunk_uniform; forwards that
         overflow are repeated on the exact kernel for the whole batch).  No effect with "f32" and on 8x8 boards (already
-        uniform); EvaluatorError with "bf16x3"."""
+        uniform); EvaluatorError with "bf16x3".
+        leaf_symmetry (square boards; set_leaf_symmetry changes it later): how evaluate_codes, the slot calls and the
+        position_codes path of policy_value_fn use the eight dihedral images the net was trained on (apz_set_leaf_symmetry):
+          "none"   (default) one orientation, as stored: the engine launches what it always launched;
+          "keyed"  every position on the one image k = leaf_symmetry_keys(codes, symmetry_seed) picks for it, folded back: one
+                   forward, and the answer stays a function of (weights, symmetry_seed, position) only;
+          "mean8"  the mean of the eight folded answers, from ONE forward of 8 n boards: equivariant by construction.  The
+                   engine is then created with max_batch = 8 * batch_size, `batchsize` stays the caller's, and the trunk
+                   arithmetic a batch gets is that of 8 n boards (five positions under "auto": a 40-board f16x2 forward).
+        forward_planes / policy_value (the KL monitor, calibrate_trunk, prewarm) are not concerned."""
+        check_leaf_symmetry(leaf_symmetry)
         self.L = _native.hip()
         self.board_width, self.board_height = int(board_width), int(board_height)
         self.batchsize = int(batch_size)
@@ -82,8 +100,9 @@ class PolicyValueNet(object):
         self.hw = self.board_width * self.board_height
         self.code_stride = (self.hw + 1 + 15) // 16 * 16
         kind = {"resnet": 0, "simple": 1}[net_kind]
+        self._max_batch = self.batchsize * (8 if leaf_symmetry == "mean8" else 1)
         cfg = ApzConfig(self.board_height, self.board_width, self.channelnum, self._n_filter, self._n_blocks,
-                        kind, self.batchsize, int(device))
+                        kind, self._max_batch, int(device))
         self._fn_lock = threading.Lock()      # policy_value_fn: one submit + wait pair on the latency slot at a time
         self._h = self.L.apz_create(C.byref(cfg))
         if not self._h:
@@ -104,6 +123,9 @@ class PolicyValueNet(object):
         self.uniform_trunk = bool(uniform_trunk)
         if self.uniform_trunk:
             self._ck(self.L.apz_set_trunk_uniform(self._h, 1))
+        self.leaf_symmetry, self.symmetry_seed = "none", int(symmetry_seed) & (2 ** 64 - 1)
+        if leaf_symmetry != "none":
+            self.set_leaf_symmetry(leaf_symmetry)
         if model_params is None:
             model_params = weights.init_params(net_kind, self.board_height, self.board_width, self.channelnum,
                                                self._n_blocks, self._n_filter, seed=seed, style=init_style)
@@ -270,12 +292,29 @@ class PolicyValueNet(object):
         n = c.shape[0]
         probs = np.empty((n, self.hw), dtype=np.float32)
         vals = np.empty(n, dtype=np.float32)
-        for s in range(0, n, self.batchsize):
-            k = min(self.batchsize, n - s)
+        step = self._codes_chunk()
+        for s in range(0, n, step):
+            k = min(step, n - s)
             self._ck(self.L.apz_forward_codes_host(self._h, as_ptr(c[s:s + k], C.c_uint8), k,
                                                    as_ptr(probs[s:s + k], C.c_float),
                                                    as_ptr(vals[s:s + k], C.c_float)))
         return probs, vals
+
+    # ---- dihedral leaf symmetry (apz_set_leaf_symmetry; csrc/leaf_sym.h)
+    def set_leaf_symmetry(self, mode, seed=None):
+        """mode "none", "keyed" or "mean8" (see __init__); seed None keeps the current symmetry_seed.  Not while a slot is
+        in flight (EvaluatorError).  A net that was not created with "mean8" takes it too, for batches of up to
+        max_batch // 8 positions per forward: evaluate_codes splits larger ones, a larger slot batch is refused."""
+        check_leaf_symmetry(mode)
+        seed = self.symmetry_seed if seed is None else int(seed) & (2 ** 64 - 1)
+        self._ck(self.L.apz_set_leaf_symmetry(self._h, LEAF_SYMMETRIES[mode], seed))
+        self.leaf_symmetry, self.symmetry_seed = mode, seed
+
+    def _codes_chunk(self):
+        """positions per forward of the code entry points: batchsize, or what 8 images each leave room for"""
+        if self.leaf_symmetry != "mean8":
+            return self.batchsize
+        return max(1, min(self.batchsize, self._max_batch // 8))
 
     # ---- stream-ordered slots: a second batch queued while the first runs (selfplay pipeline).  The engine has
     # APZ_MAX_SLOTS = 4 of them; SelfPlayEngine's pipeline groups use slots 0 .. n_slots - 1, the last one is reserved for
@@ -287,7 +326,7 @@ class PolicyValueNet(object):
         """submit + wait on one slot; safe to call from one host thread per slot."""
         c = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, self.code_stride)
         n = c.shape[0]
-        if n > self.batchsize or n == 0:
+        if n > self._codes_chunk() or n == 0:
             return self.evaluate_codes(c)
         probs = np.empty((n, self.hw), dtype=np.float32)
         vals = np.empty(n, dtype=np.float32)
@@ -487,6 +526,8 @@ class LanedEvaluator(object):
     @classmethod
     def like(cls, net, n_lanes, **kw):
         kw.setdefault("uniform_trunk", net.uniform_trunk)      # the lanes compute the bits of the net they stand beside
+        kw.setdefault("leaf_symmetry", net.leaf_symmetry)
+        kw.setdefault("symmetry_seed", net.symmetry_seed)
         """`net` plus n_lanes - 1 more PolicyValueNet handles built from its parameters."""
         extra = [PolicyValueNet(net.board_width, net.board_height, net.batchsize, n_blocks=net._n_blocks,
                                 n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, c_in=net.channelnum, device=net._device,
@@ -552,6 +593,12 @@ class LanedEvaluator(object):
     def set_act_scale_auto(self, on):
         for ln in self.lanes:
             ln.set_act_scale_auto(on)
+
+    def set_leaf_symmetry(self, mode, seed=None):
+        """Every lane: a position's answer does not depend on the lane that gives it."""
+        check_leaf_symmetry(mode)
+        for ln in self.lanes:
+            ln.set_leaf_symmetry(mode, seed)
 
     def params(self):
         return self.lanes[0].params()

@@ -372,6 +372,37 @@ int apz_layer_frame(apz_engine *e, int layer, float *host_out, int64_t count);
  * submission of a (slot, batch size) pair on (results unchanged: the same kernels with the same arguments).  Default: off
  * -- measured slower than the plain launches on ROCm 7.2 (profiles/r04_graph_ab.log). */
 int apz_set_forward_graphs(apz_engine *e, int on);
+/* Dihedral leaf symmetry of the entry points that forward position codes for a caller (apz_forward_codes_host,
+ * apz_forward_codes_async, apz_submit_codes / apz_wait, the exact repeat of an overflowed batch included); csrc/leaf_sym.h.
+ * The net is trained on all eight dihedral images of every position (apz_augment8, apz_replay_gather); by default it is
+ * evaluated in one orientation.  Image k of a code row, k = 0 .. 7 in apz_augment8's order (6 = identity): the code row of
+ * that image of the position.  If the net answers q_k on image k, the position's policy is probs[perm_p[k][p]] = q_k[p]
+ * (perm_p: the pi table of apz_augment8) and its value is unchanged: "folding back".
+ *   APZ_SYM_NONE   (default) the engine launches exactly what it launched before this call existed.
+ *   APZ_SYM_KEYED  every board is evaluated on ONE image, k = key(seed, its H*W + 1 code bytes) (apz_leaf_symmetry_keys),
+ *                  and folded back: one forward of n boards plus two short launches.  The answer stays a function of
+ *                  (weights, seed, position): not of the batch, the row, the slot, the game or the rank.
+ *   APZ_SYM_MEAN8  board b becomes rows 8b .. 8b + 7 of ONE forward of 8 n boards (image k in row 8b + k); probs[m] =
+ *                  0.125f * (((((((u_0 + u_1) + u_2) + u_3) + u_4) + u_5) + u_6) + u_7) with u_k the folded policy of image k,
+ *                  plain fp32 adds in that order, the value likewise from the eight tanh outputs: equivariant by
+ *                  construction.  Needs 8 n <= max_batch (else APZ_E_ARG, the message says so), and the arithmetic a batch
+ *                  gets (apz_set_trunk_arith, apz_set_trunk_uniform) is that of 8 n boards: five positions are a 40-board
+ *                  forward.
+ * Timed in the APZ_K_ENCODE class.  Takes effect from the next forward; HIP graphs are dropped and captured again.
+ * The planes entry points, apz_forward_dev_host, calibration, apz_prewarm, apz_layer_io and apz_conv3x3_bench are not
+ * concerned (after a forward under APZ_SYM_MEAN8, apz_layer_io speaks of its 8 n image rows).
+ * APZ_E_ARG for another mode, APZ_E_STATE while a slot is in flight, APZ_E_UNSUPPORTED on a non-square board. */
+#define APZ_SYM_NONE 0
+#define APZ_SYM_KEYED 1
+#define APZ_SYM_MEAN8 2
+int apz_set_leaf_symmetry(apz_engine *e, int mode, uint64_t seed);
+int apz_get_leaf_symmetry(apz_engine *e, int *mode, uint64_t *seed);
+/* The image index APZ_SYM_KEYED uses for each of n code rows (codes_host [n][stride], hw = H*W < stride), with
+ *   fmix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ *   t_i = fmix64(seed + 0x9E3779B97F4A7C15 * (256 * i + byte_i + 1))   i = 0 .. hw, all mod 2^64
+ *   k   = fmix64(seed ^ (sum_i t_i mod 2^64)) >> 61
+ * -> k_out [n], each 0 .. 7.  Takes no engine and needs no GPU: the function the kernel runs, compiled for the host. */
+int apz_leaf_symmetry_keys(const uint8_t *codes_host, int n, int hw, int stride, uint64_t seed, uint8_t *k_out);
 int apz_set_profiling(apz_engine *e, int on);
 /* TEST HOOK.  The 15x15 / 128-filter residual net has two trunk convolution kernels: the fused F(4x4,3x3) Winograd kernel
  * (default, csrc/trunk15_wino3.h) and the direct convolution (csrc/trunk15_ring.h) that the tests use as the in-tree
