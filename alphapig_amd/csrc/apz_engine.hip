@@ -130,6 +130,32 @@ struct TicketExchange {
     }
 };
 
+// A device buffer that grows on demand: the training entry points' scratch.  Growth waits for the device first (whatever
+// still reads the old block was queued by an earlier call), and a failed allocation leaves the buffer empty, not stale.
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+
+    int reserve(size_t need) {
+        if (need <= bytes) return APZ_OK;
+        HIP_TRY(hipDeviceSynchronize());
+        if (ptr) HIP_TRY(hipFree(ptr));
+        ptr = nullptr;
+        bytes = 0;
+        HIP_TRY(hipMalloc(&ptr, need));
+        bytes = need;
+        return APZ_OK;
+    }
+    template <class T>
+    T* as() const { return (T*)ptr; }
+    operator void*() const { return ptr; }   // (hipMemcpyAsync(e->adam_tab, ...): a copy's error text names the buffer as before)
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+};
+
 }  // namespace
 
 struct apz_engine {
@@ -202,19 +228,15 @@ struct apz_engine {
     uint64_t* smp_keys = nullptr;
     size_t smp_cap = 0;
     float* zeros256 = nullptr;          // bias stand-in for bias-free convolutions (ensure_zeros256)
-    double* bn_part = nullptr;                     // apz_bn_fwd / _bwd: per-(channel, batch split) partial sums [256 * BN_SPLITS][2]
-    float* wgw_scratch = nullptr;                  // apz_wgrad_wino: partial dU per batch slice
     double* fold_ws = nullptr;                     // pack_all: scale / shift of one layer (2 x cmax doubles)
     float* stage = nullptr;                        // apz_load_weights: the host tensors, back to back in table order
-    float* head_scratch = nullptr;                 // apz_conv1x1_bwd / apz_pv_loss: per-board partial sums
-    size_t head_scratch_floats = 0;
-    size_t wgw_floats = 0;                         // capacity of wgw_scratch
-    void* adam_tab = nullptr;                      // apz_adam_step: device copy of the tensor table
-    size_t adam_cap = 0;
-    int32_t* gather_entries = nullptr;             // apz_replay_gather: device copy of the entry words
-    size_t gather_cap = 0;
-    float* wino_scratch[2] = {nullptr, nullptr};   // apz_wino_conv: rows16 input / output copies
-    size_t wino_scratch_boards = 0;
+    // the training entry points' scratch (train_call keeps two streams from working on it at once)
+    DeviceBuffer bn_part;                          // apz_bn_fwd / _bwd: per-(channel, batch split) partial sums [256 * BN_SPLITS][2]
+    DeviceBuffer wgw_scratch;                      // the weight gradients' partial sums per batch slice
+    DeviceBuffer head_scratch;                     // apz_conv1x1_bwd2 / apz_bias_grad / apz_pv_loss: per-board partial sums
+    DeviceBuffer adam_tab;                         // apz_adam_step: device copy of the tensor table
+    DeviceBuffer gather_entries;                   // apz_replay_gather: device copy of the entry words
+    DeviceBuffer wino_scratch[2];                  // apz_wino_conv: rows16 input / output copies
     hipStream_t scratch_stream = nullptr;          // the stream of the last entry point that may have used the scratch buffers
     bool scratch_stream_valid = false;
     TicketExchange<apz::Wino3S> w3s;         // trunk15_wino3s_kernel
@@ -1313,6 +1335,45 @@ int pack_all(apz_engine* e, const ParamPtrs& P, hipStream_t st) {
 
 }  // namespace
 
+namespace {
+struct StreamScope {      // run the engine's launch helpers on a caller-supplied stream
+    apz_engine* e;
+    hipStream_t saved;
+    StreamScope(apz_engine* e_, void* s) : e(e_), saved(e_->stream) {
+        if (s != APZ_ENGINE_STREAM) e->stream = (hipStream_t)s;   // NULL is a valid handle: the null stream
+        // The training entry points share per-engine scratch (the DeviceBuffers of apz_engine: bn_part, wgw_scratch,
+        // head_scratch, adam_tab, gather_entries, wino_scratch; and fold_ws).  Calls on ONE stream are ordered by the
+        // stream; a caller that switches streams gets the new stream ordered behind everything queued on the previous
+        // one, so two streams never work on the scratch at once.
+        if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
+        e->scratch_stream = e->stream;
+        e->scratch_stream_valid = true;
+    }
+    ~StreamScope() { e->stream = saved; }
+};
+
+// The scope of a training entry point: the engine's lock, its device made current, `stream` in place of the engine's own
+// -- in that order (StreamScope records events on the current device, and it is what keeps two streams off the shared
+// scratch) -- then `body() -> int`, and after a body that succeeded the verdict of hipGetLastError.
+template <class F>
+int train_call(apz_engine* e, void* stream, F body) {
+    EngineLock guard(e->submit_lock);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    StreamScope sc(e, stream);
+    if (int rc = body()) return rc;
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+// A runtime flag as a template argument: f(std::true_type{}) or f(std::false_type{}), each kernel and launch written once
+template <class F>
+auto with_flag(bool flag, F f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+}  // namespace
+
 extern "C" {
 
 const char* apz_last_error(void) { return g_err.c_str(); }
@@ -1345,10 +1406,12 @@ void apz_destroy(apz_engine* e) {
     }
     void* dev[] = {e->w6, e->b6, e->wfc_pk, e->bfc, e->wv, e->bv, e->act[0], e->act[1], e->act[2], e->planes,
                    e->featp, e->featv, e->probs, e->values, e->codes, e->perm_s, e->perm_p, e->smp_vis, e->smp_pi, e->smp_mv, e->zeros256,
-                   e->wino_scratch[0], e->wino_scratch[1], e->bn_part, e->adam_tab, e->wgw_scratch, e->head_scratch, e->fc_logits, e->fold_ws, e->stage,
-                   e->wfc_raw, e->amax_dev, e->gather_entries, e->fplanes};
+                   e->fc_logits, e->fold_ws, e->stage, e->wfc_raw, e->amax_dev, e->fplanes};
     for (void* p : dev)
         if (p) hipFree(p);
+    for (DeviceBuffer* b : {&e->bn_part, &e->wgw_scratch, &e->head_scratch, &e->adam_tab, &e->gather_entries,
+                            &e->wino_scratch[0], &e->wino_scratch[1]})
+        b->release();
     if (e->perm_pinv) hipFree(e->perm_pinv);
     for (auto& st : e->sym) {
         void* stage[] = {st.codes, st.k, st.probs, st.values};
@@ -1749,23 +1812,6 @@ int64_t apz_conv3x3_packed_size(int cin_p, int cout_p) {
     return (int64_t)(cout_p / 16) * ((cin_p + 3) / 4) * 9 * 64;
 }
 
-namespace {
-struct StreamScope {      // run the engine's launch helpers on a caller-supplied stream
-    apz_engine* e;
-    hipStream_t saved;
-    StreamScope(apz_engine* e_, void* s) : e(e_), saved(e_->stream) {
-        if (s != APZ_ENGINE_STREAM) e->stream = (hipStream_t)s;   // NULL is a valid handle: the null stream
-        // The training entry points share per-engine scratch (head_scratch, bn_part, fold_ws, wgw_scratch, wino_scratch,
-        // adam_tab).  Calls on ONE stream are ordered by the stream; a caller that switches streams gets the new stream
-        // ordered behind everything queued on the previous one, so two streams never work on the scratch at once.
-        if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
-        e->scratch_stream = e->stream;
-        e->scratch_stream_valid = true;
-    }
-    ~StreamScope() { e->stream = saved; }
-};
-}  // namespace
-
 // The same as apz_load_weights for tensors that already live in DEVICE memory (the trainer's): pack_all runs on `stream`
 // (APZ_ENGINE_STREAM: the engine's own) without a host synchronisation, and the engine's stream waits for it.  The buffers
 // are those of the engine's first apz_load_weights.
@@ -1800,14 +1846,12 @@ int apz_conv3x3_pack(apz_engine* e, const void* w_dev, int cin, int cout, int tr
     if (!e || !w_dev || !wpk_dev || cin < 1 || cout < 1) return fail(APZ_E_ARG, "bad argument");
     const int co_p = transpose_flip ? cin : cout;
     if (co_p % 16) return fail(APZ_E_UNSUPPORTED, "packed C_out must be a multiple of 16");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const long total = apz_conv3x3_packed_size(transpose_flip ? cout : cin, co_p);
-    hipLaunchKernelGGL(apz::pack_conv3x3_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0,
-                       e->stream, (const float*)w_dev, (float*)wpk_dev, cin, cout, transpose_flip);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const long total = apz_conv3x3_packed_size(transpose_flip ? cout : cin, co_p);
+        hipLaunchKernelGGL(apz::pack_conv3x3_kernel, dim3((int)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0,
+                           e->stream, (const float*)w_dev, (float*)wpk_dev, cin, cout, transpose_flip);
+        return APZ_OK;
+    });
 }
 
 int apz_conv3x3_fwd(apz_engine* e, const void* x_dev, const void* wpk_dev, const void* bias_dev, void* y_dev, int n,
@@ -1815,59 +1859,52 @@ int apz_conv3x3_fwd(apz_engine* e, const void* x_dev, const void* wpk_dev, const
     if (!e || !x_dev || !wpk_dev || !y_dev || n < 1 || cin_p < 1) return fail(APZ_E_ARG, "bad argument");
     if (cout_p != 64 && cout_p != 128 && cout_p != 256)
         return fail(APZ_E_UNSUPPORTED, "conv3x3_fwd: C_out must be 64, 128 or 256");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    if (int rc = ensure_zeros256(e)) return rc;
-    StreamScope sc(e, stream);
-    ConvLayer L;
-    L.cin = cin_p;
-    L.cin_pad = (cin_p + 3) / 4 * 4;
-    L.cout = cout_p;
-    L.residual = false;
-    L.wpk = (float*)wpk_dev;
-    L.bias = bias_dev ? (float*)bias_dev : e->zeros256;
-    const int H = e->cfg.height, W = e->cfg.width;
-    // small batches: split the output channels over 2 or 4 workgroups per board so that
-    // boards x groups covers the CUs (each group stages the board's input itself)
-    int groups = 1;
-    while (groups * 64 < cout_p && n * groups * 2 <= e->num_cu * 2 && n * groups < e->num_cu) groups *= 2;
-    const int ct = cout_p / 64 / groups;
-    int rc = APZ_E_UNSUPPORTED;
-#define APZ_DENSE(HH, WW, CT) rc = launch_conv_r<HH, WW, CT, false>(e, L, (const float*)x_dev, nullptr, (float*)y_dev, n, HH * WW, WW, relu, groups)
-    if (H == 15 && W == 15) {
-        if (ct == 1) APZ_DENSE(15, 15, 1); else if (ct == 2) APZ_DENSE(15, 15, 2); else APZ_DENSE(15, 15, 4);
-    } else if (H == 8 && W == 8) {
-        if (ct == 1) APZ_DENSE(8, 8, 1); else if (ct == 2) APZ_DENSE(8, 8, 2); else APZ_DENSE(8, 8, 4);
-    }
-#undef APZ_DENSE
-    L.wpk = nullptr;
-    L.bias = nullptr;
-    if (rc == APZ_E_UNSUPPORTED) return fail(rc, "conv3x3_fwd: unsupported board size");
-    return rc;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = ensure_zeros256(e)) return rc;
+        ConvLayer L;
+        L.cin = cin_p;
+        L.cin_pad = (cin_p + 3) / 4 * 4;
+        L.cout = cout_p;
+        L.residual = false;
+        L.wpk = (float*)wpk_dev;
+        L.bias = bias_dev ? (float*)bias_dev : e->zeros256;
+        // small batches: split the output channels over 2 or 4 workgroups per board so that
+        // boards x groups covers the CUs (each group stages the board's input itself)
+        int groups = 1;
+        while (groups * 64 < cout_p && n * groups * 2 <= e->num_cu * 2 && n * groups < e->num_cu) groups *= 2;
+        const int ct = cout_p / 64 / groups;
+        auto dense = [&](auto S, auto CT) {      // a square board of side S, CT tiles of 64 output channels per workgroup
+            return launch_conv_r<S(), S(), CT(), false>(e, L, (const float*)x_dev, nullptr, (float*)y_dev, n, S() * S(), S(), relu,
+                                                        groups);
+        };
+        auto board = [&](auto S) { return ct == 1 ? dense(S, int_c<1>{}) : ct == 2 ? dense(S, int_c<2>{}) : dense(S, int_c<4>{}); };
+        const int H = e->cfg.height, W = e->cfg.width;
+        const int rc = H == 15 && W == 15 ? board(int_c<15>{}) : H == 8 && W == 8 ? board(int_c<8>{}) : APZ_E_UNSUPPORTED;
+        L.wpk = nullptr;
+        L.bias = nullptr;
+        if (rc == APZ_E_UNSUPPORTED) return fail(rc, "conv3x3_fwd: unsupported board size");
+        return rc;
+    });
 }
 
 int64_t apz_wino_packed_size(void) { return (int64_t)apz::WinoPack::UPK_FLOATS; }
 
 int apz_wino_pack(apz_engine* e, const void* w_dev, int transpose_flip, void* upk_dev, void* stream) {
     if (!e || !w_dev || !upk_dev) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::pack_wino2_kernel, dim3(8 * 2 * 32 * 64 / 256), dim3(256), 0, e->stream, (const float*)w_dev,
-                       (float*)upk_dev, transpose_flip);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        hipLaunchKernelGGL(apz::pack_wino2_kernel, dim3(8 * 2 * 32 * 64 / 256), dim3(256), 0, e->stream, (const float*)w_dev,
+                           (float*)upk_dev, transpose_flip);
+        return APZ_OK;
+    });
 }
 
 int apz_wino_pack_many(apz_engine* e, const void* w_dev, int count, void* upk_dev, void* stream) {
     if (!e || !w_dev || !upk_dev || count < 1 || count > 16384) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::pack_wino2_many_kernel, dim3(8 * 2 * 32 * 64 / 256, 2 * count), dim3(256), 0, e->stream,
-                       (const float*)w_dev, (float*)upk_dev);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        hipLaunchKernelGGL(apz::pack_wino2_many_kernel, dim3(8 * 2 * 32 * 64 / 256, 2 * count), dim3(256), 0, e->stream,
+                           (const float*)w_dev, (float*)upk_dev);
+        return APZ_OK;
+    });
 }
 
 int apz_wino_conv_add(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev, const void* resid_dev,
@@ -1875,41 +1912,32 @@ int apz_wino_conv_add(apz_engine* e, const void* x_dev, const void* upk_dev, con
     if (!e || !x_dev || !upk_dev || !y_dev || n < 1 || layout < 0 || layout > 1) return fail(APZ_E_ARG, "bad argument");
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wino_conv: 15x15 boards only");
     if (resid_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "wino_conv: residual input in the padded-row layout only");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    if (int rc = ensure_zeros256(e)) return rc;
-    StreamScope sc(e, stream);
-    if (layout == APZ_LAYOUT_DENSE && (size_t)n > e->wino_scratch_boards) {   // grow the rows16 copies (previous users are ordered on their stream)
-        HIP_TRY(hipDeviceSynchronize());
-        for (int i = 0; i < 2; i++) {
-            if (e->wino_scratch[i]) HIP_TRY(hipFree(e->wino_scratch[i]));
-            e->wino_scratch[i] = nullptr;
-            HIP_TRY(hipMalloc((void**)&e->wino_scratch[i], (size_t)n * 128 * 240 * sizeof(float)));
-        }
-        e->wino_scratch_boards = n;
-    }
-    const long planes = (long)n * 128;
-    const int cgrid = (int)std::min<long>((planes * 240 + 255) / 256, 16384);
-    const bool dense = layout == APZ_LAYOUT_DENSE;
-    const float* xin = dense ? e->wino_scratch[0] : (const float*)x_dev;
-    float* yout = dense ? e->wino_scratch[1] : (float*)y_dev;
-    if (dense)
-        hipLaunchKernelGGL(apz::rows16_from_dense_kernel, dim3(cgrid), dim3(256), 0, e->stream, (const float*)x_dev,
-                           e->wino_scratch[0], planes);
-    const float* b = bias_dev ? (const float*)bias_dev : e->zeros256;
-    const float* rs = (const float*)resid_dev;
-    // the self-play path's kernel (csrc/trunk15_wino3.h)
-    int rc;
-    if (rs && relu) rc = launch_wino3_t<true, true>(e, xin, (const float*)upk_dev, b, rs, yout, n);
-    else if (rs) rc = launch_wino3_t<true, false>(e, xin, (const float*)upk_dev, b, rs, yout, n);
-    else if (relu) rc = launch_wino3_t<false, true>(e, xin, (const float*)upk_dev, b, nullptr, yout, n);
-    else rc = launch_wino3_t<false, false>(e, xin, (const float*)upk_dev, b, nullptr, yout, n);
-    if (rc) return rc;
-    if (dense)
-        hipLaunchKernelGGL(apz::rows16_to_dense_kernel, dim3(cgrid), dim3(256), 0, e->stream, e->wino_scratch[1],
-                           (float*)y_dev, planes);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = ensure_zeros256(e)) return rc;
+        const long planes = (long)n * 128;
+        const int cgrid = (int)std::min<long>((planes * 240 + 255) / 256, 16384);
+        const bool dense = layout == APZ_LAYOUT_DENSE;
+        if (dense)      // the rows16 copies of input and output
+            for (auto& buf : e->wino_scratch)
+                if (int rc = buf.reserve((size_t)planes * 240 * sizeof(float))) return rc;
+        const float* xin = dense ? e->wino_scratch[0].as<float>() : (const float*)x_dev;
+        float* yout = dense ? e->wino_scratch[1].as<float>() : (float*)y_dev;
+        if (dense)
+            hipLaunchKernelGGL(apz::rows16_from_dense_kernel, dim3(cgrid), dim3(256), 0, e->stream, (const float*)x_dev,
+                               e->wino_scratch[0].as<float>(), planes);
+        const float* b = bias_dev ? (const float*)bias_dev : e->zeros256;
+        const float* rs = (const float*)resid_dev;
+        // the self-play path's kernel (csrc/trunk15_wino3.h)
+        if (int rc = with_flag(rs != nullptr, [&](auto RESID) {
+                return with_flag(relu != 0, [&](auto RELU) {
+                    return launch_wino3_t<RESID(), RELU()>(e, xin, (const float*)upk_dev, b, rs, yout, n);
+                });
+            }))
+            return rc;
+        if (dense)
+            hipLaunchKernelGGL(apz::rows16_to_dense_kernel, dim3(cgrid), dim3(256), 0, e->stream, yout, (float*)y_dev, planes);
+        return APZ_OK;
+    });
 }
 
 int apz_wino_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev, void* y_dev,
@@ -1918,24 +1946,19 @@ int apz_wino_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev, c
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wino_conv: 15x15 boards only");
     if (n > WINO3_MAX_BOARDS) return fail(APZ_E_UNSUPPORTED, "wino_conv_stats: one launch (<= 16384 boards)");
     using T = apz::Wino3;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    if (int rc = ensure_zeros256(e)) return rc;
-    StreamScope sc(e, stream);
-    const float* b = bias_dev ? (const float*)bias_dev : e->zeros256;
-    bool quarter = false;
-    const int grid = apz::wino3_grid(n, e->num_cu, e->no_quarter_trunk ? nullptr : &quarter);
-    if (!quarter) {
-        if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<false, false, false, true>, T::LDS_BYTES)) return rc;
-        hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false, false, false, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)upk_dev, b, (const float*)stats_dev, (float*)y_dev, n);
-    } else {
-        if (int rc = need_lds(e, (const void*)apz::trunk15_wino3_kernel<false, false, true, true>, T::LDS_BYTES)) return rc;
-        hipLaunchKernelGGL((apz::trunk15_wino3_kernel<false, false, true, true>), dim3(grid), dim3(512), T::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)upk_dev, b, (const float*)stats_dev, (float*)y_dev, n);
-    }
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = ensure_zeros256(e)) return rc;
+        const float* b = bias_dev ? (const float*)bias_dev : e->zeros256;
+        bool quarter = false;
+        const int grid = apz::wino3_grid(n, e->num_cu, e->no_quarter_trunk ? nullptr : &quarter);
+        return with_flag(quarter, [&](auto QUARTER) -> int {
+            const auto kern = apz::trunk15_wino3_kernel<false, false, QUARTER(), true>;
+            if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), T::LDS_BYTES, e->stream, (const float*)x_dev, (const float*)upk_dev, b,
+                               (const float*)stats_dev, (float*)y_dev, n);
+            return APZ_OK;
+        });
+    });
 }
 
 int apz_wino_conv(apz_engine* e, const void* x_dev, const void* upk_dev, const void* bias_dev, void* y_dev, int n, int relu,
@@ -1949,13 +1972,11 @@ int64_t apz_wino3h_packed_size(void) { return (int64_t)(apz::Wino3H16::UPK_BYTES
 int apz_wino3h_pack_many(apz_engine* e, const void* w_dev, const void* b_dev, int count, void* upk_dev, void* bias_dev,
                          void* flag_dev, void* stream) {
     if (!e || !w_dev || !upk_dev || !bias_dev || count < 1 || count > 16384) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::pack_wino3h16_many_kernel, dim3(128, 2 * count), dim3(128), 0, e->stream, (const float*)w_dev,
-                       (const float*)b_dev, (unsigned short*)upk_dev, (float*)bias_dev, (unsigned*)flag_dev);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        hipLaunchKernelGGL(apz::pack_wino3h16_many_kernel, dim3(128, 2 * count), dim3(128), 0, e->stream, (const float*)w_dev,
+                           (const float*)b_dev, (unsigned short*)upk_dev, (float*)bias_dev, (unsigned*)flag_dev);
+        return APZ_OK;
+    });
 }
 
 extern "C++" {
@@ -1968,14 +1989,13 @@ int launch_wino3h16_train(apz_engine* e, const void* x_dev, const void* upk_dev,
     if (n > WINO3_MAX_BOARDS) return fail(APZ_E_UNSUPPORTED, "wino3h: one launch (<= 16384 boards)");
     using T = apz::Wino3H16;
     const auto kern = apz::trunk15_wino3h16_kernel<RESID, false, FORM>;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(kern, dim3(apz::wino3_grid(n, e->num_cu)), dim3(512), T::LDS_BYTES, e->stream, (const float*)x_dev, upk_dev,
-                       (const float*)bias_dev, (const float*)resid_dev, (float*)y_dev, n, (unsigned*)flag_dev, aux, aux_n);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(kern, dim3(apz::wino3_grid(n, e->num_cu)), dim3(512), T::LDS_BYTES, e->stream, (const float*)x_dev,
+                           upk_dev, (const float*)bias_dev, (const float*)resid_dev, (float*)y_dev, n, (unsigned*)flag_dev, aux,
+                           aux_n);
+        return APZ_OK;
+    });
 }
 }  // namespace
 }  // extern "C++"
@@ -1989,27 +2009,11 @@ int apz_wino3h_conv_stats(apz_engine* e, const void* x_dev, const void* upk_dev,
 int apz_wino3h_conv_dgrad(apz_engine* e, const void* dy_dev, const void* upk_dev, const void* bias_dev, const void* add_dev,
                           void* dx_dev, int n, const void* dymax_dev, int dymax_count, void* flag_dev, void* stream) {
     if (dymax_count < 1) return fail(APZ_E_ARG, "bad argument");
-    void* dm = const_cast<void*>(dymax_dev);
-    if (add_dev)
-        return launch_wino3h16_train<apz::WINO3H16_DGRAD, true>(e, dy_dev, upk_dev, bias_dev, add_dev, dx_dev, n, flag_dev, dm,
-                                                                dymax_count, stream);
-    return launch_wino3h16_train<apz::WINO3H16_DGRAD, false>(e, dy_dev, upk_dev, bias_dev, nullptr, dx_dev, n, flag_dev, dm,
-                                                             dymax_count, stream);
+    return with_flag(add_dev != nullptr, [&](auto RESID) {
+        return launch_wino3h16_train<apz::WINO3H16_DGRAD, RESID()>(e, dy_dev, upk_dev, bias_dev, add_dev, dx_dev, n, flag_dev,
+                                                                   const_cast<void*>(dymax_dev), dymax_count, stream);
+    });
 }
-
-namespace {
-int wgrad_scratch(apz_engine* e, size_t floats) {   // per-slice partial weight gradients (both weight-gradient kernels)
-    if (floats > e->wgw_floats) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (e->wgw_scratch) HIP_TRY(hipFree(e->wgw_scratch));
-        e->wgw_scratch = nullptr;
-        e->wgw_floats = 0;
-        HIP_TRY(hipMalloc((void**)&e->wgw_scratch, floats * sizeof(float)));
-        e->wgw_floats = floats;
-    }
-    return APZ_OK;
-}
-}  // namespace
 
 int apz_conv3x3_wgrad(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, int cin, int cout,
                       int layout, void* stream) {
@@ -2017,40 +2021,28 @@ int apz_conv3x3_wgrad(apz_engine* e, const void* x_dev, const void* dy_dev, void
         return fail(APZ_E_ARG, "bad argument (C_out must be a multiple of 32)");
     if (layout == APZ_LAYOUT_ROWS16 && (e->cfg.height != 15 || e->cfg.width != 15))
         return fail(APZ_E_UNSUPPORTED, "padded-row layout: 15x15 boards only");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const int H = e->cfg.height, W = e->cfg.width;
-    const int gx = cout / 32, gy = (cin + 63) / 64;
-    int slices = std::max(1, std::min(n, (e->num_cu * 2) / std::max(1, gx * gy)));
-    if (H == 15 && W == 15) {
-        using G = apz::WgradGeo<15, 15>;
-        slices = std::max(1, std::min(n, e->num_cu / std::max(1, gx * gy)));   // 85 KB LDS: one workgroup per CU
-        if (int rc = wgrad_scratch(e, (size_t)slices * cout * cin * 9)) return rc;
-        if (layout == APZ_LAYOUT_DENSE) {
-            if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<15, 15>, G::LDS_BYTES)) return rc;
-            hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<15, 15>), dim3(gx, gy, slices), dim3(256), G::LDS_BYTES, e->stream,
-                               (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
-        } else {
-            using G16 = apz::WgradGeo<15, 15, true>;
-            if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<15, 15, true>, G16::LDS_BYTES)) return rc;
-            hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<15, 15, true>), dim3(gx, gy, slices), dim3(256), G16::LDS_BYTES,
-                               e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
-        }
-    } else if (H == 8 && W == 8) {
-        using G = apz::WgradGeo<8, 8>;
-        if (int rc = wgrad_scratch(e, (size_t)slices * cout * cin * 9)) return rc;
-        if (int rc = need_lds(e, (const void*)apz::conv3x3_wgrad_kernel<8, 8>, G::LDS_BYTES)) return rc;
-        hipLaunchKernelGGL((apz::conv3x3_wgrad_kernel<8, 8>), dim3(gx, gy, slices), dim3(256), G::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, cin, cout);
-    } else {
+    return train_call(e, stream, [&]() -> int {
+        const int gx = cout / 32, gy = (cin + 63) / 64;
+        // a square board of side S (R16: in padded rows), `per_cu` workgroups per CU: every slice of the batch leaves its
+        // partial sums, which are then added in index order
+        auto run = [&](auto S, auto R16, int per_cu) -> int {
+            using G = apz::WgradGeo<S(), S(), R16()>;
+            const auto kern = apz::conv3x3_wgrad_kernel<S(), S(), R16()>;
+            const int slices = std::max(1, std::min(n, (e->num_cu * per_cu) / std::max(1, gx * gy)));
+            if (int rc = e->wgw_scratch.reserve((size_t)slices * cout * cin * 9 * sizeof(float))) return rc;
+            if (int rc = need_lds(e, (const void*)kern, G::LDS_BYTES)) return rc;
+            hipLaunchKernelGGL(kern, dim3(gx, gy, slices), dim3(256), G::LDS_BYTES, e->stream, (const float*)x_dev,
+                               (const float*)dy_dev, e->wgw_scratch.as<float>(), n, cin, cout);
+            hipLaunchKernelGGL(apz::colsum_kernel, dim3((cout * cin * 9 + 63) / 64), dim3(256), 0, e->stream,
+                               e->wgw_scratch.as<const float>(), (float*)dw_dev, slices, cout * cin * 9, 1.0f);
+            return APZ_OK;
+        };
+        const int H = e->cfg.height, W = e->cfg.width;
+        if (H == 15 && W == 15)     // 85 KB LDS: one workgroup per CU
+            return with_flag(layout == APZ_LAYOUT_ROWS16, [&](auto R16) { return run(int_c<15>{}, R16, 1); });
+        if (H == 8 && W == 8) return run(int_c<8>{}, std::false_type{}, 2);
         return fail(APZ_E_UNSUPPORTED, "conv3x3_wgrad: unsupported board size");
-    }
-    // the slices' partial sums, added in index order
-    hipLaunchKernelGGL(apz::colsum_kernel, dim3((cout * cin * 9 + 63) / 64), dim3(256), 0, e->stream, (const float*)e->wgw_scratch,
-                       (float*)dw_dev, slices, cout * cin * 9, 1.0f);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    });
 }
 
 namespace {
@@ -2066,10 +2058,8 @@ int bn_geometry(apz_engine* e, int layout, int* ps, int* rs) {
     return APZ_OK;
 }
 constexpr int BN_SPLITS = 64;      // batch splits per channel at most (every consumer workgroup adds them)
-int bn_scratch(apz_engine* e) {    // per-(channel, split) partial sums: overwritten by every statistics launch, nothing to zero
-    if (!e->bn_part) HIP_TRY(hipMalloc((void**)&e->bn_part, (size_t)256 * BN_SPLITS * 2 * sizeof(double)));
-    return APZ_OK;
-}
+// per-(channel, split) partial sums: overwritten by every statistics launch, nothing to zero
+int bn_scratch(apz_engine* e) { return e->bn_part.reserve((size_t)256 * BN_SPLITS * 2 * sizeof(double)); }
 // grid.y of the four BatchNorm launches: channels x splits ~ 8 workgroups per CU (padded rows: four boards per trip)
 int bn_splits(const apz_engine* e, int n, int C, int layout) {
     const int per = layout == APZ_LAYOUT_ROWS16 ? (n + 3) / 4 : n;
@@ -2093,31 +2083,30 @@ int apz_bn_fwd_stats(apz_engine* e, const void* x_dev, const void* resid_dev, co
     if ((stats_dev || mask_dev) && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_fwd_stats: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if (int rc = bn_scratch(e)) return rc;
-    const int H = e->cfg.height, W = e->cfg.width;
-    const int splits = bn_splits(e, n, C, layout);
-    const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev, (double)n * H * W, eps,
-                           momentum};
-    if (layout == APZ_LAYOUT_ROWS16) {
-        // statistics from the producer (apz_wino_conv_stats: one pair of sums per channel and board): no pass over x for them
-        if (!stats_dev)
-            hipLaunchKernelGGL(apz::bn_stats_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, e->bn_part, n, C);
-        hipLaunchKernelGGL(apz::bn_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
-                           (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev,
-                           stats_dev ? (const double*)stats_dev : (const double*)e->bn_part, stats_dev ? n : splits, fin,
-                           (float*)y_dev, (unsigned char*)mask_dev, n, C, relu);
-    } else {
-        hipLaunchKernelGGL(apz::bn_stats_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, e->bn_part, n, C,
-                           ps, rs, H, W);
-        hipLaunchKernelGGL(apz::bn_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
-                           (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, (const double*)e->bn_part,
-                           splits, fin, (float*)y_dev, n, C, ps, rs, H, W, relu);
-    }
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int H = e->cfg.height, W = e->cfg.width;
+        const int splits = bn_splits(e, n, C, layout);
+        const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev, (double)n * H * W, eps,
+                               momentum};
+        if (layout == APZ_LAYOUT_ROWS16) {
+            // statistics from the producer (apz_wino_conv_stats: one pair of sums per channel and board): no pass over x for them
+            if (!stats_dev)
+                hipLaunchKernelGGL(apz::bn_stats_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C);
+            hipLaunchKernelGGL(apz::bn_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
+                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev,
+                               stats_dev ? (const double*)stats_dev : part, stats_dev ? n : splits, fin,
+                               (float*)y_dev, (unsigned char*)mask_dev, n, C, relu);
+        } else {
+            hipLaunchKernelGGL(apz::bn_stats_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C,
+                               ps, rs, H, W);
+            hipLaunchKernelGGL(apz::bn_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
+                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, part,
+                               splits, fin, (float*)y_dev, n, C, ps, rs, H, W, relu);
+        }
+        return APZ_OK;
+    });
 }
 
 int apz_bn_bwd_splits(apz_engine* e, int n, int C, int layout) {
@@ -2142,109 +2131,88 @@ int apz_bn_bwd_max(apz_engine* e, const void* dy_dev, const void* x_dev, const v
     if (dxmax_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_max: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if (int rc = bn_scratch(e)) return rc;
-    const int H = e->cfg.height, W = e->cfg.width;
-    const int splits = bn_splits(e, n, C, layout);
-    if (layout == APZ_LAYOUT_ROWS16) {
-        hipLaunchKernelGGL(apz::bn_bwd_reduce_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
-                           e->bn_part, (const unsigned char*)mask_dev, n, C, relu);
-        hipLaunchKernelGGL(apz::bn_bwd_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
-                           (const float*)invstd_dev, (const double*)e->bn_part, splits, (float*)dx_dev, (float*)dres_dev,
-                           (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C,
-                           relu, (double)n * H * W, (float*)dxmax_dev);
-    } else {
-        hipLaunchKernelGGL(apz::bn_bwd_reduce_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
-                           e->bn_part, n, C, ps, rs, H, W, relu);
-        hipLaunchKernelGGL(apz::bn_bwd_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
-                           (const float*)invstd_dev, (const double*)e->bn_part, splits, (float*)dx_dev, (float*)dres_dev,
-                           (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu,
-                           (double)n * H * W);
-    }
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int H = e->cfg.height, W = e->cfg.width;
+        const int splits = bn_splits(e, n, C, layout);
+        if (layout == APZ_LAYOUT_ROWS16) {
+            hipLaunchKernelGGL(apz::bn_bwd_reduce_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
+                               part, (const unsigned char*)mask_dev, n, C, relu);
+            hipLaunchKernelGGL(apz::bn_bwd_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
+                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev,
+                               (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C,
+                               relu, (double)n * H * W, (float*)dxmax_dev);
+        } else {
+            hipLaunchKernelGGL(apz::bn_bwd_reduce_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
+                               part, n, C, ps, rs, H, W, relu);
+            hipLaunchKernelGGL(apz::bn_bwd_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
+                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev,
+                               (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu,
+                               (double)n * H * W);
+        }
+        return APZ_OK;
+    });
 }
 
 int apz_colsum(apz_engine* e, const void* in_dev, void* out_dev, int rows, int cols, float scale, void* stream) {
     if (!e || !in_dev || !out_dev || rows < 1 || cols < 1) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::colsum_kernel, dim3((cols + 63) / 64), dim3(256), 0, e->stream, (const float*)in_dev, (float*)out_dev,
-                       rows, cols, scale);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        hipLaunchKernelGGL(apz::colsum_kernel, dim3((cols + 63) / 64), dim3(256), 0, e->stream, (const float*)in_dev, (float*)out_dev,
+                           rows, cols, scale);
+        return APZ_OK;
+    });
 }
 
+extern "C++" {
 namespace {
-// The decomposition of both Winograd weight-gradient kernels, by channel blocks (csrc/wgrad_wino3.h: 16 blocks x slices =
-// one workgroup per CU); the workgroups of a slice sit on one XCD (see the kernel).  Grows the slices' scratch.
-int wgrad_wino_plan(apz_engine* e, int n, int blocks, int* spx, int* slices) {
-    *spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * blocks)));
-    *slices = 8 * *spx;
-    return wgrad_scratch(e, (size_t)*slices * apz::WgradWino::SCRATCH_FLOATS_PER_SLICE);
-}
-
-// ... and their second launch: the slices' partial dU summed and transformed back into dw
-int launch_wgrad_wino_finish(apz_engine* e, int slices, void* dw_dev) {
-    hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream,
-                       (const float*)e->wgw_scratch, slices, (float*)dw_dev);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+// Both Winograd weight-gradient entry points (T = apz::WgradWino3 / apz::WgradWino3H; `kernel(BUF)` = T's kernel with or
+// without raw buffer loads; `extra...` = the kernel's arguments behind spx): the decomposition by channel blocks
+// (csrc/wgrad_wino3.h: 16 blocks x slices = one workgroup per CU; the workgroups of a slice sit on one XCD, see the
+// kernel), the slices' scratch, the launch, and the second launch that sums the slices' partial dU and transforms the sum
+// back into dw.
+template <class T, class K, class... A>
+int wgrad_wino_call(apz_engine* e, K kernel, const void* x_dev, const void* dy_dev, void* dw_dev, int n, void* stream, A... extra) {
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
+    if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
+    return train_call(e, stream, [&]() -> int {
+        const int spx = std::max(1, std::min((n + 7) / 8, e->num_cu / (8 * T::BLOCKS)));
+        const int slices = 8 * spx;
+        if (int rc = e->wgw_scratch.reserve((size_t)slices * apz::WgradWino::SCRATCH_FLOATS_PER_SLICE * sizeof(float))) return rc;
+        float* part = e->wgw_scratch.as<float>();
+        // rows through raw buffer loads (hardware zero fill for rows off the board, scalar board offset) from 256 boards on:
+        // 133.6 against 144.4 us at 512 boards, 38.7 against 37.8 us at 128 (same box, alternating rounds: tools/wgrad_kernel_bench.hip)
+        if (int rc = with_flag(n >= 256, [&](auto BUF) -> int {
+                const auto kern = kernel(BUF);
+                if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
+                hipLaunchKernelGGL(kern, dim3(T::BLOCKS * slices), dim3(T::THREADS), T::LDS_BYTES, e->stream, (const float*)x_dev,
+                                   (const float*)dy_dev, part, n, spx, extra...);
+                return APZ_OK;
+            }))
+            return rc;
+        hipLaunchKernelGGL(apz::wgrad_wino_finish_kernel, dim3(128 * 128 * 9 / 4 / 256), dim3(256), 0, e->stream, (const float*)part,
+                           slices, (float*)dw_dev);
+        return APZ_OK;
+    });
 }
 }  // namespace
+}  // extern "C++"
 
 int apz_wgrad_wino(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, void* stream) {
     if (!e || !x_dev || !dy_dev || !dw_dev || n < 1) return fail(APZ_E_ARG, "bad argument");
-    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
-    if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
-    using T3 = apz::WgradWino3;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    int spx, slices;
-    if (int rc = wgrad_wino_plan(e, n, T3::BLOCKS, &spx, &slices)) return rc;
-    // rows through raw buffer loads (hardware zero fill for rows off the board, scalar board offset) from 256 boards on:
-    // 133.6 against 144.4 us at 512 boards, 38.7 against 37.8 us at 128 (same box, alternating rounds: tools/wgrad_kernel_bench.hip)
-    const void* kern = n < 256 ? (const void*)apz::wgrad_wino3_kernel<false> : (const void*)apz::wgrad_wino3_kernel<true>;
-    if (int rc = need_lds(e, kern, T3::LDS_BYTES)) return rc;
-    if (n >= 256)
-        hipLaunchKernelGGL(apz::wgrad_wino3_kernel<true>, dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx);
-    else
-        hipLaunchKernelGGL(apz::wgrad_wino3_kernel<false>, dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES, e->stream,
-                           (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx);
-    return launch_wgrad_wino_finish(e, slices, dw_dev);
+    return wgrad_wino_call<apz::WgradWino3>(e, [](auto BUF) { return apz::wgrad_wino3_kernel<BUF()>; }, x_dev, dy_dev, dw_dev, n,
+                                            stream);
 }
 
 int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, void* dw_dev, int n, const void* dymax_dev,
                          int dymax_count, void* flag_dev, void* stream) {
     if (!e || !x_dev || !dy_dev || !dw_dev || !dymax_dev || dymax_count < 1 || n < 1) return fail(APZ_E_ARG, "bad argument");
-    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: 15x15 boards only");
-    if (n > 32768) return fail(APZ_E_UNSUPPORTED, "wgrad_wino: at most 32768 boards per call (32-bit buffer offsets)");
-    using T3 = apz::WgradWino3H;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    int spx, slices;
-    if (int rc = wgrad_wino_plan(e, n, T3::BLOCKS, &spx, &slices)) return rc;
-    const void* kern = n < 256 ? (const void*)apz::wgrad_wino3h_kernel<false> : (const void*)apz::wgrad_wino3h_kernel<true>;
-    if (int rc = need_lds(e, kern, T3::LDS_BYTES)) return rc;
-    if (n >= 256)                                     // buffer loads from 256 boards on, as apz_wgrad_wino
-        hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<true>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
-                           e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
-                           dymax_count, (unsigned*)flag_dev);
-    else
-        hipLaunchKernelGGL((apz::wgrad_wino3h_kernel<false>), dim3(T3::BLOCKS * slices), dim3(T3::THREADS), T3::LDS_BYTES,
-                           e->stream, (const float*)x_dev, (const float*)dy_dev, e->wgw_scratch, n, spx, (const float*)dymax_dev,
-                           dymax_count, (unsigned*)flag_dev);
-    return launch_wgrad_wino_finish(e, slices, dw_dev);
+    return wgrad_wino_call<apz::WgradWino3H>(e, [](auto BUF) { return apz::wgrad_wino3h_kernel<BUF()>; }, x_dev, dy_dev, dw_dev, n,
+                                             stream, (const float*)dymax_dev, dymax_count, (unsigned*)flag_dev);
 }
 
 int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
@@ -2256,28 +2224,21 @@ int apz_adam_step_unless(apz_engine* e, const void* table_host, int ntensors, fl
                          float rescale, const void* skip_dev, void* stream) {
     if (!e || !table_host || ntensors < 1 || ntensors > 4096) return fail(APZ_E_ARG, "bad argument");
     static_assert(sizeof(apz::AdamTensor) == 48, "apz_adam_tensor layout");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const size_t bytes = (size_t)ntensors * sizeof(apz::AdamTensor);
-    if (bytes > e->adam_cap) {
-        if (e->adam_tab) HIP_TRY(hipFree(e->adam_tab));
-        e->adam_tab = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->adam_tab, bytes));
-        e->adam_cap = bytes;
-    }
-    // Stream-ordered upload: the copy queues behind the previous step's kernel (which read the same device table), and
-    // for pageable host memory hipMemcpyAsync returns once the 6 KB have been staged, so the caller's buffer need
-    // not outlive the call.  (No stream synchronisation: the optimiser step no longer drains the GPU.)
-    HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
-    if (skip_dev)
-        hipLaunchKernelGGL(apz::adam_step_unless_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
-                           (const apz::AdamTensor*)e->adam_tab, lr_t, b1, b2, eps, rescale, (const unsigned*)skip_dev);
-    else
-        hipLaunchKernelGGL(apz::adam_step_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
-                           (const apz::AdamTensor*)e->adam_tab, lr_t, b1, b2, eps, rescale);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const size_t bytes = (size_t)ntensors * sizeof(apz::AdamTensor);
+        if (int rc = e->adam_tab.reserve(bytes)) return rc;
+        const auto* tab = e->adam_tab.as<const apz::AdamTensor>();
+        // Stream-ordered upload: the copy queues behind the previous step's kernel (which read the same device table), and
+        // for pageable host memory hipMemcpyAsync returns once the 6 KB have been staged, so the caller's buffer need
+        // not outlive the call.  (No stream synchronisation: the optimiser step no longer drains the GPU.)
+        HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+        if (skip_dev)      // (two kernels with two signatures)
+            hipLaunchKernelGGL(apz::adam_step_unless_kernel, dim3(32, ntensors), dim3(256), 0, e->stream, tab, lr_t, b1, b2, eps,
+                               rescale, (const unsigned*)skip_dev);
+        else
+            hipLaunchKernelGGL(apz::adam_step_kernel, dim3(32, ntensors), dim3(256), 0, e->stream, tab, lr_t, b1, b2, eps, rescale);
+        return APZ_OK;
+    });
 }
 
 // ---- heads and loss of the training graph (csrc/heads_train.h)
@@ -2293,16 +2254,6 @@ void launch_sgemm(apz_engine* e, const float* a, const float* b, const float* bi
         hipLaunchKernelGGL(apz::sgemm_ksplit_kernel, dim3((N + 15) / 16, (M + 15) / 16), dim3(256), 0, e->stream, a, b, bias, c, M,
                            N, K, a_rs, a_cs, b_rs, b_cs, ldc);
 }
-
-int head_scratch(apz_engine* e, size_t floats) {
-    if (floats > e->head_scratch_floats) {
-        if (e->head_scratch) HIP_TRY(hipFree(e->head_scratch));
-        e->head_scratch = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->head_scratch, floats * sizeof(float)));
-        e->head_scratch_floats = floats;
-    }
-    return APZ_OK;
-}
 }  // namespace
 
 int apz_conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C,
@@ -2310,16 +2261,14 @@ int apz_conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const v
     if (!e || !x_dev || !w_dev || !y_dev || n < 1 || C < 1 || C > 1024 || CO < 1 || CO > 8) return fail(APZ_E_ARG, "bad argument");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
-    if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
-    hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (e->cfg.height * e->cfg.width + 63) / 64), dim3(256), lds, e->stream,
-                       (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, e->cfg.height,
-                       e->cfg.width, ps, rs);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
+        if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
+        hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (e->cfg.height * e->cfg.width + 63) / 64), dim3(256), lds, e->stream,
+                           (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, e->cfg.height,
+                           e->cfg.width, ps, rs);
+        return APZ_OK;
+    });
 }
 
 int apz_conv1x1_bwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* dy_dev, void* dx_dev, void* dw_dev,
@@ -2338,92 +2287,81 @@ int apz_conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const
         return fail(APZ_E_ARG, "bad argument");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const int P = e->cfg.height * e->cfg.width, CO = CO1 + CO2;
-    if (int rc = head_scratch(e, (size_t)n * CO * C)) return rc;
-    const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
-    if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
-    hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
-                       (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
-                       e->head_scratch, C, CO1, CO2, e->cfg.height, e->cfg.width, ps, rs, accumulate_dx);
-    hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)e->head_scratch,
-                       (float*)dw_dev, n, CO * C, 1.0f);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const int P = e->cfg.height * e->cfg.width, CO = CO1 + CO2;
+        if (int rc = e->head_scratch.reserve((size_t)n * CO * C * sizeof(float))) return rc;
+        float* part = e->head_scratch.as<float>();      // dw per board
+        const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
+        if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
+        hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
+                           (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
+                           part, C, CO1, CO2, e->cfg.height, e->cfg.width, ps, rs, accumulate_dx);
+        hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)part,
+                           (float*)dw_dev, n, CO * C, 1.0f);
+        return APZ_OK;
+    });
 }
 
 int apz_bias_grad(apz_engine* e, const void* dy_dev, void* db_dev, int n, int C, int layout, void* stream) {
     if (!e || !dy_dev || !db_dev || n < 1 || C < 1) return fail(APZ_E_ARG, "bad argument");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const int slices = std::max(1, std::min(n, (e->num_cu * 8 + C - 1) / C));
-    if (int rc = head_scratch(e, (size_t)slices * C)) return rc;
-    hipLaunchKernelGGL(apz::bias_grad_kernel, dim3(C, slices), dim3(256), 0, e->stream, (const float*)dy_dev, e->head_scratch, n, C,
-                       ps);
-    hipLaunchKernelGGL(apz::colsum_kernel, dim3((C + 63) / 64), dim3(256), 0, e->stream, (const float*)e->head_scratch,
-                       (float*)db_dev, slices, C, 1.0f);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const int slices = std::max(1, std::min(n, (e->num_cu * 8 + C - 1) / C));
+        if (int rc = e->head_scratch.reserve((size_t)slices * C * sizeof(float))) return rc;
+        float* part = e->head_scratch.as<float>();      // db per slice of the batch
+        hipLaunchKernelGGL(apz::bias_grad_kernel, dim3(C, slices), dim3(256), 0, e->stream, (const float*)dy_dev, part, n, C, ps);
+        hipLaunchKernelGGL(apz::colsum_kernel, dim3((C + 63) / 64), dim3(256), 0, e->stream, (const float*)part, (float*)db_dev,
+                           slices, C, 1.0f);
+        return APZ_OK;
+    });
 }
 
 int apz_add(apz_engine* e, void* y_dev, const void* x_dev, int64_t count, void* stream) {
     if (!e || !y_dev || !x_dev || count < 1) return fail(APZ_E_ARG, "bad argument");
     if (((uintptr_t)y_dev | (uintptr_t)x_dev) & 15) return fail(APZ_E_ARG, "add: 16-byte aligned tensors");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const long n4 = count / 4;
-    hipLaunchKernelGGL(apz::add_inplace_kernel, dim3((int)std::max<long>(1, std::min<long>((n4 + 255) / 256, 8192))), dim3(256), 0,
-                       e->stream, (float*)y_dev, (const float*)x_dev, n4, (long)count);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const long n4 = count / 4;
+        hipLaunchKernelGGL(apz::add_inplace_kernel, dim3((int)std::max<long>(1, std::min<long>((n4 + 255) / 256, 8192))), dim3(256), 0,
+                           e->stream, (float*)y_dev, (const float*)x_dev, n4, (long)count);
+        return APZ_OK;
+    });
 }
 
 int apz_fc_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int K, int N,
                void* stream) {
     if (!e || !x_dev || !w_dev || !y_dev || n < 1 || K < 1 || N < 1) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    // y[n][N] = x[n][K] W[N][K]^T + b:  A = x (row stride K), B(k, j) = W[j][k]
-    launch_sgemm(e, (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, n, N, K, (long)K, 1L, 1L,
-                 (long)K, N);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        // y[n][N] = x[n][K] W[N][K]^T + b:  A = x (row stride K), B(k, j) = W[j][k]
+        launch_sgemm(e, (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, n, N, K, (long)K, 1L, 1L,
+                     (long)K, N);
+        return APZ_OK;
+    });
 }
 
 int apz_fc_bwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* dy_dev, void* dx_dev, void* dw_dev, void* db_dev,
                int n, int K, int N, void* stream) {
     if (!e || !x_dev || !w_dev || !dy_dev || n < 1 || K < 1 || N < 1) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if (dx_dev)     // dx[n][K] = dy[n][N] W[N][K]
-        launch_sgemm(e, (const float*)dy_dev, (const float*)w_dev, nullptr, (float*)dx_dev, n, K, N, (long)N, 1L, (long)K, 1L, K);
-    if (dw_dev)     // dW[N][K] = dy^T[N][n] x[n][K]:  A(m, k) = dy[k][m]
-        launch_sgemm(e, (const float*)dy_dev, (const float*)x_dev, nullptr, (float*)dw_dev, N, K, n, 1L, (long)N, (long)K, 1L, K);
-    if (db_dev)
-        hipLaunchKernelGGL(apz::colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, e->stream, (const float*)dy_dev, (float*)db_dev,
-                           n, N, 1.0f);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (dx_dev)     // dx[n][K] = dy[n][N] W[N][K]
+            launch_sgemm(e, (const float*)dy_dev, (const float*)w_dev, nullptr, (float*)dx_dev, n, K, N, (long)N, 1L, (long)K, 1L, K);
+        if (dw_dev)     // dW[N][K] = dy^T[N][n] x[n][K]:  A(m, k) = dy[k][m]
+            launch_sgemm(e, (const float*)dy_dev, (const float*)x_dev, nullptr, (float*)dw_dev, N, K, n, 1L, (long)N, (long)K, 1L, K);
+        if (db_dev)
+            hipLaunchKernelGGL(apz::colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, e->stream, (const float*)dy_dev, (float*)db_dev,
+                               n, N, 1.0f);
+        return APZ_OK;
+    });
 }
 
 int apz_dropout(apz_engine* e, const void* x_dev, void* y_dev, int64_t count, float keep, uint64_t seed, uint64_t step,
                 void* stream) {
     if (!e || !x_dev || !y_dev || count < 1 || !(keep > 0.f) || keep > 1.f) return fail(APZ_E_ARG, "bad argument");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    hipLaunchKernelGGL(apz::dropout_kernel, dim3((int)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, e->stream,
-                       (const float*)x_dev, (float*)y_dev, (long)count, keep, (unsigned long long)seed, (unsigned long long)step);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        hipLaunchKernelGGL(apz::dropout_kernel, dim3((int)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, e->stream,
+                           (const float*)x_dev, (float*)y_dev, (long)count, keep, (unsigned long long)seed, (unsigned long long)step);
+        return APZ_OK;
+    });
 }
 
 int apz_pv_loss(apz_engine* e, const void* logits_dev, const void* vlogit_dev, const void* pi_dev, const void* z_dev, int n,
@@ -2431,36 +2369,29 @@ int apz_pv_loss(apz_engine* e, const void* logits_dev, const void* vlogit_dev, c
     if (!e || !logits_dev || !vlogit_dev || n < 1) return fail(APZ_E_ARG, "bad argument");
     if ((loss3_dev || dlogits_dev || dvlogit_dev) && (!pi_dev || !z_dev)) return fail(APZ_E_ARG, "targets missing");
     if (e->hw > 4096) return fail(APZ_E_UNSUPPORTED, "board too large");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if (int rc = head_scratch(e, (size_t)n * 3)) return rc;
-    hipLaunchKernelGGL(apz::pv_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, (const float*)logits_dev,
-                       (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev, n, e->hw, 1.0f / (float)n,
-                       loss3_dev ? e->head_scratch : (float*)nullptr, (float*)dlogits_dev, (float*)dvlogit_dev, (float*)probs_dev,
-                       (float*)values_dev);
-    if (loss3_dev)  // (value loss, policy loss, entropy): batch means, samples summed in index order
-        hipLaunchKernelGGL(apz::colsum_kernel, dim3(1), dim3(256), 0, e->stream, (const float*)e->head_scratch, (float*)loss3_dev, n,
-                           3, 1.0f / (float)n);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = e->head_scratch.reserve((size_t)n * 3 * sizeof(float))) return rc;
+        float* part = e->head_scratch.as<float>();      // the three terms per sample
+        hipLaunchKernelGGL(apz::pv_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, (const float*)logits_dev,
+                           (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev, n, e->hw, 1.0f / (float)n,
+                           loss3_dev ? part : (float*)nullptr, (float*)dlogits_dev, (float*)dvlogit_dev, (float*)probs_dev,
+                           (float*)values_dev);
+        if (loss3_dev)  // (value loss, policy loss, entropy): batch means, samples summed in index order
+            hipLaunchKernelGGL(apz::colsum_kernel, dim3(1), dim3(256), 0, e->stream, (const float*)part, (float*)loss3_dev, n, 3,
+                               1.0f / (float)n);
+        return APZ_OK;
+    });
 }
 
 int apz_layout_convert(apz_engine* e, const void* src_dev, void* dst_dev, int64_t planes, int to_rows16, void* stream) {
     if (!e || !src_dev || !dst_dev || planes < 1) return fail(APZ_E_ARG, "bad argument");
     if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "padded-row layout: 15x15 boards only");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    const int grid = (int)std::min<int64_t>((planes * 240 + 255) / 256, 16384);
-    if (to_rows16)
-        hipLaunchKernelGGL(apz::rows16_from_dense_kernel, dim3(grid), dim3(256), 0, e->stream, (const float*)src_dev, (float*)dst_dev,
-                           (long)planes);
-    else
-        hipLaunchKernelGGL(apz::rows16_to_dense_kernel, dim3(grid), dim3(256), 0, e->stream, (const float*)src_dev, (float*)dst_dev,
-                           (long)planes);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        const int grid = (int)std::min<int64_t>((planes * 240 + 255) / 256, 16384);
+        const auto kern = to_rows16 ? apz::rows16_from_dense_kernel : apz::rows16_to_dense_kernel;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, (const float*)src_dev, (float*)dst_dev, (long)planes);
+        return APZ_OK;
+    });
 }
 
 // ---- device replay buffer (csrc/replay.h)
@@ -2479,25 +2410,17 @@ int apz_replay_gather(apz_engine* e, const void* codes_dev, const void* pi_dev, 
         if (entries_host[j] < 0 || (int64_t)entries_host[j] >= 8 * capacity)
             return fail(APZ_E_ARG, "replay gather: entry " + std::to_string(j) + " = " + std::to_string(entries_host[j]) +
                                        " lies outside [0, 8 * capacity = " + std::to_string(8 * capacity) + ")");
-    EngineLock guard(e->submit_lock);
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    StreamScope sc(e, stream);
-    if ((size_t)n > e->gather_cap) {
-        if (e->gather_entries) HIP_TRY(hipFree(e->gather_entries));
-        e->gather_entries = nullptr;
-        e->gather_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->gather_entries, (size_t)n * sizeof(int32_t)));
-        e->gather_cap = n;
-    }
-    // stream-ordered upload behind the previous gather's kernel (apz_adam_step's table travels the same way)
-    HIP_TRY(hipMemcpyAsync(e->gather_entries, entries_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    const long total = (long)n * e->hw;
-    hipLaunchKernelGGL(apz::replay_gather_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 16)), dim3(256), 0,
-                       e->stream, (const unsigned char*)codes_dev, (const float*)pi_dev, (const float*)z_dev,
-                       (const int*)e->gather_entries, e->perm_s, e->perm_p, (float*)planes_out_dev, (float*)pi_out_dev,
-                       (float*)z_out_dev, n, e->cfg.height, e->cfg.width, e->code_stride, n_planes);
-    HIP_TRY(hipGetLastError());
-    return APZ_OK;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = e->gather_entries.reserve((size_t)n * sizeof(int32_t))) return rc;
+        // stream-ordered upload behind the previous gather's kernel (apz_adam_step's table travels the same way)
+        HIP_TRY(hipMemcpyAsync(e->gather_entries, entries_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+        const long total = (long)n * e->hw;
+        hipLaunchKernelGGL(apz::replay_gather_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 16)), dim3(256), 0,
+                           e->stream, (const unsigned char*)codes_dev, (const float*)pi_dev, (const float*)z_dev,
+                           e->gather_entries.as<const int>(), e->perm_s, e->perm_p, (float*)planes_out_dev, (float*)pi_out_dev,
+                           (float*)z_out_dev, n, e->cfg.height, e->cfg.width, e->code_stride, n_planes);
+        return APZ_OK;
+    });
 }
 
 // apz_forward_host for planes that already live in device memory (a mini-batch of the device replay buffer): the engine's

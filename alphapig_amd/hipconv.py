@@ -31,9 +31,15 @@ def _engine(h, w, device_index):
     return _ENGINES[key]
 
 
+_TORCH = _F32 = None
+
+
 def _torch():
-    import torch
-    return torch
+    global _TORCH, _F32
+    if _TORCH is None:
+        import torch
+        _TORCH, _F32 = torch, torch.float32
+    return _TORCH
 
 
 def _ck(L, rc):
@@ -41,17 +47,44 @@ def _ck(L, rc):
         raise RuntimeError("%s (code %d)" % (L.apz_last_error().decode(), rc))
 
 
-def _ctx(x, layout=DENSE):
-    """-> (library, engine handle for x's board size and device, stream pointer)"""
+def _any_engine(device_index):
+    """Operators that do not depend on the board (FullyConnected, Dropout, Adam) run on whichever engine this device
+    already has (the net's own board size), else on a 15x15 one."""
+    for (h, w, d), hnd in _ENGINES.items():
+        if d == device_index:
+            return hnd
+    return _engine(15, 15, device_index)
+
+
+def _check(t, what, dtype=None, shape=None):
+    """ValueError(what) unless t is a contiguous device tensor of `dtype` (default float32) -- and of `shape`, if given"""
+    if not (t.is_cuda and t.dtype == (dtype or _F32 or _torch().float32) and t.is_contiguous() and
+            (shape is None or tuple(t.shape) == shape)):
+        raise ValueError(what)
+
+
+def _ctx(x, board=None):
+    """-> (library, engine handle, stream pointer) for every operator.  x: a tensor (checked: contiguous float32 on a
+    device) or a torch.device; board: (height, width) of the engine, None = whichever the device has (_any_engine).  The
+    stream is torch's current one on that device."""
     torch = _torch()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
-        raise ValueError("HIP operators take contiguous float32 device tensors")
+    if isinstance(x, torch.device):
+        dev = x
+    else:
+        _check(x, "HIP operators take contiguous float32 device tensors")
+        dev = x.device
+    hnd = _any_engine(dev.index or 0) if board is None else _engine(board[0], board[1], dev.index or 0)
+    return _native.hip(), hnd, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _board(x, layout=DENSE):
+    """(height, width) of the board a tensor [n][C][H][W] in `layout` holds"""
     h, w = int(x.shape[2]), int(x.shape[3])
     if layout == ROWS16:
         if (h, w) != (15, 16):
             raise ValueError("padded-row tensors are [n][C][15][16]")
         w = 15
-    return _native.hip(), _engine(h, w, x.device.index or 0), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    return h, w
 
 
 def _ptr(t):
@@ -59,7 +92,8 @@ def _ptr(t):
 
 
 def _empty(shape, like):
-    return _torch().empty(shape, dtype=_torch().float32, device=like.device)
+    torch = _torch()
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
 def is_trunk_shape(weight, x, layout):
@@ -72,16 +106,12 @@ def is_trunk_shape(weight, x, layout):
 def wino_pack_many(weights, out=None):
     """weights [count][128][128][3][3] (one contiguous tensor) -> [count][2][apz_wino_packed_size()]: every layer's
     transformed weights for the forward convolution ([:, 0]) and the data-gradient convolution ([:, 1]), one launch."""
-    torch = _torch()
-    if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and
-            tuple(weights.shape[1:]) == (128, 128, 3, 3)):
-        raise ValueError("wino_pack_many takes a contiguous float32 device tensor [count][128][128][3][3]")
-    L = _native.hip()
-    hnd = _engine(15, 15, weights.device.index or 0)
+    _check(weights, "wino_pack_many takes a contiguous float32 device tensor [count][128][128][3][3]", None,
+           tuple(weights.shape[:1]) + (128, 128, 3, 3))
+    L, hnd, stream = _ctx(weights, (15, 15))
     count = int(weights.shape[0])
     if out is None:
         out = _empty((count, 2, L.apz_wino_packed_size()), weights)
-    stream = C.c_void_p(torch.cuda.current_stream(weights.device).cuda_stream)
     _ck(L, L.apz_wino_pack_many(hnd, weights.data_ptr(), count, out.data_ptr(), stream))
     return out
 
@@ -91,18 +121,15 @@ def wino3h_pack_many(weights, biases=None, out=None, flag=None):
     zero), one contiguous float32 device tensor each -> (upk [count][2][apz_wino3h_packed_size()], bias [count][2][256])
     for the forward ([:, 0]) and the data gradient ([:, 1]), one launch.  out: such a pair to fill again; flag: a device
     int32 word the launch zeroes (the overflow word of the step that follows)."""
-    torch = _torch()
-    if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and
-            tuple(weights.shape[1:]) == (128, 128, 3, 3)):
-        raise ValueError("wino3h_pack_many takes a contiguous float32 device tensor [count][128][128][3][3]")
+    _check(weights, "wino3h_pack_many takes a contiguous float32 device tensor [count][128][128][3][3]", None,
+           tuple(weights.shape[:1]) + (128, 128, 3, 3))
     count = int(weights.shape[0])
-    if biases is not None and not (biases.is_contiguous() and biases.dtype == torch.float32 and tuple(biases.shape) == (count, 128)):
+    if biases is not None and not (biases.is_contiguous() and biases.dtype == _torch().float32 and
+                                   tuple(biases.shape) == (count, 128)):
         raise ValueError("biases: a contiguous float32 [count][128] tensor")
-    L = _native.hip()
-    hnd = _engine(15, 15, weights.device.index or 0)
+    L, hnd, stream = _ctx(weights, (15, 15))
     if out is None:
         out = (_empty((count, 2, L.apz_wino3h_packed_size()), weights), _empty((count, 2, 256), weights))
-    stream = C.c_void_p(torch.cuda.current_stream(weights.device).cuda_stream)
     _ck(L, L.apz_wino3h_pack_many(hnd, weights.data_ptr(), _ptr(biases), count, out[0].data_ptr(), out[1].data_ptr(), _ptr(flag),
                                   stream))
     return out
@@ -111,13 +138,12 @@ def wino3h_pack_many(weights, biases=None, out=None, flag=None):
 def conv3x3_fwd_stats_f16x2(x, upk, bias, flag):
     """conv3x3_fwd_stats on the f16x2 kernel: upk / bias = one layer's forward pair of wino3h_pack_many.  -> (y, stats);
     a non-finite output sets the int32 device word `flag` to 1."""
-    torch = _torch()
-    L, hnd, stream = _ctx(x, ROWS16)
+    L, hnd, stream = _ctx(x, _board(x, ROWS16))
     if tuple(x.shape[1:]) != (128, 15, 16):
         raise ValueError("conv3x3_fwd_stats_f16x2: the 128-channel trunk in the padded-row layout")
     n = int(x.shape[0])
     y = _empty(tuple(x.shape), x)
-    stats = torch.empty((128, n, 2), dtype=torch.float64, device=x.device)
+    stats = _torch().empty((128, n, 2), dtype=_torch().float64, device=x.device)
     _ck(L, L.apz_wino3h_conv_stats(hnd, x.data_ptr(), upk.data_ptr(), bias.data_ptr(), y.data_ptr(), stats.data_ptr(), n,
                                    flag.data_ptr(), stream))
     return y, stats
@@ -127,7 +153,7 @@ def conv3x3_dgrad_f16x2(dy, upk, bias, dymax, flag, add=None):
     """conv3x3_dgrad on the f16x2 kernel (padded rows): upk / bias = one layer's data-gradient pair of wino3h_pack_many;
     dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two input scale; NaN entries are
     ignored, a +inf entry sets `flag`); (+ add)."""
-    L, hnd, stream = _ctx(dy, ROWS16)
+    L, hnd, stream = _ctx(dy, _board(dy, ROWS16))
     if tuple(dy.shape[1:]) != (128, 15, 16) or (add is not None and add.shape != dy.shape):
         raise ValueError("conv3x3_dgrad_f16x2: the 128-channel trunk in the padded-row layout")
     n = int(dy.shape[0])
@@ -142,7 +168,7 @@ def conv3x3_wgrad_f16x2(x, dy, dymax, flag):
     dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two scale of dy); flag = the int32
     overflow word, set -- never cleared -- when the transformed activations leave the fp16 range, a partial result is not
     finite or dymax holds +inf."""
-    L, hnd, stream = _ctx(x, ROWS16)
+    L, hnd, stream = _ctx(x, _board(x, ROWS16))
     if x.dim() != 4 or tuple(x.shape[1:]) != (128, 15, 16) or dy.shape != x.shape:
         raise ValueError("conv3x3_wgrad_f16x2: the 128 -> 128 trunk shape in the padded-row layout")
     if int(dymax.numel()) < 1:
@@ -156,12 +182,14 @@ def conv3x3_wgrad_f16x2(x, dy, dymax, flag):
 def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     """conv(x, W) (flip: the data-gradient convolution with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]) + bias + resid.
     upk: the layer's transformed weights in that orientation when the caller packed them already (wino_pack_many)."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     co, ci = int(weight.shape[0]), int(weight.shape[1])
     cin_p, cout_p = (co, ci) if flip else (ci, co)
     n = int(x.shape[0])
     if int(x.shape[1]) != cin_p:
         raise ValueError("channel mismatch")
+    if relu and resid is not None and layout != ROWS16:     # (a dense residual is added by a launch of its own: add_)
+        raise ValueError("relu after a dense residual is not provided")
     y = _empty((n, cout_p) + tuple(x.shape[2:]), x)
     # the Winograd kernel works on board pairs x channel halves: from 192 boards on it fills the chip and beats the
     # direct kernel (measured round 1: 24.2 vs 31.0 ms per training step at batch 512, 12.3 vs 11.8 ms at 128);
@@ -173,8 +201,6 @@ def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
         if resid is not None and layout != ROWS16:
             _ck(L, L.apz_wino_conv_add(hnd, x.data_ptr(), upk.data_ptr(), _ptr(bias), None, y.data_ptr(), n, 0, layout, stream))
             add_(y, resid)
-            if relu:
-                raise ValueError("relu after a dense residual is not provided")
         else:
             _ck(L, L.apz_wino_conv_add(hnd, x.data_ptr(), upk.data_ptr(), _ptr(bias), _ptr(resid), y.data_ptr(), n, int(relu),
                                        layout, stream))
@@ -186,8 +212,6 @@ def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     _ck(L, L.apz_conv3x3_fwd(hnd, x.data_ptr(), wpk.data_ptr(), _ptr(bias), y.data_ptr(), n, cin_p, cout_p,
                              int(relu and resid is None), stream))
     if resid is not None:
-        if relu:
-            raise ValueError("relu after a dense residual is not provided")
         add_(y, resid)
     return y
 
@@ -201,8 +225,7 @@ def conv3x3_fwd_stats(x, weight, bias, upk=None):
     """The trunk shape in the padded-row layout, for a BatchNorm that follows: -> (y, stats); stats [128][n][2] float64 =
     per (channel, board) the sum and the sum of squares of y, taken in the convolution's epilogue (bn_fwd(stats=...)
     then makes no pass of its own over y for them)."""
-    torch = _torch()
-    L, hnd, stream = _ctx(x, ROWS16)
+    L, hnd, stream = _ctx(x, _board(x, ROWS16))
     if not is_trunk_shape(weight, x, ROWS16):
         raise ValueError("conv3x3_fwd_stats: the 128 -> 128 trunk shape in the padded-row layout")
     n = int(x.shape[0])
@@ -210,7 +233,7 @@ def conv3x3_fwd_stats(x, weight, bias, upk=None):
         upk = _empty((L.apz_wino_packed_size(),), x)
         _ck(L, L.apz_wino_pack(hnd, weight.data_ptr(), 0, upk.data_ptr(), stream))
     y = _empty(tuple(x.shape), x)
-    stats = torch.empty((128, n, 2), dtype=torch.float64, device=x.device)
+    stats = _torch().empty((128, n, 2), dtype=_torch().float64, device=x.device)
     _ck(L, L.apz_wino_conv_stats(hnd, x.data_ptr(), upk.data_ptr(), _ptr(bias), y.data_ptr(), stats.data_ptr(), n, stream))
     return y, stats
 
@@ -223,7 +246,7 @@ def conv3x3_dgrad(dy, weight, layout=DENSE, add=None, upk=None):
 
 def conv3x3_wgrad(x, dy, layout=DENSE):
     """dw [C_out][C_in][3][3] = sum over boards of x (*) dy."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, ci, co = int(x.shape[0]), int(x.shape[1]), int(dy.shape[1])
     dw = _empty((co, ci, 3, 3), x)
     # through the Winograd domain (3.6x fewer MFMAs; wgrad_wino3_kernel beats the direct kernel from 8 boards on: 14 against
@@ -237,7 +260,7 @@ def conv3x3_wgrad(x, dy, layout=DENSE):
 
 def bias_grad(dy, layout=DENSE):
     """db[c] = sum over boards and cells of dy (pad cells of a padded-row gradient are zero)."""
-    L, hnd, stream = _ctx(dy, layout)
+    L, hnd, stream = _ctx(dy, _board(dy, layout))
     db = _empty((int(dy.shape[1]),), dy)
     _ck(L, L.apz_bias_grad(hnd, dy.data_ptr(), db.data_ptr(), int(dy.shape[0]), int(dy.shape[1]), layout, stream))
     return db
@@ -245,7 +268,7 @@ def bias_grad(dy, layout=DENSE):
 
 def add_(y, x):
     """y += x"""
-    L, hnd, stream = _ctx(y, DENSE if y.shape[3] != 16 else ROWS16)
+    L, hnd, stream = _ctx(y, _board(y, DENSE if y.shape[3] != 16 else ROWS16))
     if y.shape != x.shape:
         raise ValueError("shape mismatch")
     _ck(L, L.apz_add(hnd, y.data_ptr(), x.data_ptr(), y.numel(), stream))
@@ -259,7 +282,7 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, resid=None, relu=True, layout=DENS
     run_mean / run_var are updated in place (momentum = weight of the new batch value).  -> (y, mean, invstd)
     stats: conv3x3_fwd_stats' second result for this x.  want_mask (padded rows): -> (y, mean, invstd, mask), mask = the
     ReLU decisions as uint8 [n][C][60] (4 bits per byte), for bn_bwd(mask=...)."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, c = int(x.shape[0]), int(x.shape[1])
     y = _empty(tuple(x.shape), x)
     mean, invstd = _empty((c,), x), _empty((c,), x)
@@ -279,7 +302,7 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
     sums of dx -- colsum() of it is the bias gradient of the convolution in front (bias_parts() hands such views out).
     dxmax (padded rows): a contiguous float32 [bn_bwd_splits(x, layout)][C] tensor that receives max |dx| per split and
     channel (conv3x3_dgrad_f16x2's dymax)."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, c = int(x.shape[0]), int(x.shape[1])
     dx = _empty(tuple(x.shape), x)
     dres = _empty(tuple(x.shape), x) if want_dres else None
@@ -291,22 +314,18 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
         ld = int(dxsum.stride(0))
     if mask is not None and (tuple(mask.shape) != (n, c, 60) or mask.dtype != _torch().uint8 or not mask.is_contiguous()):
         raise ValueError("mask: contiguous uint8 [n][C][60]")
-    if dxmax is None:
-        _ck(L, L.apz_bn_bwd(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
-                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, n, c, layout, int(relu),
-                            stream))
-        return dx, dres, dgamma, dbeta
-    if tuple(dxmax.shape) != (bn_bwd_splits(x, layout), c) or not dxmax.is_contiguous() or dxmax.dtype != _torch().float32:
+    if dxmax is not None and (tuple(dxmax.shape) != (bn_bwd_splits(x, layout), c) or not dxmax.is_contiguous() or
+                              dxmax.dtype != _torch().float32):
         raise ValueError("dxmax: a contiguous float32 [splits][C] tensor")
     _ck(L, L.apz_bn_bwd_max(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
-                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, dxmax.data_ptr(), n, c,
+                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, _ptr(dxmax), n, c,
                             layout, int(relu), stream))
     return dx, dres, dgamma, dbeta
 
 
 def bn_bwd_splits(x, layout=DENSE):
     """rows of bn_bwd's dxsum matrix for tensors of x's shape"""
-    L, hnd, _ = _ctx(x, layout)
+    L, hnd, _ = _ctx(x, _board(x, layout))
     s = L.apz_bn_bwd_splits(hnd, int(x.shape[0]), int(x.shape[1]), layout)
     _ck(L, s)
     return int(s)
@@ -314,13 +333,11 @@ def bn_bwd_splits(x, layout=DENSE):
 
 def colsum(m, scale=1.0):
     """out[j] = scale * sum_i m[i][j] (fixed order, double accumulation); m: contiguous [rows][cols] float32"""
-    torch = _torch()
-    if not (m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and m.dim() == 2):
+    if m.dim() != 2:
         raise ValueError("colsum takes a contiguous float32 device matrix")
-    L = _native.hip()
-    hnd = _any_engine(m.device.index or 0)
+    _check(m, "colsum takes a contiguous float32 device matrix")
+    L, hnd, stream = _ctx(m)
     out = _empty((int(m.shape[1]),), m)
-    stream = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
     _ck(L, L.apz_colsum(hnd, m.data_ptr(), out.data_ptr(), int(m.shape[0]), int(m.shape[1]), scale, stream))
     return out
 
@@ -328,7 +345,7 @@ def colsum(m, scale=1.0):
 # ---- heads ----------------------------------------------------------------------------------------------------------
 def conv1x1_fwd(x, weight, bias=None, layout=DENSE):
     """y [n][CO][H][W] (dense) = W x + b, CO <= 8."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, c, co = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
     h, w = int(x.shape[2]), (15 if layout == ROWS16 else int(x.shape[3]))
     y = _empty((n, co, h, w), x)
@@ -338,7 +355,7 @@ def conv1x1_fwd(x, weight, bias=None, layout=DENSE):
 
 def conv1x1_bwd(x, weight, dy, layout=DENSE, dx=None):
     """-> (dx, dw, db).  dx given: the gradient is ADDED to it (the second head); else a new tensor in x's layout."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, c, co = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
     acc = dx is not None
     if dx is None:
@@ -352,7 +369,7 @@ def conv1x1_bwd(x, weight, dy, layout=DENSE, dx=None):
 def conv1x1_bwd_pair(x, w1, dy1, w2, dy2, layout=DENSE):
     """Two 1x1 convolutions of the same input (the two heads): -> (dx, dw1, db1, dw2, db2), dx = both heads' input
     gradients added, in one pass over x."""
-    L, hnd, stream = _ctx(x, layout)
+    L, hnd, stream = _ctx(x, _board(x, layout))
     n, c, co1, co2 = int(x.shape[0]), int(x.shape[1]), int(w1.shape[0]), int(w2.shape[0])
     dx = _empty(tuple(x.shape), x)
     dw = _empty((co1 + co2, c), x)
@@ -361,25 +378,9 @@ def conv1x1_bwd_pair(x, w1, dy1, w2, dy2, layout=DENSE):
     return dx, dw[:co1].view(w1.shape), bias_grad(dy1, DENSE), dw[co1:].view(w2.shape), bias_grad(dy2, DENSE)
 
 
-def _any_engine(device_index):
-    """Operators that do not depend on the board (FullyConnected, Dropout, Adam) run on whichever engine this device
-    already has (the net's own board size), else on a 15x15 one."""
-    for (h, w, d), hnd in _ENGINES.items():
-        if d == device_index:
-            return hnd
-    return _engine(15, 15, device_index)
-
-
-def _ctx2(x):
-    torch = _torch()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
-        raise ValueError("HIP operators take contiguous float32 device tensors")
-    return _native.hip(), _any_engine(x.device.index or 0), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-
-
 def fc_fwd(x, weight, bias=None):
     """y [n][N] = x [n][K] W[N][K]^T + b"""
-    L, hnd, stream = _ctx2(x)
+    L, hnd, stream = _ctx(x)
     n, k, nn = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
     y = _empty((n, nn), x)
     _ck(L, L.apz_fc_fwd(hnd, x.data_ptr(), weight.data_ptr(), _ptr(bias), y.data_ptr(), n, k, nn, stream))
@@ -388,7 +389,7 @@ def fc_fwd(x, weight, bias=None):
 
 def fc_bwd(x, weight, dy):
     """-> (dx, dw, db)"""
-    L, hnd, stream = _ctx2(x)
+    L, hnd, stream = _ctx(x)
     n, k, nn = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
     dx, dw, db = _empty((n, k), x), _empty((nn, k), x), _empty((nn,), x)
     _ck(L, L.apz_fc_bwd(hnd, x.data_ptr(), weight.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
@@ -398,7 +399,7 @@ def fc_bwd(x, weight, dy):
 
 def dropout(x, keep, seed, step):
     """y = x * mask / keep, mask = [hash(seed, step, element) < keep]; the same call on dy is the backward pass."""
-    L, hnd, stream = _ctx2(x)
+    L, hnd, stream = _ctx(x)
     y = _empty(tuple(x.shape), x)
     _ck(L, L.apz_dropout(hnd, x.data_ptr(), y.data_ptr(), x.numel(), keep, seed, step, stream))
     return y
@@ -408,10 +409,9 @@ def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=No
     """The reference's loss head (policy_value_net_mxnet.py:180-193) on [n][H*W] logits and [n] value logits.
     -> dict with loss3 = (value loss, policy loss, entropy) [device, 3 floats], dlogits, dvlogit (grads),
     probs, values (outputs).  loss3: a contiguous float32 device tensor of 3 to write the losses into."""
-    L, _, stream = _ctx2(logits)
     n, hw = int(logits.shape[0]), int(logits.shape[1])
     side = int(round(hw ** 0.5))
-    hnd = _engine(side, side, logits.device.index or 0)
+    L, hnd, stream = _ctx(logits, (side, side))
     out = {}
     if pi is not None:
         out["loss3"] = _empty((3,), logits) if loss3 is None else loss3
@@ -428,14 +428,14 @@ def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=No
 # ---- layout ---------------------------------------------------------------------------------------------------------
 def to_rows16(x):
     """dense [n][C][15][15] -> padded rows [n][C][15][16] (pad column zero)"""
-    L, hnd, stream = _ctx(x, DENSE)
+    L, hnd, stream = _ctx(x, _board(x, DENSE))
     y = _empty((int(x.shape[0]), int(x.shape[1]), 15, 16), x)
     _ck(L, L.apz_layout_convert(hnd, x.data_ptr(), y.data_ptr(), int(x.shape[0]) * int(x.shape[1]), 1, stream))
     return y
 
 
 def from_rows16(x):
-    L, hnd, stream = _ctx(x, ROWS16)
+    L, hnd, stream = _ctx(x, _board(x, ROWS16))
     y = _empty((int(x.shape[0]), int(x.shape[1]), 15, 15), x)
     _ck(L, L.apz_layout_convert(hnd, x.data_ptr(), y.data_ptr(), int(x.shape[0]) * int(x.shape[1]), 0, stream))
     return y
@@ -457,12 +457,12 @@ def replay_gather(codes, pi, z, entries, height, width, n_planes=9):
     if n_planes not in (9, 4):
         raise ValueError("n_planes must be 9 or 4")
     cap = int(codes.shape[0])
-    if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape) == (cap, stride)):
-        raise ValueError("codes: a contiguous uint8 device tensor [cap][%d]" % stride)
+    _check(codes, "codes: a contiguous uint8 device tensor [cap][%d]" % stride, torch.uint8, (cap, stride))
     for t, shape, what in ((pi, (cap, hw), "pi"), (z, (cap,), "z")):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and
-                t.device == codes.device):
-            raise ValueError("%s: a contiguous float32 tensor %s on the device of codes" % (what, list(shape)))
+        msg = "%s: a contiguous float32 tensor %s on the device of codes" % (what, list(shape))
+        if t.device != codes.device:
+            raise ValueError(msg)
+        _check(t, msg, None, shape)
     ent = np.asarray(entries).reshape(-1)
     if ent.size and not np.issubdtype(ent.dtype, np.integer):
         raise ValueError("entries must be integers")
@@ -475,9 +475,7 @@ def replay_gather(codes, pi, z, entries, height, width, n_planes=9):
     pis, zs = _empty((k, hw), states), _empty((k,), states)
     if k == 0:
         return states, pis, zs
-    L = _native.hip()
-    hnd = _engine(h, w, codes.device.index or 0)
-    stream = C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)
+    L, hnd, stream = _ctx(codes.device, (h, w))
     _ck(L, L.apz_replay_gather(hnd, codes.data_ptr(), pi.data_ptr(), z.data_ptr(), cap, _native.as_ptr(ent, C.c_int32), k,
                                n_planes, states.data_ptr(), pis.data_ptr(), zs.data_ptr(), stream))
     return states, pis, zs
@@ -488,18 +486,11 @@ def adam_step(entries, lr_t, b1, b2, eps, rescale, device, skip=None):
     """One launch over all tensors.  entries: [(w, grad, m, v, wd)] of float32 device tensors (apz_adam_step).  skip: a
     device int32 word; when it is not zero at the time the launch runs, nothing is updated (apz_adam_step_unless)."""
     import numpy as np
-    torch = _torch()
     tab = np.zeros(len(entries), dtype=[("w", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("n", "i8"), ("wd", "f4"),
                                         ("pad", "i4")])
     for i, (w, g, m, v, wd) in enumerate(entries):
         if g.shape != w.shape or not g.is_contiguous():
             raise ValueError("gradient %d: shape / layout mismatch" % i)
         tab[i] = (w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), wd, 0)
-    L = _native.hip()
-    hnd = _any_engine(device.index or 0)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    if skip is None:
-        _ck(L, L.apz_adam_step(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, stream))
-    else:
-        _ck(L, L.apz_adam_step_unless(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, skip.data_ptr(),
-                                      stream))
+    L, hnd, stream = _ctx(device)
+    _ck(L, L.apz_adam_step_unless(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, _ptr(skip), stream))

@@ -32,6 +32,11 @@ BN_EPS = 1e-3
 BN_MOMENTUM = 0.9
 SIMPLE_CONVS = ("conv1", "conv2", "conv3", "conv4", "conv5", "conv_final")
 DeviceBatch = collections.namedtuple("DeviceBatch", "states pis zs")     # HipTrainer.upload()
+# what the forward pass leaves on the tape for the backward pass: one conv_act layer (x -> Convolution y -> BatchNorm,
+# relu a), and one residual block (x -> convA ya -> bnA, relu ha -> convB yb -> bnB + x, relu out; m / i: the batch mean
+# and 1 / std of each BatchNorm, k: its ReLU decisions as a bit mask, padded rows only)
+ConvAct = collections.namedtuple("ConvAct", "name x y a mean invstd layout")
+Block = collections.namedtuple("Block", "x ya ha ma ia yb out mb ib ka kb")
 
 
 TRAINABLE_SIDES = (15, 8)
@@ -162,7 +167,7 @@ class HipTrainer(object):
             blay = layout
         a, mean, invstd = o.bn_fwd(y, None, p[name + "_beta"], p[name + "_mean"], p[name + "_var"], None, True, blay,
                                    1.0 - BN_MOMENTUM, BN_EPS)
-        return a, (name, x, y, a, mean, invstd, layout)
+        return a, ConvAct(name, x, y, a, mean, invstd, layout)
 
     def _conv_act_bwd(self, da, rec, need_dx, dx_acc=None):
         o, p, g = self.ops, self.p, self.grad
@@ -177,6 +182,35 @@ class HipTrainer(object):
         g[name + "_bias"] = o.bias_grad(dy, layout)
         return o.conv3x3_dgrad(dy, w, layout) if need_dx else None
 
+    def _trunk_conv(self, j):
+        """Trunk convolution j = 2 i - 2 (A of block i) or 2 i - 1 (B): its parameter prefix"""
+        return "conv%s%d" % ("AB"[j % 2], j // 2 + 1)
+
+    def _trunk_conv_fwd(self, x, j):
+        """Trunk convolution j on x -> (y, stats): stats = the per-board sums bn_fwd(stats=...) takes, or None.  Padded rows:
+        on the f16x2 kernel in a fast pass, else on the Winograd kernel, whose epilogue leaves the BatchNorm's sums (no
+        statistics pass; apz_wino_conv_stats is one launch: up to 16384 boards); other nets plain."""
+        o = self.ops
+        if self._fast:
+            return o.conv3x3_fwd_stats_f16x2(x, self._u16[0][j, 0], self._u16[1][j, 0], self._flag)
+        w, b = self.p[self._trunk_conv(j) + "_weight"], self.p[self._trunk_conv(j) + "_bias"]
+        if not self.rows16:
+            return o.conv3x3_fwd(x, w, b, o.DENSE), None
+        if int(x.shape[0]) <= 16384:
+            return o.conv3x3_fwd_stats(x, w, b, upk=self._upk[j, 0])
+        return o.conv3x3_fwd(x, w, b, o.ROWS16, upk=self._upk[j, 0]), None
+
+    def _trunk_conv_dgrad(self, dy, j, skip=None, dymax=None):
+        """The data gradient of trunk convolution j (+ skip: the skip connection's gradient of the same tensor) on the
+        kernel of the pass; dymax: bn_bwd's dxmax for dy (the f16x2 launch's input scale)."""
+        o = self.ops
+        if self._fast:
+            return o.conv3x3_dgrad_f16x2(dy, self._u16[0][j, 1], self._u16[1][j, 1], dymax, self._flag, add=skip)
+        w = self.p[self._trunk_conv(j) + "_weight"]
+        if not self.rows16:
+            return o.conv3x3_dgrad(dy, w, o.DENSE, add=skip)
+        return o.conv3x3_dgrad(dy, w, o.ROWS16, add=skip, upk=self._upk[j, 1])
+
     def _forward(self, states, step):
         o, p = self.ops, self.p
         tape = {"blocks": [], "stack": []}
@@ -184,39 +218,22 @@ class HipTrainer(object):
             x, rec = self._conv_act_fwd(states, "res_conv1", o.DENSE)
             tape["stem"] = rec
             lay = o.ROWS16 if self.rows16 else o.DENSE
-            upk = u16 = None
-            if self.rows16:
+            if self.rows16:             # every trunk layer's weights packed for this pass's kernel, both orientations, one launch
                 x = o.to_rows16(x)
                 if self._fast:          # (the pack launch zeroes the step's overflow word)
-                    self._u16 = u16 = o.wino3h_pack_many(self._trunk_w, self._trunk_b, self._u16, self._flag)
+                    self._u16 = o.wino3h_pack_many(self._trunk_w, self._trunk_b, self._u16, self._flag)
                 else:
-                    self._upk = upk = o.wino_pack_many(self._trunk_w, self._upk)
-            tape["upk"], tape["u16"] = upk, u16
+                    self._upk = o.wino_pack_many(self._trunk_w, self._upk)
+            wm = self.rows16            # padded rows: the ReLU decisions as a byte per four elements for the backward pass
             for i in range(1, self.n_blocks + 1):
-                A, B = "A%d" % i, "B%d" % i
-                ua, ub = (upk[2 * i - 2, 0], upk[2 * i - 1, 0]) if upk is not None else (None, None)
-                sa = sb = None
-                fused = upk is not None and int(x.shape[0]) <= 16384       # (apz_wino_conv_stats: one launch)
-                if u16 is not None:     # the same contract on the f16x2 kernel
-                    ya, sa = o.conv3x3_fwd_stats_f16x2(x, u16[0][2 * i - 2, 0], u16[1][2 * i - 2, 0], self._flag)
-                elif fused:             # the Winograd kernel's epilogue leaves the BatchNorm's per-board sums: no statistics pass
-                    ya, sa = o.conv3x3_fwd_stats(x, p["conv" + A + "_weight"], p["conv" + A + "_bias"], upk=ua)
-                else:
-                    ya = o.conv3x3_fwd(x, p["conv" + A + "_weight"], p["conv" + A + "_bias"], lay, upk=ua)
-                wm = self.rows16        # padded rows: the ReLU decisions as a byte per four elements for the backward pass
-                ha, ma, ia, *ka = o.bn_fwd(ya, p["bn" + A + "_gamma"], p["bn" + A + "_beta"], p["bn" + A + "_moving_mean"],
-                                           p["bn" + A + "_moving_var"], None, True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sa,
-                                           want_mask=wm)
-                if u16 is not None:
-                    yb, sb = o.conv3x3_fwd_stats_f16x2(ha, u16[0][2 * i - 1, 0], u16[1][2 * i - 1, 0], self._flag)
-                elif fused:
-                    yb, sb = o.conv3x3_fwd_stats(ha, p["conv" + B + "_weight"], p["conv" + B + "_bias"], upk=ub)
-                else:
-                    yb = o.conv3x3_fwd(ha, p["conv" + B + "_weight"], p["conv" + B + "_bias"], lay, upk=ub)
-                out, mb, ib, *kb = o.bn_fwd(yb, p["bn" + B + "_gamma"], p["bn" + B + "_beta"], p["bn" + B + "_moving_mean"],
-                                            p["bn" + B + "_moving_var"], x, True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sb,
-                                            want_mask=wm)
-                tape["blocks"].append((x, ya, ha, ma, ia, yb, out, mb, ib, ka[0] if ka else None, kb[0] if kb else None))
+                A, B = "bnA%d" % i, "bnB%d" % i
+                ya, sa = self._trunk_conv_fwd(x, 2 * i - 2)
+                ha, ma, ia, *ka = o.bn_fwd(ya, p[A + "_gamma"], p[A + "_beta"], p[A + "_moving_mean"], p[A + "_moving_var"], None,
+                                           True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sa, want_mask=wm)
+                yb, sb = self._trunk_conv_fwd(ha, 2 * i - 1)
+                out, mb, ib, *kb = o.bn_fwd(yb, p[B + "_gamma"], p[B + "_beta"], p[B + "_moving_mean"], p[B + "_moving_var"], x,
+                                            True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sb, want_mask=wm)
+                tape["blocks"].append(Block(x, ya, ha, ma, ia, yb, out, mb, ib, ka[0] if ka else None, kb[0] if kb else None))
                 x = out
         else:
             lay = o.DENSE
@@ -252,43 +269,33 @@ class HipTrainer(object):
         # the two heads share their input: both BatchNorm backward passes, then ONE pass over the trunk output for dx
         dys = []
         for da, rec in ((dpol.view(n, 4, self.side, self.side), tape["pol"]), (dval.view(n, 2, self.side, self.side), tape["val"])):
-            name, _, y, a, mean, invstd, _ = rec
-            dy, _, _, g[name + "_beta"] = o.bn_bwd(da, y, a, None, mean, invstd, True, False, o.DENSE)
+            dy, _, _, g[rec.name + "_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, o.DENSE)
             dys.append(dy)
-        xh = tape["pol"][1]
         dx, g["conv3_1_1_weight"], g["conv3_1_1_bias"], g["conv3_2_1_weight"], g["conv3_2_1_bias"] = o.conv1x1_bwd_pair(
-            xh, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"][6])
+            tape["pol"].x, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"].layout)
         if self.kind == "resnet":
-            upk, u16 = tape.get("upk"), tape.get("u16")
             # the trunk convolutions' bias gradients = column sums of the dx their BatchNorms hand back: every bn_bwd
             # leaves its per-split sums in its own columns of ONE matrix, added after the loop in one launch
             nb = self.n_blocks
-            nf = int(tape["blocks"][0][1].shape[1]) if nb else 0
-            parts = o._empty((o.bn_bwd_splits(tape["blocks"][0][1], lay), 2 * nb * nf), dx) if nb else None
+            nf = int(tape["blocks"][0].ya.shape[1]) if nb else 0
+            parts = o._empty((o.bn_bwd_splits(tape["blocks"][0].ya, lay), 2 * nb * nf), dx) if nb else None
             # f16x2: each bn_bwd also leaves max |dx| per split and channel, which the data-gradient launch right behind it
             # folds into its input scale (one buffer: every pair runs in stream order)
-            dmax = o._empty((parts.shape[0], nf), dx) if (u16 is not None and nb) else None
+            dmax = o._empty((parts.shape[0], nf), dx) if (self._fast and nb) else None
             for i in range(nb, 0, -1):
                 A, B = "A%d" % i, "B%d" % i
-                x, ya, ha, ma, ia, yb, out, mb, ib, ka, kb = tape["blocks"][i - 1]
-                ua, ub = (upk[2 * i - 2, 1], upk[2 * i - 1, 1]) if upk is not None else (None, None)
+                blk = tape["blocks"][i - 1]
                 ca, cb = (2 * i - 2) * nf, (2 * i - 1) * nf
-                dyb, dskip, g["bn" + B + "_gamma"], g["bn" + B + "_beta"] = o.bn_bwd(dx, yb, out, p["bn" + B + "_gamma"], mb, ib,
-                                                                                    True, True, lay, dxsum=parts[:, cb:cb + nf], mask=kb,
-                                                                                    dxmax=dmax)
-                g["conv" + B + "_weight"] = o.conv3x3_wgrad(ha, dyb, lay)
-                if u16 is not None:
-                    dha = o.conv3x3_dgrad_f16x2(dyb, u16[0][2 * i - 1, 1], u16[1][2 * i - 1, 1], dmax, self._flag)
-                else:
-                    dha = o.conv3x3_dgrad(dyb, p["conv" + B + "_weight"], lay, upk=ub)
-                dya, _, g["bn" + A + "_gamma"], g["bn" + A + "_beta"] = o.bn_bwd(dha, ya, ha, p["bn" + A + "_gamma"], ma, ia,
-                                                                                True, False, lay, dxsum=parts[:, ca:ca + nf], mask=ka,
-                                                                                dxmax=dmax)
-                g["conv" + A + "_weight"] = o.conv3x3_wgrad(x, dya, lay)
-                if u16 is not None:
-                    dx = o.conv3x3_dgrad_f16x2(dya, u16[0][2 * i - 2, 1], u16[1][2 * i - 2, 1], dmax, self._flag, add=dskip)
-                else:
-                    dx = o.conv3x3_dgrad(dya, p["conv" + A + "_weight"], lay, add=dskip, upk=ua)   # trunk + skip gradients meet
+                dyb, dskip, g["bn" + B + "_gamma"], g["bn" + B + "_beta"] = o.bn_bwd(
+                    dx, blk.yb, blk.out, p["bn" + B + "_gamma"], blk.mb, blk.ib, True, True, lay, dxsum=parts[:, cb:cb + nf],
+                    mask=blk.kb, dxmax=dmax)
+                g["conv" + B + "_weight"] = o.conv3x3_wgrad(blk.ha, dyb, lay)
+                dha = self._trunk_conv_dgrad(dyb, 2 * i - 1, None, dmax)
+                dya, _, g["bn" + A + "_gamma"], g["bn" + A + "_beta"] = o.bn_bwd(
+                    dha, blk.ya, blk.ha, p["bn" + A + "_gamma"], blk.ma, blk.ia, True, False, lay, dxsum=parts[:, ca:ca + nf],
+                    mask=blk.ka, dxmax=dmax)
+                g["conv" + A + "_weight"] = o.conv3x3_wgrad(blk.x, dya, lay)
+                dx = self._trunk_conv_dgrad(dya, 2 * i - 2, dskip, dmax)       # trunk + skip gradients meet
             db = o.colsum(parts) if nb else None
             for i in range(1, nb + 1):
                 g["convA%d_bias" % i] = db[(2 * i - 2) * nf:(2 * i - 1) * nf]
@@ -320,14 +327,10 @@ class HipTrainer(object):
         when it is set (train_step does the same without the extra synchronisation)."""
         if self.trunk_arith == "f32":
             return self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
-        if not isinstance(state_batch, DeviceBatch):
-            state_batch = self.upload(state_batch, mcts_probs, winner_batch)
-        self._stat_snap.copy_(self._stat_buf)
-        loss3 = self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True)
+        batch, loss3 = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape)
         if int(self._flag.view(self.torch.int32).item()) == 0:
             return loss3
-        self._repeat_exact()
-        return self._loss_and_grads(state_batch, keep_tape=keep_tape)
+        return self._repeat_exact(batch, keep_tape)
 
     def _loss_and_grads(self, state_batch, mcts_probs=None, winner_batch=None, keep_tape=False, fast=False, loss3=None):
         if isinstance(state_batch, DeviceBatch):
@@ -346,11 +349,22 @@ class HipTrainer(object):
         self.tape = tape if keep_tape else None
         return out["loss3"]
 
-    def _repeat_exact(self):
+    def _fast_pass(self, state_batch, mcts_probs, winner_batch, keep_tape, loss3=None):
+        """trunk_arith "f16x2": the moving statistics snapshotted (a repeated pass must not move them twice), then the pass
+        on the f16x2 kernels -> (the mini-batch on the device, loss3).  The caller reads the overflow word and, when it is
+        set, calls _repeat_exact."""
+        if not isinstance(state_batch, DeviceBatch):
+            state_batch = self.upload(state_batch, mcts_probs, winner_batch)
+        self._stat_snap.copy_(self._stat_buf)
+        return state_batch, self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True, loss3=loss3)
+
+    def _repeat_exact(self, batch, keep_tape):
         """An f16x2 launch of the pass just queued left the fp16 range: its gradients never reached Adam; the moving
-        statistics go back to their values at the start of the step, which is then taken again on the exact kernels."""
+        statistics go back to their values at the start of the pass, which is then taken again on the exact kernels
+        -> loss3."""
         self.trunk_overflows += 1
         self._stat_buf.copy_(self._stat_snap)
+        return self._loss_and_grads(batch, keep_tape=keep_tape)
 
     def relu_masks(self):
         """{layer: [n][C][H][W] bool} -- which activations of the kept forward pass were positive.  (A comparator that
@@ -360,28 +374,26 @@ class HipTrainer(object):
         tape, out = self.tape, {}
         recs = [tape["pol"], tape["val"]] + tape["stack"] + ([tape["stem"]] if "stem" in tape else [])
         for rec in recs:
-            out[rec[0]] = rec[3] > 0
+            out[rec.name] = rec.a > 0
         for i, blk in enumerate(tape["blocks"], 1):
-            out["bnA%d" % i] = cut(blk[2]) > 0
-            out["block%d" % i] = cut(blk[6]) > 0
+            out["bnA%d" % i] = cut(blk.ha) > 0
+            out["block%d" % i] = cut(blk.out) > 0
         return out
 
     def train_step(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape=False):
         """One optimiser step -> (loss, entropy).  state_batch may be upload()'s DeviceBatch (mcts_probs / winner_batch are
         then ignored)."""
         if self.trunk_arith == "f16x2":
-            if not isinstance(state_batch, DeviceBatch):
-                state_batch = self.upload(state_batch, mcts_probs, winner_batch)
-            self._stat_snap.copy_(self._stat_buf)
-            self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True, loss3=self._word[:3])
+            batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=self._word[:3])
             self.t += 1
             self._adam(learning_rate, skip=self._flag)      # skipped on the device when the overflow word is set
             w4 = self._word.cpu().numpy()      # the losses and the overflow word: still the step's only synchronisation
             if w4[3:].view(np.uint32)[0] == 0:
                 return float(w4[0] + w4[1]), float(w4[2])
             self.t -= 1
-            self._repeat_exact()
-        loss3 = self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
+            loss3 = self._repeat_exact(batch, keep_tape)
+        else:
+            loss3 = self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
         self.t += 1
         self._adam(learning_rate)
         l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
@@ -486,63 +498,33 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
     PolicyValueNet) supplies old/new predictions when given, else the trainer's own inference
     graph.  -> (loss, entropy, kl, lr_multiplier); `monitors` (a dict, optional) receives the reference's value-head
     monitors explained_var_old / explained_var_new (train_mxnet.py:222-227) and the learning rate used.
-    mini_batch may also be the DeviceBatch a code replay buffer draws (alphapig_amd/replay.py): see _policy_update_batch."""
-    if isinstance(mini_batch, DeviceBatch):
-        return _policy_update_batch(trainer, mini_batch, learn_rate, lr_multiplier, epochs, kl_targ, evaluator, monitors)
-    states = np.stack([np.ascontiguousarray(d[0]) for d in mini_batch]).astype(np.float32)
-    pis = np.stack([d[1] for d in mini_batch]).astype(np.float32)
-    zs = np.array([d[2] for d in mini_batch], dtype=np.float32)
+    mini_batch may also be the DeviceBatch a code replay buffer draws (alphapig_amd/replay.py), already stacked.  NumPy
+    arrays (CompactReplayBuffer): uploaded once, like the list's.  Device tensors (DeviceReplayBuffer): no stacking and no
+    upload; the KL monitor's forwards read the planes where they are (`policy_value_dev`; an evaluator without it gets them
+    on the host, once) and zs come to the host once for the explained-variance monitors.  The KL stays the NumPy expression
+    on the probabilities copied back: it decides the early stop and the learning-rate multiplier, so its bits must not
+    depend on the buffer kind."""
     pv = (evaluator.policy_value if evaluator is not None else trainer.policy_value)
-    old_probs, old_v = pv(states)
-    new_v = old_v
-    loss = entropy = kl = 0.0
-    batch = trainer.upload(states, pis, zs) if hasattr(trainer, "upload") else states     # once for all epochs
-    lr_used = lr_multiplier                               # (the reference logs learn_rate * the multiplier the epochs ran with)
-    for _ in range(epochs):
-        loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
-        if evaluator is not None:
-            if hasattr(trainer, "sync_evaluator") and hasattr(evaluator, "load_device_params"):
-                trainer.sync_evaluator(evaluator)
-            else:
-                evaluator.set_params(trainer.get_params())
-        new_probs, new_v = pv(states)
-        kl = float(np.mean(np.sum(old_probs * (np.log(old_probs + 1e-10) - np.log(new_probs + 1e-10)), axis=1)))
-        if kl > kl_targ * 4:
-            break
-    if kl > kl_targ * 2 and lr_multiplier > 0.05:        # train_mxnet.py:215-218
-        lr_multiplier /= 1.5
-    elif kl < kl_targ / 2 and lr_multiplier < 20:
-        lr_multiplier *= 1.5
-    if monitors is not None:
-        monitors["explained_var_old"] = explained_variance(zs, old_v)
-        monitors["explained_var_new"] = explained_variance(zs, new_v)
-        monitors["learn_rate"] = float(learn_rate * lr_used)
-    return loss, entropy, kl, lr_multiplier
-
-
-def _policy_update_batch(trainer, mini_batch, learn_rate, lr_multiplier, epochs, kl_targ, evaluator, monitors):
-    """policy_update on a mini-batch that is already stacked.  NumPy arrays (CompactReplayBuffer): uploaded once, like the
-    list's.  Device tensors (DeviceReplayBuffer): no stacking and no upload; the KL monitor's forwards read the planes where
-    they are (`policy_value_dev`; an evaluator without it gets them on the host, once) and zs come to the host once for the
-    explained-variance monitors.  The KL stays the NumPy expression on the probabilities copied back: it decides the early
-    stop and the learning-rate multiplier, so its bits must not depend on the buffer kind."""
-    states, pis, zs = mini_batch
-    pv = (evaluator.policy_value if evaluator is not None else trainer.policy_value)
-    if isinstance(states, np.ndarray):
-        states, pis, zs = (np.ascontiguousarray(a, dtype=np.float32) for a in (states, pis, zs))
-        batch = trainer.upload(states, pis, zs) if hasattr(trainer, "upload") else states     # once for all epochs
-    else:
-        batch = mini_batch
+    if isinstance(mini_batch, DeviceBatch) and not isinstance(mini_batch.states, np.ndarray):
+        batch, (states, pis, zs) = mini_batch, mini_batch
         pv_dev = getattr(evaluator if evaluator is not None else trainer, "policy_value_dev", None)
         if pv_dev is not None:
             pv = pv_dev
         else:
             states = states.cpu().numpy()
         pis, zs = None, zs.cpu().numpy()           # (train_step ignores them beside a DeviceBatch)
+    else:
+        if isinstance(mini_batch, DeviceBatch):
+            states, pis, zs = (np.ascontiguousarray(a, dtype=np.float32) for a in mini_batch)
+        else:
+            states = np.stack([np.ascontiguousarray(d[0]) for d in mini_batch]).astype(np.float32)
+            pis = np.stack([d[1] for d in mini_batch]).astype(np.float32)
+            zs = np.array([d[2] for d in mini_batch], dtype=np.float32)
+        batch = trainer.upload(states, pis, zs) if hasattr(trainer, "upload") else states     # once for all epochs
     old_probs, old_v = pv(states)
     new_v = old_v
     loss = entropy = kl = 0.0
-    lr_used = lr_multiplier
+    lr_used = lr_multiplier                               # (the reference logs learn_rate * the multiplier the epochs ran with)
     for _ in range(epochs):
         loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
         if evaluator is not None:

@@ -3,6 +3,7 @@
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/route_trace.py     (on the GPU, once per tree)
     python tools/route_trace.py --compare A_kernel_trace.csv B_kernel_trace.csv            (on the host)
+    python tools/route_trace.py --compare --whole A_kernel_trace.csv B_kernel_trace.csv    (traces of any other run)
 
 Bits cannot tell the small-batch trunk kernels from the batched ones (they are bit-equal by contract); the launch sequence
 can.  The run makes one forward per case below: every engine of tests/test_gpu_forward_modes.py at 5 and at 40 boards, every
@@ -11,7 +12,8 @@ automatic response on.  In front of forward k and behind it the run launches the
 the trace at those launches and compares, case by case (the run prints their numbers), the sequence of (kernel, grid,
 workgroup, LDS bytes) between them.  The runtime's own copy kernels are left out: whether a hipMemcpyAsync becomes such a
 kernel or a DMA transfer is its choice from run to run (its fill kernels, the ticket resets, stay in).  Exit status 1 on any
-difference."""
+difference.  --whole: the traces have no separator launches (tools/train_digest.py under rocprofv3): each is one case, compared
+from its first launch to its last."""
 import csv
 import os
 import sys
@@ -83,25 +85,28 @@ def run():
         print("%3d %s" % (k, label), flush=True)
 
 
-def forwards(path):
-    """kernel-trace CSV -> {case + 1: [(kernel, grid, workgroup, LDS)] between the case's two sampler launches}"""
+def forwards(path, whole=False):
+    """kernel-trace CSV -> {case + 1: [(kernel, grid, workgroup, LDS)] between the case's two sampler launches}
+    (whole: {1: every launch of the trace})"""
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
     shape = lambda r: (r["Kernel_Name"].split("(")[0],) + tuple(
         int(r[c + a]) for c in ("Grid_Size_", "Workgroup_Size_") for a in "XYZ") + (int(r["LDS_Block_Size"]),)
-    out, cur = {}, None
+    out, cur = ({1: []}, None) if whole else ({}, None)
+    if whole:
+        cur = out[1]
     for r in rows:
         s = shape(r)
         if s[0].startswith("__amd_rocclr_copy"):
             continue
-        if SEPARATOR in s[0]:
+        if SEPARATOR in s[0] and not whole:
             cur = out.setdefault(s[1] // s[4], []) if cur is None else None     # (one 64-thread workgroup per row)
         elif cur is not None:
             cur.append(s)
     return out
 
 
-def compare(a, b):
-    fa, fb = forwards(a), forwards(b)
+def compare(a, b, whole=False):
+    fa, fb = forwards(a, whole), forwards(b, whole)
     bad = 0
     for k in sorted(set(fa) | set(fb)):
         same = fa.get(k) == fb.get(k)
@@ -119,5 +124,6 @@ def compare(a, b):
 if __name__ == "__main__":
     if "--compare" in sys.argv:
         i = sys.argv.index("--compare")
-        sys.exit(compare(sys.argv[i + 1], sys.argv[i + 2]))
+        paths = [a for a in sys.argv[i + 1:] if a != "--whole"]
+        sys.exit(compare(paths[0], paths[1], "--whole" in sys.argv))
     run()
