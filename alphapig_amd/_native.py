@@ -130,7 +130,8 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_conv3x3_bench", "apz_layer_io", "apz_layer_frame", "apz_set_profiling", "apz_kernel_time_ms", "apz_prewarm", "apz_test_select_trunk", "apz_set_trunk_arith", "apz_trunk_overflows",
                "apz_set_trunk_act_exponents", "apz_get_trunk_act_exponents", "apz_calibrate_trunk_planes", "apz_calibrate_trunk_codes",
                "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host",
-               "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys"]
+               "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys",
+               "apz_bn_fwd_frame", "apz_bn_bwd_frame", "apz_frame_planes_dev", "apz_conv1x1_fwd_frame", "apz_conv1x1_bwd2_frame"]
 
 
 def _one_hip_runtime():
@@ -304,6 +305,11 @@ def hip():
         "apz_set_leaf_symmetry": (C.c_int, [vp, C.c_int, C.c_uint64]),
         "apz_get_leaf_symmetry": (C.c_int, [vp, i32p, _ptr(C.c_uint64)]),
         "apz_leaf_symmetry_keys": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_uint64, u8p]),
+        "apz_bn_fwd_frame": (C.c_int, [vp] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp]),
+        "apz_bn_bwd_frame": (C.c_int, [vp] * 13 + [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "apz_frame_planes_dev": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
+        "apz_conv1x1_fwd_frame": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "apz_conv1x1_bwd2_frame": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

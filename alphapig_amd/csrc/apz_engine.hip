@@ -29,6 +29,7 @@
 #include "wgrad_wino3h.h"
 #include "sampler.h"
 #include "conv_train.h"
+#include "bn_frame.h"
 #include "heads_train.h"
 #include "weights_pack.h"
 #include "act_max.h"
@@ -2159,6 +2160,62 @@ int apz_bn_bwd_max(apz_engine* e, const void* dy_dev, const void* x_dev, const v
     });
 }
 
+// ---- framed boards in the training step (csrc/bn_frame.h): the padded-row BatchNorm with a board mask, on the 15x15 engine
+namespace {
+int frame_train_check(const apz_engine* e, int side, const char* who) {
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, std::string(who) + ": the 15x15 engine only");
+    if (!(apz::Frame15::framed_side(side) || side == 15))
+        return fail(APZ_E_UNSUPPORTED, std::string(who) + ": side must be 6, 7, 9, 11, 12, 13, 14 or 15");
+    return APZ_OK;
+}
+}  // namespace
+
+int apz_bn_fwd_frame(apz_engine* e, const void* x_dev, const void* resid_dev, const void* gamma_dev, const void* beta_dev,
+                     void* run_mean_dev, void* run_var_dev, void* y_dev, void* mean_dev, void* invstd_dev, void* mask_dev, int n,
+                     int C, int layout, int relu, float momentum, float eps, int side, void* stream) {
+    if (!e || !x_dev || !beta_dev || !y_dev || !mean_dev || !invstd_dev || n < 1 || C < 1 || C > 256)
+        return fail(APZ_E_ARG, "bad argument");
+    if (layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_fwd_frame: padded-row layout only");
+    if (int rc = frame_train_check(e, side, "bn_fwd_frame")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int splits = bn_splits(e, n, C, layout);
+        const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev,
+                               (double)n * side * side, eps, momentum};
+        hipLaunchKernelGGL(apz::bn_stats_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C, side);
+        hipLaunchKernelGGL(apz::bn_apply_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
+                           (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, part, splits, fin,
+                           (float*)y_dev, (unsigned char*)mask_dev, n, C, relu, side);
+        return APZ_OK;
+    });
+}
+
+int apz_bn_bwd_frame(apz_engine* e, const void* dy_dev, const void* x_dev, const void* out_dev, const void* mask_dev,
+                     const void* gamma_dev, const void* mean_dev, const void* invstd_dev, void* dx_dev, void* dres_dev,
+                     void* dgamma_dev, void* dbeta_dev, void* dxsum_dev, int dxsum_ld, void* dxmax_dev, int n, int C, int layout,
+                     int relu, int side, void* stream) {
+    if (!e || !dy_dev || !x_dev || !mean_dev || !invstd_dev || !dx_dev || n < 1 || C < 1 || C > 256 ||
+        (relu && !out_dev && !mask_dev) || (dxsum_dev && dxsum_ld < C))
+        return fail(APZ_E_ARG, "bad argument");
+    if (layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_frame: padded-row layout only");
+    if (int rc = frame_train_check(e, side, "bn_bwd_frame")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int splits = bn_splits(e, n, C, layout);
+        hipLaunchKernelGGL(apz::bn_bwd_reduce_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                           (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev, part,
+                           (const unsigned char*)mask_dev, n, C, relu, side);
+        hipLaunchKernelGGL(apz::bn_bwd_apply_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                           (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
+                           (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev, (float*)dgamma_dev,
+                           (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C, relu,
+                           (double)n * side * side, (float*)dxmax_dev, side);
+        return APZ_OK;
+    });
+}
+
 int apz_colsum(apz_engine* e, const void* in_dev, void* out_dev, int rows, int cols, float scale, void* stream) {
     if (!e || !in_dev || !out_dev || rows < 1 || cols < 1) return fail(APZ_E_ARG, "bad argument");
     return train_call(e, stream, [&]() -> int {
@@ -2302,6 +2359,45 @@ int apz_conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const
     });
 }
 
+// ... on the S x S window of a padded-row trunk tensor (framed boards): the same two kernels with H = W = side on planes of
+// 240 floats in rows of 16.  Forward: y dense [n][CO][side][side].  Backward: dx rows 0 .. side - 1 are written (columns
+// side .. 15 zero), rows side .. 14 are NOT -- apz_bn_bwd_frame, the consumer, selects them away.
+int apz_conv1x1_fwd_frame(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C,
+                          int CO, int side, void* stream) {
+    if (!e || !x_dev || !w_dev || !y_dev || n < 1 || C < 1 || C > 1024 || CO < 1 || CO > 8) return fail(APZ_E_ARG, "bad argument");
+    if (int rc = frame_train_check(e, side, "conv1x1_fwd_frame")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
+        if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
+        hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (side * side + 63) / 64), dim3(256), lds, e->stream,
+                           (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, side, side,
+                           apz::Frame15::GPLANE, apz::Frame15::GROW);
+        return APZ_OK;
+    });
+}
+
+int apz_conv1x1_bwd2_frame(apz_engine* e, const void* x_dev, const void* w1_dev, const void* dy1_dev, int CO1, const void* w2_dev,
+                           const void* dy2_dev, int CO2, void* dx_dev, void* dw_dev, int n, int C, int side, int accumulate_dx,
+                           void* stream) {
+    if (!e || !x_dev || !w1_dev || !dy1_dev || !dw_dev || n < 1 || C < 1 || C > 1024 || CO1 < 1 || CO2 < 0 || CO1 + CO2 > 8 ||
+        (CO2 > 0 && (!w2_dev || !dy2_dev)))
+        return fail(APZ_E_ARG, "bad argument");
+    if (int rc = frame_train_check(e, side, "conv1x1_bwd2_frame")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        const int P = side * side, CO = CO1 + CO2;
+        if (int rc = e->head_scratch.reserve((size_t)n * CO * C * sizeof(float))) return rc;
+        float* part = e->head_scratch.as<float>();      // dw per board
+        const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
+        if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
+        hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
+                           (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
+                           part, C, CO1, CO2, side, side, apz::Frame15::GPLANE, apz::Frame15::GROW, accumulate_dx);
+        hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)part,
+                           (float*)dw_dev, n, CO * C, 1.0f);
+        return APZ_OK;
+    });
+}
+
 int apz_bias_grad(apz_engine* e, const void* dy_dev, void* db_dev, int n, int C, int layout, void* stream) {
     if (!e || !dy_dev || !db_dev || n < 1 || C < 1) return fail(APZ_E_ARG, "bad argument");
     int ps, rs;
@@ -2390,6 +2486,18 @@ int apz_layout_convert(apz_engine* e, const void* src_dev, void* dst_dev, int64_
         const int grid = (int)std::min<int64_t>((planes * 240 + 255) / 256, 16384);
         const auto kern = to_rows16 ? apz::rows16_from_dense_kernel : apz::rows16_to_dense_kernel;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, (const float*)src_dev, (float*)dst_dev, (long)planes);
+        return APZ_OK;
+    });
+}
+
+// dense [planes][side][side] -> dense [planes][15][15], off-board cells zero (frame_planes_kernel of the framed evaluator)
+int apz_frame_planes_dev(apz_engine* e, const void* src_dev, void* dst_dev, int64_t planes, int side, void* stream) {
+    if (!e || !src_dev || !dst_dev || planes < 1) return fail(APZ_E_ARG, "bad argument");
+    if (int rc = frame_train_check(e, side, "frame_planes_dev")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        const long total = (long)planes * apz::Frame15::CELLS;
+        hipLaunchKernelGGL(apz::frame_planes_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 8)), dim3(256), 0,
+                           e->stream, (const float*)src_dev, (float*)dst_dev, (long)planes, side);
         return APZ_OK;
     });
 }

@@ -276,12 +276,22 @@ def add_(y, x):
 
 
 # ---- BatchNorm ------------------------------------------------------------------------------------------------------
+def _frame_side(side, layout, stats=None):
+    """The `side` argument of the framed BatchNorm operators, checked before the library sees it"""
+    side = int(side)
+    if layout != ROWS16 or stats is not None:
+        raise ValueError("side: padded-row tensors only, and no statistics from a convolution's epilogue (they cover all 225 cells)")
+    return side
+
+
 def bn_fwd(x, gamma, beta, run_mean, run_var, resid=None, relu=True, layout=DENSE, momentum=0.1, eps=1e-3, stats=None,
-           want_mask=False):
+           want_mask=False, side=None):
     """y = act(batch_norm(x) (+ resid)) with batch statistics; gamma None = fixed at 1 (the reference's fix_gamma layers).
     run_mean / run_var are updated in place (momentum = weight of the new batch value).  -> (y, mean, invstd)
     stats: conv3x3_fwd_stats' second result for this x.  want_mask (padded rows): -> (y, mean, invstd, mask), mask = the
-    ReLU decisions as uint8 [n][C][60] (4 bits per byte), for bn_bwd(mask=...)."""
+    ReLU decisions as uint8 [n][C][60] (4 bits per byte), for bn_bwd(mask=...).
+    side (padded rows; None: the 15x15 board): the framed board's side S (csrc/bn_frame.h) -- statistics over the S x S
+    window only (count n S S), whatever the off-board cells of x and resid hold; off-board y exactly +0, mask bits 0."""
     L, hnd, stream = _ctx(x, _board(x, layout))
     n, c = int(x.shape[0]), int(x.shape[1])
     y = _empty(tuple(x.shape), x)
@@ -289,19 +299,27 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, resid=None, relu=True, layout=DENS
     if stats is not None and (tuple(stats.shape) != (c, n, 2) or stats.dtype != _torch().float64 or not stats.is_contiguous()):
         raise ValueError("stats: contiguous float64 [C][n][2]")
     mask = _torch().empty((n, c, 60), dtype=_torch().uint8, device=x.device) if want_mask else None
+    if side is not None:
+        _ck(L, L.apz_bn_fwd_frame(hnd, x.data_ptr(), _ptr(resid), _ptr(gamma), beta.data_ptr(), _ptr(run_mean), _ptr(run_var),
+                                  y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(mask), n, c, layout, int(relu), momentum,
+                                  eps, _frame_side(side, layout, stats), stream))
+        return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
     _ck(L, L.apz_bn_fwd_stats(hnd, x.data_ptr(), _ptr(resid), _ptr(gamma), beta.data_ptr(), _ptr(run_mean), _ptr(run_var),
                               y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(stats), _ptr(mask), n, c, layout, int(relu),
                               momentum, eps, stream))
     return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
 
 
-def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DENSE, dxsum=None, mask=None, dxmax=None):
+def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DENSE, dxsum=None, mask=None, dxmax=None,
+           side=None):
     """-> (dx, dres or None, dgamma, dbeta); y is the forward output (the ReLU mask) -- or None when mask (bn_fwd's
     want_mask result) carries the ReLU decisions.
     dxsum: a [bn_bwd_splits(x, layout)][C] view (row stride >= C) of a float32 matrix that receives the per-split column
     sums of dx -- colsum() of it is the bias gradient of the convolution in front (bias_parts() hands such views out).
     dxmax (padded rows): a contiguous float32 [bn_bwd_splits(x, layout)][C] tensor that receives max |dx| per split and
-    channel (conv3x3_dgrad_f16x2's dymax)."""
+    channel (conv3x3_dgrad_f16x2's dymax).
+    side (padded rows; None: the 15x15 board): the framed board's side, as in bn_fwd -- off-board dy and x may hold
+    anything; off-board dx and dres are exactly +0."""
     L, hnd, stream = _ctx(x, _board(x, layout))
     n, c = int(x.shape[0]), int(x.shape[1])
     dx = _empty(tuple(x.shape), x)
@@ -317,14 +335,21 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
     if dxmax is not None and (tuple(dxmax.shape) != (bn_bwd_splits(x, layout), c) or not dxmax.is_contiguous() or
                               dxmax.dtype != _torch().float32):
         raise ValueError("dxmax: a contiguous float32 [splits][C] tensor")
+    if side is not None:
+        _ck(L, L.apz_bn_bwd_frame(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(),
+                                  invstd.data_ptr(), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld,
+                                  _ptr(dxmax), n, c, layout, int(relu), _frame_side(side, layout), stream))
+        return dx, dres, dgamma, dbeta
     _ck(L, L.apz_bn_bwd_max(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
                             dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, _ptr(dxmax), n, c,
                             layout, int(relu), stream))
     return dx, dres, dgamma, dbeta
 
 
-def bn_bwd_splits(x, layout=DENSE):
-    """rows of bn_bwd's dxsum matrix for tensors of x's shape"""
+def bn_bwd_splits(x, layout=DENSE, side=None):
+    """rows of bn_bwd's dxsum matrix for tensors of x's shape (side: as in bn_bwd -- the framed kernels keep the grid)"""
+    if side is not None:
+        _frame_side(side, layout)
     L, hnd, _ = _ctx(x, _board(x, layout))
     s = L.apz_bn_bwd_splits(hnd, int(x.shape[0]), int(x.shape[1]), layout)
     _ck(L, s)
@@ -343,10 +368,16 @@ def colsum(m, scale=1.0):
 
 
 # ---- heads ----------------------------------------------------------------------------------------------------------
-def conv1x1_fwd(x, weight, bias=None, layout=DENSE):
-    """y [n][CO][H][W] (dense) = W x + b, CO <= 8."""
+def conv1x1_fwd(x, weight, bias=None, layout=DENSE, side=None):
+    """y [n][CO][H][W] (dense) = W x + b, CO <= 8.  side (padded rows): the framed board's side S -- y [n][CO][S][S] from
+    the S x S window of x, whatever its off-board cells hold."""
     L, hnd, stream = _ctx(x, _board(x, layout))
     n, c, co = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0])
+    if side is not None:
+        side = _frame_side(side, layout)
+        y = _empty((n, co, side, side), x)
+        _ck(L, L.apz_conv1x1_fwd_frame(hnd, x.data_ptr(), weight.data_ptr(), _ptr(bias), y.data_ptr(), n, c, co, side, stream))
+        return y
     h, w = int(x.shape[2]), (15 if layout == ROWS16 else int(x.shape[3]))
     y = _empty((n, co, h, w), x)
     _ck(L, L.apz_conv1x1_fwd(hnd, x.data_ptr(), weight.data_ptr(), _ptr(bias), y.data_ptr(), n, c, co, layout, stream))
@@ -366,15 +397,23 @@ def conv1x1_bwd(x, weight, dy, layout=DENSE, dx=None):
     return dx, dw, db
 
 
-def conv1x1_bwd_pair(x, w1, dy1, w2, dy2, layout=DENSE):
+def conv1x1_bwd_pair(x, w1, dy1, w2, dy2, layout=DENSE, side=None):
     """Two 1x1 convolutions of the same input (the two heads): -> (dx, dw1, db1, dw2, db2), dx = both heads' input
-    gradients added, in one pass over x."""
+    gradients added, in one pass over x.  side (padded rows): the framed board's side S, dy1 / dy2 dense [n][CO][S][S];
+    rows S .. 14 of dx are NOT written (bn_bwd(side=S), which reads dx next, masks them)."""
     L, hnd, stream = _ctx(x, _board(x, layout))
     n, c, co1, co2 = int(x.shape[0]), int(x.shape[1]), int(w1.shape[0]), int(w2.shape[0])
     dx = _empty(tuple(x.shape), x)
     dw = _empty((co1 + co2, c), x)
-    _ck(L, L.apz_conv1x1_bwd2(hnd, x.data_ptr(), w1.data_ptr(), dy1.data_ptr(), co1, w2.data_ptr(), dy2.data_ptr(), co2,
-                               dx.data_ptr(), dw.data_ptr(), n, c, layout, 0, stream))
+    if side is not None:
+        side = _frame_side(side, layout)
+        for dy, co in ((dy1, co1), (dy2, co2)):
+            _check(dy, "conv1x1_bwd_pair: dy dense [n][CO][side][side]", None, (n, co, side, side))
+        _ck(L, L.apz_conv1x1_bwd2_frame(hnd, x.data_ptr(), w1.data_ptr(), dy1.data_ptr(), co1, w2.data_ptr(), dy2.data_ptr(), co2,
+                                        dx.data_ptr(), dw.data_ptr(), n, c, side, 0, stream))
+    else:
+        _ck(L, L.apz_conv1x1_bwd2(hnd, x.data_ptr(), w1.data_ptr(), dy1.data_ptr(), co1, w2.data_ptr(), dy2.data_ptr(), co2,
+                                   dx.data_ptr(), dw.data_ptr(), n, c, layout, 0, stream))
     return dx, dw[:co1].view(w1.shape), bias_grad(dy1, DENSE), dw[co1:].view(w2.shape), bias_grad(dy2, DENSE)
 
 
@@ -431,6 +470,17 @@ def to_rows16(x):
     L, hnd, stream = _ctx(x, _board(x, DENSE))
     y = _empty((int(x.shape[0]), int(x.shape[1]), 15, 16), x)
     _ck(L, L.apz_layout_convert(hnd, x.data_ptr(), y.data_ptr(), int(x.shape[0]) * int(x.shape[1]), 1, stream))
+    return y
+
+
+def frame_planes(x):
+    """dense [n][C][S][S] (S = 6, 7, 9, 11 .. 14) -> dense [n][C][15][15]: the board in the top-left window of the 15x15
+    frame, every off-board cell zero (csrc/frame15.h)"""
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError("frame_planes takes [n][C][S][S]")
+    L, hnd, stream = _ctx(x, (15, 15))
+    y = _empty((int(x.shape[0]), int(x.shape[1]), 15, 15), x)
+    _ck(L, L.apz_frame_planes_dev(hnd, x.data_ptr(), y.data_ptr(), int(x.shape[0]) * int(x.shape[1]), int(x.shape[2]), stream))
     return y
 
 

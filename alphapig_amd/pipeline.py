@@ -158,7 +158,8 @@ class TrainPipeline(object):
         monitor, checkpoints and the arena; default: a second HIP PolicyValueNet, or `policy_value_net` itself when one
         was passed in.  distributed: None = on iff alphapig_amd.dist holds a process group.
         resume: the directory of a checkpoint (save_checkpoint; conf key checkpoint_every) written by a pipeline of the same
-        board, net, batch_size, buffer_size, replay, concurrent_games and world size: run() goes on where that one stood."""
+        board, net, batch_size, buffer_size, replay, train_framed, concurrent_games and world size: run() goes on where that
+        one stood."""
         self.async_update = bool(conf.get("async_update", True))
         self.round_seconds = float(conf.get("round_seconds", 0.5))
         self.round_steps = conf.get("round_steps")
@@ -205,6 +206,20 @@ class TrainPipeline(object):
         self.replay = conf.get("replay", "tuples")
         if self.replay not in ("tuples", "compact", "device"):
             raise ValueError("replay must be 'tuples', 'compact' or 'device', not %r" % (self.replay,))
+        # train_framed (default False): HipTrainer's `framed` -- the training step on the framed boards (6x6, 7x7, 9x9,
+        # 11x11 .. 14x14: the 15x15 trunk kernels, the board mask in the BatchNorm passes).  On such a board it goes with the
+        # tuple buffer and the f32 trainer only; 15x15 and 8x8 train as they always did, whatever the key says.
+        self.train_framed = bool(conf.get("train_framed", False))
+        if self.train_framed:
+            from .train import FRAMED_SIDES
+            bw, bh = int(conf["board_width"]), int(conf["board_height"])
+            if bw == bh and bw in FRAMED_SIDES:
+                if self.replay != "tuples":
+                    raise ValueError("train_framed on a %dx%d board takes replay='tuples', not %r: the code replay buffers' "
+                                     "framed form does not exist" % (bw, bh, self.replay))
+                if self.train_arith != "f32":
+                    raise ValueError("train_framed on a %dx%d board takes train_arith='f32', not %r: the f16x2 trunk's "
+                                     "statistics epilogue and scales see off-board cells" % (bw, bh, self.train_arith))
         if self.replay == "device":
             import torch
             if not torch.cuda.is_available():
@@ -226,6 +241,7 @@ class TrainPipeline(object):
         self._conf_match = {k: conf.get(k) for k in ("board_width", "board_height", "n_in_row", "n_blocks", "n_filter",
                                                      "batch_size", "buffer_size", "concurrent_games")}
         self._conf_match["replay"] = self.replay
+        self._conf_match["train_framed"] = self.train_framed
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -367,7 +383,7 @@ class TrainPipeline(object):
             # a re-created trainer (set_params dropped the old one) continues the dropout mask sequence instead of replaying it
             net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                       device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
-                                      trunk_arith=self.train_arith)
+                                      trunk_arith=self.train_arith, framed=self.train_framed)
         return net._trainer
 
     def _note_overflows(self, rec, trainer):
@@ -593,9 +609,10 @@ class TrainPipeline(object):
     def _resume(self, path):
         state = checkpoint.read_state(path)
         for k, mine in self._conf_match.items():
-            if state["conf"].get(k) != mine:
+            theirs = state["conf"].get(k, False if k == "train_framed" else None)   # (a checkpoint from before the key: off)
+            if theirs != mine:
                 raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
-                                 (path, k, state["conf"].get(k), k, mine))
+                                 (path, k, theirs, k, mine))
         if bool(state["async_update"]) != self.async_update:
             raise ValueError("the checkpoint %s was written with async_update=%r" % (path, state["async_update"]))
         # (a checkpoint from before the leaf symmetries, or of a run without them, has no such keys: "none")
@@ -728,7 +745,8 @@ class TrainPipeline(object):
             with ctx:
                 if trainer is None:
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
-                                         device_index=net._device, seed=self._seed, trunk_arith=self.train_arith)
+                                         device_index=net._device, seed=self._seed, trunk_arith=self.train_arith,
+                                         framed=self.train_framed)
                 self._async_trainer = trainer
                 tstate = getattr(self, "_async_trainer_state", None)
                 if tstate is not None:                  # resume=: the trainer this thread built continues the saved one

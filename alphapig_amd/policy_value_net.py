@@ -61,7 +61,7 @@ def act_exponent_for(m, k_min=None, k_max=None):
 class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
-                 uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0):
+                 uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0, train_framed=False):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -72,7 +72,8 @@ class PolicyValueNet(object):
           "bf16x3" three bf16 terms, six products (csrc/trunk15_wino3b.h): round 4's form, kept for comparison;
           "auto"   (default) "f16x2" where such kernels exist (15x15 / 128-filter residual net; 8x8 boards), else "f32".
         Square boards of 6x6 .. 14x14 other than 8x8 and 10x10 (128-filter residual net only) run framed on the 15x15 kernels and
-        follow the 15x15 rules throughout; HipTrainer / train_step do not support them.
+        follow the 15x15 rules throughout; train_step runs on them with train_framed=True only (HipTrainer(framed=True): the
+        15x15 trunk kernels with the board mask in the BatchNorm passes) and raises ValueError otherwise.
         8x8 boards (round 6): "f16x2" runs every convolution with a multiple of 64 input channels on the fp16 matrix pipe with
         split operands (csrc/conv8_split.h), for EVERY batch size: a board's bits do not depend on the batch there.
         uniform_trunk (default False): with "f16x2" on the 15x15 / 128-filter net, batches of <= 32 boards run the small-batch
@@ -96,6 +97,7 @@ class PolicyValueNet(object):
         self.channelnum = int(c_in)
         self._n_blocks, self._n_filter = int(n_blocks), int(n_filter)
         self.net_kind = net_kind
+        self.train_framed = bool(train_framed)
         self._device = int(device)
         self.hw = self.board_width * self.board_height
         self.code_stride = (self.hw + 1 + 15) // 16 * 16
@@ -428,7 +430,7 @@ class PolicyValueNet(object):
         from .train import HipTrainer
         if getattr(self, "_trainer", None) is None:
             self._trainer = HipTrainer(self.params(), self.net_kind, self._n_blocks, batch_size=self.batchsize,
-                                       device_index=self._device)
+                                       device_index=self._device, framed=self.train_framed)
         loss, entropy = self._trainer.train_step(state_batch, mcts_probs, winner_batch, learning_rate)
         self._trainer.sync_evaluator(self)
         return np.array([loss], dtype=np.float32), np.array([entropy], dtype=np.float32)

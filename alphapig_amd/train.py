@@ -40,23 +40,44 @@ Block = collections.namedtuple("Block", "x ya ha ma ia yb out mb ib ka kb")
 
 
 TRAINABLE_SIDES = (15, 8)
+FRAMED_SIDES = (6, 7, 9, 11, 12, 13, 14)      # Frame15::framed_side (csrc/frame15.h)
 
 
-def check_trainable_board(params):
+def check_trainable_board(params, framed=False, net_kind="resnet", trunk_arith="f32"):
     """ValueError unless the policy head of `params` (fc_3_1_1_bias: one output per cell) belongs to a board the training
-    kernels exist for: 15x15 or 8x8.  The evaluator also runs the other square boards from 6x6 to 14x14 except 10x10 ("framed" on the 15x15
-    trunk kernels, csrc/frame15.h); the training step does not -- the padded-row training kernels take their BatchNorm
-    statistics over all 225 cells of the frame ("Boards smaller than 15x15").  Needs no GPU."""
+    step runs on.  15x15 and 8x8 have training kernels of their own and pass whatever `framed` says.  The other square
+    boards from 6x6 to 14x14 except 10x10 -- the evaluator's "framed" boards, the S x S window of the 15x15 trunk kernels'
+    frame (csrc/frame15.h) -- pass with framed=True only: the step then runs the 15x15 trunk kernels with the board mask
+    in its BatchNorm passes (csrc/bn_frame.h; DESIGN.md, "Boards smaller than 15x15"), for the residual net of 128
+    filters (net_kind, and the shape of res_conv1_weight / convA1_weight when `params` holds them) in trunk_arith "f32":
+    the f16x2 trunk's statistics epilogue and device-chosen scales see off-board cells.  Without the switch the plain
+    padded-row kernels would take their BatchNorm statistics over all 225 cells of the frame, so the call is refused.
+    Needs no GPU."""
     hw = int(np.asarray(params["fc_3_1_1_bias"]).shape[0])
     side = int(round(hw ** 0.5))
-    if side * side == hw and side not in TRAINABLE_SIDES:
+    if side * side != hw or side in TRAINABLE_SIDES:
+        return
+    if not framed:
         raise ValueError("HipTrainer supports 15x15 and 8x8 boards, not %dx%d: the evaluator runs the other 6x6 .. 14x14 boards (not 10x10) framed "
-                         "on the 15x15 kernels, the training step on them does not exist" % (side, side))
+                         "on the 15x15 kernels, the training step on them does not exist without framed=True (SxS: 6, 7, 9, "
+                         "11 .. 14, residual net of 128 filters)" % (side, side))
+    if side not in FRAMED_SIDES:
+        raise ValueError("framed training runs boards of side %s (and 15x15 and 8x8 on their own kernels), not %dx%d" %
+                         (", ".join(str(s) for s in FRAMED_SIDES), side, side))
+    if net_kind != "resnet":
+        raise ValueError("framed training runs the residual net only, not net_kind %r on a %dx%d board" % (net_kind, side, side))
+    for k in ("res_conv1_weight", "convA1_weight"):
+        if k in params and int(np.shape(params[k])[0]) != 128:
+            raise ValueError("framed training runs the residual net of 128 filters, not %d (%dx%d board)" %
+                             (int(np.shape(params[k])[0]), side, side))
+    if trunk_arith != "f32":
+        raise ValueError("framed training has no trunk_arith=%r form: the f16x2 trunk's statistics epilogue and its "
+                         "device-chosen scales see off-board cells (%dx%d board)" % (trunk_arith, side, side))
 
 
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
-                 seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32"):
+                 seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False):
         """params: name -> array, in any order.  height / width: the board (default: square, from the policy head's size).
         seed / dropout_step0: the dropout masks are a stateless hash of (seed, dropout_step0 + step, element) -- a trainer
         that is re-created (set_params, a resumed checkpoint) or one of several ranks passes its own seed / the steps
@@ -68,11 +89,15 @@ class HipTrainer(object):
         launch leaves the fp16 range is taken again on the exact kernels (trunk_overflows counts them) and ends
         bit-identical to the "f32" trainer's step.  Only the 15x15, 128-filter residual trunk has the f16x2 form:
         other nets raise ValueError.  (profiles/r07_train_f16x2.md: 0.86 of the "f32" step time at batch 512, but
-        only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)"""
+        only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)
+        framed: opt in to the training step on the framed boards (6x6, 7x7, 9x9, 11x11 .. 14x14; check_trainable_board):
+        the residual net of 128 filters on the 15x15 trunk kernels, the board mask in the BatchNorm passes.  Without it
+        those boards raise ValueError as they always did; 15x15 and 8x8 train as they always did whatever it says."""
         if trunk_arith not in ("f32", "f16x2"):
             raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
         if "fc_3_1_1_bias" in params:
-            check_trainable_board(params)          # before anything touches the GPU: today's failure would come from the first step
+            # before anything touches the GPU: today's failure would come from the first step
+            check_trainable_board(params, framed, net_kind, trunk_arith)
         import torch
         from . import _native, hipconv
         if not torch.cuda.is_available():
@@ -112,7 +137,13 @@ class HipTrainer(object):
         self.t = 0
         self.grad = {}
         # the self-play kernels' padded-row layout for the trunk when the net has their shape
-        self.rows16 = (net_kind == "resnet" and n_blocks > 0 and self.side == 15 and
+        # framed boards (check_trainable_board has seen the net): the board's side, the `side` of every trunk-side operator;
+        # None on 15x15 and 8x8, where nothing changes
+        self.framed = bool(framed)
+        self.frame_side = self.side if (self.framed and self.side in FRAMED_SIDES) else None
+        if self.frame_side and (n_blocks < 1 or tuple(self.p["convA1_weight"].shape) != (128, 128, 3, 3)):
+            raise ValueError("framed training needs the residual trunk of 128 filters (at least one block)")
+        self.rows16 = (net_kind == "resnet" and n_blocks > 0 and (self.side == 15 or self.frame_side is not None) and
                        tuple(self.p["convA1_weight"].shape) == (128, 128, 3, 3))
         # ... whose 2 n_blocks weight tensors then live back to back in one buffer (self.p holds views): one launch packs
         # all of them for the Winograd kernel in both orientations at the start of a step (hipconv.wino_pack_many)
@@ -182,6 +213,34 @@ class HipTrainer(object):
         g[name + "_bias"] = o.bias_grad(dy, layout)
         return o.conv3x3_dgrad(dy, w, layout) if need_dx else None
 
+    def _stem_fwd_framed(self, states):
+        """The stem on a framed board: the planes into the 15x15 frame, the dense 15x15 convolution, and the BatchNorm
+        BEHIND to_rows16 (the convolution leaves bias-and-neighbour values off the board; the framed BatchNorm is the mask)
+        -> (a, ConvAct): x = the framed planes, y / a padded rows"""
+        o, p, S = self.ops, self.p, self.frame_side
+        xf = o.frame_planes(states)
+        y = o.to_rows16(o.conv3x3_fwd(xf, p["res_conv1_weight"], p["res_conv1_bias"], o.DENSE))
+        a, mean, invstd = o.bn_fwd(y, None, p["res_conv1_beta"], p["res_conv1_mean"], p["res_conv1_var"], None, True, o.ROWS16,
+                                   1.0 - BN_MOMENTUM, BN_EPS, side=S)
+        return a, ConvAct("res_conv1", xf, y, a, mean, invstd, o.ROWS16)
+
+    def _stem_bwd_framed(self, da, rec):
+        o, g = self.ops, self.grad
+        dy, _, _, g["res_conv1_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, o.ROWS16,
+                                                 side=self.frame_side)
+        dy = o.from_rows16(dy)              # off-board cells zero: the dense 15x15 gradients below are the S x S board's
+        g["res_conv1_weight"] = o.conv3x3_wgrad(rec.x, dy, o.DENSE)
+        g["res_conv1_bias"] = o.bias_grad(dy, o.DENSE)
+
+    def _head_fwd_framed(self, x, name):
+        """conv_act of a head on a framed board: the 1x1 convolution reads the S x S window of the padded-row trunk output,
+        everything behind it is dense S x S"""
+        o, p = self.ops, self.p
+        y = o.conv1x1_fwd(x, p[name + "_weight"], p[name + "_bias"], o.ROWS16, side=self.frame_side)
+        a, mean, invstd = o.bn_fwd(y, None, p[name + "_beta"], p[name + "_mean"], p[name + "_var"], None, True, o.DENSE,
+                                   1.0 - BN_MOMENTUM, BN_EPS)
+        return a, ConvAct(name, x, y, a, mean, invstd, o.ROWS16)
+
     def _trunk_conv(self, j):
         """Trunk convolution j = 2 i - 2 (A of block i) or 2 i - 1 (B): its parameter prefix"""
         return "conv%s%d" % ("AB"[j % 2], j // 2 + 1)
@@ -196,7 +255,7 @@ class HipTrainer(object):
         w, b = self.p[self._trunk_conv(j) + "_weight"], self.p[self._trunk_conv(j) + "_bias"]
         if not self.rows16:
             return o.conv3x3_fwd(x, w, b, o.DENSE), None
-        if int(x.shape[0]) <= 16384:
+        if self.frame_side is None and int(x.shape[0]) <= 16384:      # (the epilogue's sums cover all 225 cells)
             return o.conv3x3_fwd_stats(x, w, b, upk=self._upk[j, 0])
         return o.conv3x3_fwd(x, w, b, o.ROWS16, upk=self._upk[j, 0]), None
 
@@ -215,11 +274,16 @@ class HipTrainer(object):
         o, p = self.ops, self.p
         tape = {"blocks": [], "stack": []}
         if self.kind == "resnet":
-            x, rec = self._conv_act_fwd(states, "res_conv1", o.DENSE)
+            S = self.frame_side
+            if S:
+                x, rec = self._stem_fwd_framed(states)
+            else:
+                x, rec = self._conv_act_fwd(states, "res_conv1", o.DENSE)
             tape["stem"] = rec
             lay = o.ROWS16 if self.rows16 else o.DENSE
             if self.rows16:             # every trunk layer's weights packed for this pass's kernel, both orientations, one launch
-                x = o.to_rows16(x)
+                if not S:
+                    x = o.to_rows16(x)
                 if self._fast:          # (the pack launch zeroes the step's overflow word)
                     self._u16 = o.wino3h_pack_many(self._trunk_w, self._trunk_b, self._u16, self._flag)
                 else:
@@ -229,10 +293,10 @@ class HipTrainer(object):
                 A, B = "bnA%d" % i, "bnB%d" % i
                 ya, sa = self._trunk_conv_fwd(x, 2 * i - 2)
                 ha, ma, ia, *ka = o.bn_fwd(ya, p[A + "_gamma"], p[A + "_beta"], p[A + "_moving_mean"], p[A + "_moving_var"], None,
-                                           True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sa, want_mask=wm)
+                                           True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sa, want_mask=wm, side=S)
                 yb, sb = self._trunk_conv_fwd(ha, 2 * i - 1)
                 out, mb, ib, *kb = o.bn_fwd(yb, p[B + "_gamma"], p[B + "_beta"], p[B + "_moving_mean"], p[B + "_moving_var"], x,
-                                            True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sb, want_mask=wm)
+                                            True, lay, 1.0 - BN_MOMENTUM, BN_EPS, stats=sb, want_mask=wm, side=S)
                 tape["blocks"].append(Block(x, ya, ha, ma, ia, yb, out, mb, ib, ka[0] if ka else None, kb[0] if kb else None))
                 x = out
         else:
@@ -243,8 +307,12 @@ class HipTrainer(object):
                 tape["stack"].append(rec)
         tape["layout"] = lay
         n = int(x.shape[0])
-        pol, tape["pol"] = self._conv_act_fwd(x, "conv3_1_1", lay)
-        val, tape["val"] = self._conv_act_fwd(x, "conv3_2_1", lay)
+        if self.frame_side:
+            pol, tape["pol"] = self._head_fwd_framed(x, "conv3_1_1")
+            val, tape["val"] = self._head_fwd_framed(x, "conv3_2_1")
+        else:
+            pol, tape["pol"] = self._conv_act_fwd(x, "conv3_1_1", lay)
+            val, tape["val"] = self._conv_act_fwd(x, "conv3_2_1", lay)
         pol, val = pol.view(n, -1), val.view(n, -1)
         if self.dropout > 0:
             keep = 1.0 - self.dropout
@@ -272,11 +340,11 @@ class HipTrainer(object):
             dy, _, _, g[rec.name + "_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, o.DENSE)
             dys.append(dy)
         dx, g["conv3_1_1_weight"], g["conv3_1_1_bias"], g["conv3_2_1_weight"], g["conv3_2_1_bias"] = o.conv1x1_bwd_pair(
-            tape["pol"].x, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"].layout)
+            tape["pol"].x, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"].layout, side=self.frame_side)
         if self.kind == "resnet":
             # the trunk convolutions' bias gradients = column sums of the dx their BatchNorms hand back: every bn_bwd
             # leaves its per-split sums in its own columns of ONE matrix, added after the loop in one launch
-            nb = self.n_blocks
+            nb, S = self.n_blocks, self.frame_side
             nf = int(tape["blocks"][0].ya.shape[1]) if nb else 0
             parts = o._empty((o.bn_bwd_splits(tape["blocks"][0].ya, lay), 2 * nb * nf), dx) if nb else None
             # f16x2: each bn_bwd also leaves max |dx| per split and channel, which the data-gradient launch right behind it
@@ -288,21 +356,24 @@ class HipTrainer(object):
                 ca, cb = (2 * i - 2) * nf, (2 * i - 1) * nf
                 dyb, dskip, g["bn" + B + "_gamma"], g["bn" + B + "_beta"] = o.bn_bwd(
                     dx, blk.yb, blk.out, p["bn" + B + "_gamma"], blk.mb, blk.ib, True, True, lay, dxsum=parts[:, cb:cb + nf],
-                    mask=blk.kb, dxmax=dmax)
+                    mask=blk.kb, dxmax=dmax, side=S)
                 g["conv" + B + "_weight"] = o.conv3x3_wgrad(blk.ha, dyb, lay)
                 dha = self._trunk_conv_dgrad(dyb, 2 * i - 1, None, dmax)
                 dya, _, g["bn" + A + "_gamma"], g["bn" + A + "_beta"] = o.bn_bwd(
                     dha, blk.ya, blk.ha, p["bn" + A + "_gamma"], blk.ma, blk.ia, True, False, lay, dxsum=parts[:, ca:ca + nf],
-                    mask=blk.ka, dxmax=dmax)
+                    mask=blk.ka, dxmax=dmax, side=S)
                 g["conv" + A + "_weight"] = o.conv3x3_wgrad(blk.x, dya, lay)
                 dx = self._trunk_conv_dgrad(dya, 2 * i - 2, dskip, dmax)       # trunk + skip gradients meet
             db = o.colsum(parts) if nb else None
             for i in range(1, nb + 1):
                 g["convA%d_bias" % i] = db[(2 * i - 2) * nf:(2 * i - 1) * nf]
                 g["convB%d_bias" % i] = db[(2 * i - 1) * nf:2 * i * nf]
-            if self.rows16:
-                dx = o.from_rows16(dx)
-            self._conv_act_bwd(dx, tape["stem"], False)
+            if S:
+                self._stem_bwd_framed(dx, tape["stem"])
+            else:
+                if self.rows16:
+                    dx = o.from_rows16(dx)
+                self._conv_act_bwd(dx, tape["stem"], False)
         else:
             for j in range(len(SIMPLE_CONVS) - 1, -1, -1):
                 dx = self._conv_act_bwd(dx, tape["stack"][j], j > 0)
@@ -370,11 +441,12 @@ class HipTrainer(object):
         """{layer: [n][C][H][W] bool} -- which activations of the kept forward pass were positive.  (A comparator that
         takes its ReLU decisions from here differs from this trainer by rounding only: an activation within rounding
         distance of zero otherwise lands on different sides in different arithmetic and moves whole gradient rows.)"""
-        cut = (lambda t: t[..., :15]) if self.rows16 else (lambda t: t)
+        S = self.frame_side
+        cut = (lambda t: t[..., :S, :S]) if S else (lambda t: t[..., :15]) if self.rows16 else (lambda t: t)
         tape, out = self.tape, {}
         recs = [tape["pol"], tape["val"]] + tape["stack"] + ([tape["stem"]] if "stem" in tape else [])
         for rec in recs:
-            out[rec.name] = rec.a > 0
+            out[rec.name] = (cut(rec.a) if (S and rec.name == "res_conv1") else rec.a) > 0
         for i, blk in enumerate(tape["blocks"], 1):
             out["bnA%d" % i] = cut(blk.ha) > 0
             out["block%d" % i] = cut(blk.out) > 0
@@ -444,7 +516,7 @@ class HipTrainer(object):
         statistic, "m/<name>" / "v/<name>": Adam's moments} -- what load_state takes."""
         out = {"meta": {"t": int(self.t), "dropout_step0": int(self.dropout_step0), "seed": int(self.seed),
                         "trunk_overflows": int(self.trunk_overflows), "net_kind": self.kind, "n_blocks": int(self.n_blocks),
-                        "trunk_arith": self.trunk_arith}}
+                        "trunk_arith": self.trunk_arith, "framed": self.framed}}
         for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
             for k, t in group.items():
                 out["%s/%s" % (tag, k)] = t.cpu().numpy()
@@ -458,6 +530,9 @@ class HipTrainer(object):
         meta = state["meta"]
         if meta["net_kind"] != self.kind or int(meta["n_blocks"]) != self.n_blocks:
             raise ValueError("this trainer state belongs to a %s net of %s blocks" % (meta["net_kind"], meta["n_blocks"]))
+        if bool(meta.get("framed", False)) != self.framed:
+            raise ValueError("this trainer state was written with framed=%s, the trainer was built with framed=%s" %
+                             (bool(meta.get("framed", False)), self.framed))
         todo = []
         for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
             for k, t in group.items():

@@ -68,7 +68,8 @@ int apz_device_count(void);
  * activation are zeroed after each layer, so the results are those of the S x S net.  Every interface below speaks S x S
  * (planes [n][c_in][S][S], codes of stride (S*S + 1 + 15) / 16 * 16, S*S probabilities); all inference entry points, the
  * arithmetics, apz_set_trunk_uniform, the activation exponents and the HIP-graph replay work as at 15x15.  The training
- * entry points (apz_conv3x3_fwd, apz_wino_*, apz_layout_convert, ...) stay 15x15 / 8x8 only.
+ * entry points (apz_conv3x3_fwd, apz_wino_*, apz_layout_convert, ...) stay 15x15 / 8x8 only; the training step of a
+ * framed board runs on a 15x15 engine through them and the apz_*_frame entry points below, which take the side explicitly.
  * APZ_E_UNSUPPORTED (NULL, message in apz_last_error): non-square boards, S < 6, S > 15, 10x10, and at a framed size the simple net
  * or 64 / 256 filters. */
 apz_engine *apz_create(const apz_config *cfg);
@@ -343,6 +344,39 @@ int apz_pv_loss(apz_engine *e, const void *logits_dev, const void *vlogit_dev, c
                 int n, void *loss3_dev, void *dlogits_dev, void *dvlogit_dev, void *probs_dev, void *values_dev,
                 void *stream);
 int apz_layout_convert(apz_engine *e, const void *src_dev, void *dst_dev, int64_t planes, int to_rows16, void *stream);
+
+/* ---- the training step on framed boards (csrc/bn_frame.h, csrc/frame15.h): a board of side S in 6 .. 14 (not 8, not 10)
+ * is the top-left S x S window of the 15x15 frame, and the trunk runs on the 15x15 kernels above (apz_wino_conv_add,
+ * apz_wgrad_wino), which compute exactly the S x S convolution and its gradients provided the off-board cells of every
+ * tensor they READ are zero.  They write whole planes, so the mask sits in the BatchNorm passes.  Every entry point here
+ * takes `side` explicitly and runs on a 15x15 engine (APZ_E_UNSUPPORTED on another, and for a side other than 6, 7, 9,
+ * 11, 12, 13, 14 or 15).  side = 15 returns the bits of the plain padded-row entry points.
+ *   apz_bn_fwd_frame         apz_bn_fwd_stats (padded-row layout only, statistics always by a pass of its own) over the
+ *                            on-board cells: count n * side * side (batch variance, and the unbiased factor of run_var);
+ *                            off-board cells of x and resid may hold anything, NaN and inf included (they are selected
+ *                            away, never multiplied); every off-board cell of y is exactly +0 and every off-board bit of
+ *                            mask_dev 0.
+ *   apz_bn_bwd_frame         apz_bn_bwd_max with the same mask: dy and xhat are selected before they are summed, count
+ *                            n * side * side, off-board dx and dres exactly +0, dxsum / dxmax from the masked values.
+ *   apz_frame_planes_dev     dense [planes][side][side] -> dense [planes][15][15], off-board cells zero.
+ *   apz_conv1x1_fwd_frame    apz_conv1x1_fwd on the window of a padded-row x: y dense [n][CO][side][side].
+ *   apz_conv1x1_bwd2_frame   apz_conv1x1_bwd2 with dy1 / dy2 dense [n][CO][side][side], x and dx padded rows: rows
+ *                            0 .. side - 1 of dx are written (columns side .. 15 zero), rows side .. 14 are left as they
+ *                            were -- apz_bn_bwd_frame, which reads dx next, masks them. */
+int apz_bn_fwd_frame(apz_engine *e, const void *x_dev, const void *resid_dev, const void *gamma_dev,
+                     const void *beta_dev, void *run_mean_dev, void *run_var_dev, void *y_dev, void *mean_dev,
+                     void *invstd_dev, void *mask_dev, int n, int C, int layout, int relu, float momentum, float eps,
+                     int side, void *stream);
+int apz_bn_bwd_frame(apz_engine *e, const void *dy_dev, const void *x_dev, const void *out_dev, const void *mask_dev,
+                     const void *gamma_dev, const void *mean_dev, const void *invstd_dev, void *dx_dev, void *dres_dev,
+                     void *dgamma_dev, void *dbeta_dev, void *dxsum_dev, int dxsum_ld, void *dxmax_dev, int n, int C,
+                     int layout, int relu, int side, void *stream);
+int apz_frame_planes_dev(apz_engine *e, const void *src_dev, void *dst_dev, int64_t planes, int side, void *stream);
+int apz_conv1x1_fwd_frame(apz_engine *e, const void *x_dev, const void *w_dev, const void *bias_dev, void *y_dev, int n,
+                          int C, int CO, int side, void *stream);
+int apz_conv1x1_bwd2_frame(apz_engine *e, const void *x_dev, const void *w1_dev, const void *dy1_dev, int CO1,
+                           const void *w2_dev, const void *dy2_dev, int CO2, void *dx_dev, void *dw_dev, int n, int C,
+                           int side, int accumulate_dx, void *stream);
 
 int apz_sync(apz_engine *e);
 void *apz_stream(apz_engine *e);

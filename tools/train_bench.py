@@ -2,7 +2,9 @@
 """Training-step timing on the GPU box: the product trainer (alphapig_amd/train.py, every operator a HIP kernel of
 this repository) beside the same graph in PyTorch (MIOpen convolutions; tests/torch_trainer.py, the comparator the
 trainer is tested against), 10-block net, 15x15.  --arith f32,f16x2: the product trainer with each trunk arithmetic
-(HipTrainer trunk_arith), the two alternating --reps times on the same box, step times side by side."""
+(HipTrainer trunk_arith), the two alternating --reps times on the same box, step times side by side.  --side 15,9,13: the
+product trainer per board side (framed sides: HipTrainer framed=True), alternating in one process in the same way, each
+side's step time and its ratio to the first."""
 import argparse
 import json
 import os
@@ -26,11 +28,14 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--arith", default=None, help="comma list of HipTrainer trunk arithmetics (f32,f16x2): alternating runs")
-    ap.add_argument("--reps", type=int, default=3, help="--arith: alternating repetitions")
+    ap.add_argument("--reps", type=int, default=3, help="--arith / --side: alternating repetitions")
+    ap.add_argument("--side", default=None, help="comma list of board sides (15 and framed sides 6, 7, 9, 11 .. 14): alternating runs")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
     out = {}
+    if args.side:
+        return side_ab(args, rs)
     if args.arith:
         return arith_ab(args, prm, rs)
     for B in [int(x) for x in args.batches.split(",")]:
@@ -100,6 +105,42 @@ def arith_ab(args, prm, rs):
                                            for a in ariths) +
               ("   ratio %s/%s %.3f" % (ariths[1], ariths[0], med[ariths[1]] / med[ariths[0]]) if len(ariths) > 1 else ""),
               flush=True)
+        for tr in trs.values():
+            tr.close()
+    print(json.dumps(out))
+
+
+def side_ab(args, rs):
+    """The step per board side and batch size, alternating like arith_ab: one trainer per side, `--reps` rounds of (warm-up
+    step, `--steps` timed steps on an uploaded mini-batch) per side in turn; the median step time per side and its ratio to
+    the first side's."""
+    import torch
+    sides = [int(x) for x in args.side.split(",")]
+    out = {}
+    for B in [int(x) for x in args.batches.split(",")]:
+        trs, batches, times = {}, {}, {S: [] for S in sides}
+        for S in sides:
+            prm = weights.init_params("resnet", S, S, 9, 10, 128, seed=0, style="bench")
+            trs[S] = HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, framed=True)
+            batches[S] = trs[S].upload((rs.rand(B, 9, S, S) > 0.7).astype(np.float32),
+                                       rs.dirichlet(np.ones(S * S), size=B).astype(np.float32),
+                                       rs.choice([-1.0, 1.0], size=B).astype(np.float32))
+        for _ in range(args.reps):
+            for S in sides:
+                trs[S].train_step(batches[S], None, None, 1e-3)
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(args.steps):
+                    trs[S].train_step(batches[S], None, None, 1e-3)
+                torch.cuda.synchronize()
+                times[S].append(1e3 * (time.perf_counter() - t) / args.steps)
+        med = {S: float(np.median(times[S])) for S in sides}
+        for S in sides:
+            out["B%d_side%d" % (B, S)] = {"ms_per_step": med[S], "runs_ms": [round(x, 3) for x in times[S]],
+                                          "ratio_to_side%d" % sides[0]: round(med[S] / med[sides[0]], 4)}
+        print("batch %4d  " % B + "   ".join("%dx%d %.3f ms/step (x%.3f; runs %s)" % (S, S, med[S], med[S] / med[sides[0]],
+                                                                                     ", ".join("%.3f" % x for x in times[S]))
+                                           for S in sides), flush=True)
         for tr in trs.values():
             tr.close()
     print(json.dumps(out))

@@ -5,7 +5,8 @@ with 1000 playouts) on ONE MI355X, asynchronous schedule (alphapig_amd/pipeline.
 step on while the trainer thread updates; every published version is installed device to device.
 Prints one JSON line per reporting window (profiles/r04_train_loop_15x15.log); --lock-step runs round 3's loop;
 --max-update-share caps the share of the wall clock the trainer may be busy; --checkpoint-every / --checkpoint-dir / --resume
-write checkpoints and continue from one (the final line lists what every written part cost)."""
+write checkpoints and continue from one (the final line lists what every written part cost); --side S runs the same loop
+on a framed board (6, 7, 9, 11 .. 14: TrainPipeline train_framed, forced opening off), n_in_row 5."""
 import argparse
 import json
 import os
@@ -65,9 +66,10 @@ def main():
     ap.add_argument("--checkpoint-dir", default=None, help="where they go (default: <model_dir>/checkpoints)")
     ap.add_argument("--checkpoint-selfplay", default="games", choices=("games", "none"),
                     help="save the games in flight with their trees, or abandon them")
+    ap.add_argument("--side", type=int, default=15, help="board side: 15, or a framed side (6, 7, 9, 11 .. 14) with train_framed")
     ap.add_argument("--resume", default=None, help="a checkpoint directory, or 'latest' for the newest complete one in --checkpoint-dir")
     args = ap.parse_args()
-    conf = dict(board_width=15, board_height=15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
+    conf = dict(board_width=args.side, board_height=args.side, train_framed=args.side != 15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
                 n_playout=400, c_puct=5, buffer_size=2198800, batch_size=128, epochs=8, kl_targ=0.02,
                 check_freq=10 ** 9, pure_mcts_playout_num=args.pure_playouts, game_batch_num=args.games,
                 play_batch_size=1, concurrent_games=1024, n_blocks=10, n_filter=128, eval_games=args.eval_games,
