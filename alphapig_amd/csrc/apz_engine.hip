@@ -30,6 +30,7 @@
 #include "sampler.h"
 #include "conv_train.h"
 #include "bn_frame.h"
+#include "grad_guard.h"
 #include "heads_train.h"
 #include "weights_pack.h"
 #include "act_max.h"
@@ -236,6 +237,7 @@ struct apz_engine {
     DeviceBuffer wgw_scratch;                      // the weight gradients' partial sums per batch slice
     DeviceBuffer head_scratch;                     // apz_conv1x1_bwd2 / apz_bias_grad / apz_pv_loss: per-board partial sums
     DeviceBuffer adam_tab;                         // apz_adam_step: device copy of the tensor table
+    DeviceBuffer guard_part;                       // apz_grad_norm / apz_adam_step_guarded: [32 ntensors] doubles, then as many words
     DeviceBuffer gather_entries;                   // apz_replay_gather: device copy of the entry words
     DeviceBuffer wino_scratch[2];                  // apz_wino_conv: rows16 input / output copies
     hipStream_t scratch_stream = nullptr;          // the stream of the last entry point that may have used the scratch buffers
@@ -1343,7 +1345,7 @@ struct StreamScope {      // run the engine's launch helpers on a caller-supplie
     StreamScope(apz_engine* e_, void* s) : e(e_), saved(e_->stream) {
         if (s != APZ_ENGINE_STREAM) e->stream = (hipStream_t)s;   // NULL is a valid handle: the null stream
         // The training entry points share per-engine scratch (the DeviceBuffers of apz_engine: bn_part, wgw_scratch,
-        // head_scratch, adam_tab, gather_entries, wino_scratch; and fold_ws).  Calls on ONE stream are ordered by the
+        // head_scratch, adam_tab, guard_part, gather_entries, wino_scratch; and fold_ws).  Calls on ONE stream are ordered by the
         // stream; a caller that switches streams gets the new stream ordered behind everything queued on the previous
         // one, so two streams never work on the scratch at once.
         if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
@@ -1410,7 +1412,7 @@ void apz_destroy(apz_engine* e) {
                    e->fc_logits, e->fold_ws, e->stage, e->wfc_raw, e->amax_dev, e->fplanes};
     for (void* p : dev)
         if (p) hipFree(p);
-    for (DeviceBuffer* b : {&e->bn_part, &e->wgw_scratch, &e->head_scratch, &e->adam_tab, &e->gather_entries,
+    for (DeviceBuffer* b : {&e->bn_part, &e->wgw_scratch, &e->head_scratch, &e->adam_tab, &e->guard_part, &e->gather_entries,
                             &e->wino_scratch[0], &e->wino_scratch[1]})
         b->release();
     if (e->perm_pinv) hipFree(e->perm_pinv);
@@ -2294,6 +2296,49 @@ int apz_adam_step_unless(apz_engine* e, const void* table_host, int ntensors, fl
                                rescale, (const unsigned*)skip_dev);
         else
             hipLaunchKernelGGL(apz::adam_step_kernel, dim3(32, ntensors), dim3(256), 0, e->stream, tab, lr_t, b1, b2, eps, rescale);
+        return APZ_OK;
+    });
+}
+
+// ---- the guarded optimiser step (csrc/grad_guard.h)
+namespace {
+bool guard_args_ok(const apz_engine* e, const void* table_host, int ntensors, const void* record_dev) {
+    return e && table_host && ntensors >= 1 && ntensors <= 4096 && record_dev && ((uintptr_t)record_dev & 15) == 0;
+}
+// inside a train_call: the table uploaded (stream-ordered, as apz_adam_step_unless does), the two reduction launches queued
+int queue_grad_guard(apz_engine* e, const void* table_host, int ntensors, float rescale, float clip, const void* loss3_dev,
+                     const void* skip_in_dev, void* record_dev) {
+    const size_t bytes = (size_t)ntensors * sizeof(apz::AdamTensor), parts = (size_t)ntensors * apz::GUARD_SPLITS;
+    if (int rc = e->adam_tab.reserve(bytes)) return rc;
+    if (int rc = e->guard_part.reserve(parts * (sizeof(double) + sizeof(unsigned)))) return rc;
+    const auto* tab = e->adam_tab.as<const apz::AdamTensor>();
+    double* part = e->guard_part.as<double>();
+    unsigned* bad = (unsigned*)(part + parts);
+    HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(apz::grad_sumsq_kernel, dim3(apz::GUARD_SPLITS, ntensors), dim3(256), 0, e->stream, tab, part, bad);
+    hipLaunchKernelGGL(apz::grad_guard_fold_kernel, dim3(1), dim3(256), 0, e->stream, (const double*)part, (const unsigned*)bad,
+                       ntensors, rescale, clip, (const float*)loss3_dev, (const unsigned*)skip_in_dev, (apz::GuardRecord*)record_dev);
+    return APZ_OK;
+}
+}  // namespace
+
+int apz_grad_norm(apz_engine* e, const void* table_host, int ntensors, float rescale, float clip, const void* loss3_dev,
+                  const void* skip_in_dev, void* record_dev, void* stream) {
+    if (!guard_args_ok(e, table_host, ntensors, record_dev)) return fail(APZ_E_ARG, "bad argument");
+    static_assert(sizeof(apz::GuardRecord) == 16, "apz guard record layout");
+    return train_call(e, stream, [&]() -> int {
+        return queue_grad_guard(e, table_host, ntensors, rescale, clip, loss3_dev, skip_in_dev, record_dev);
+    });
+}
+
+int apz_adam_step_guarded(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
+                          float rescale, float clip, const void* loss3_dev, const void* skip_in_dev, void* record_dev,
+                          void* stream) {
+    if (!guard_args_ok(e, table_host, ntensors, record_dev)) return fail(APZ_E_ARG, "bad argument");
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = queue_grad_guard(e, table_host, ntensors, rescale, clip, loss3_dev, skip_in_dev, record_dev)) return rc;
+        hipLaunchKernelGGL(apz::adam_step_guarded_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
+                           e->adam_tab.as<const apz::AdamTensor>(), lr_t, b1, b2, eps, (const apz::GuardRecord*)record_dev);
         return APZ_OK;
     });
 }

@@ -535,6 +535,13 @@ def replay_gather(codes, pi, z, entries, height, width, n_planes=9):
 def adam_step(entries, lr_t, b1, b2, eps, rescale, device, skip=None):
     """One launch over all tensors.  entries: [(w, grad, m, v, wd)] of float32 device tensors (apz_adam_step).  skip: a
     device int32 word; when it is not zero at the time the launch runs, nothing is updated (apz_adam_step_unless)."""
+    tab = _adam_table(entries)
+    L, hnd, stream = _ctx(device)
+    _ck(L, L.apz_adam_step_unless(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, _ptr(skip), stream))
+
+
+def _adam_table(entries):
+    """[(w, grad, m, v, wd)] -> the host table of apz_adam_step (48-byte entries)"""
     import numpy as np
     tab = np.zeros(len(entries), dtype=[("w", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("n", "i8"), ("wd", "f4"),
                                         ("pad", "i4")])
@@ -542,5 +549,59 @@ def adam_step(entries, lr_t, b1, b2, eps, rescale, device, skip=None):
         if g.shape != w.shape or not g.is_contiguous():
             raise ValueError("gradient %d: shape / layout mismatch" % i)
         tab[i] = (w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), wd, 0)
+    return tab
+
+
+# why bits of the guard record (csrc/grad_guard.h)
+GUARD_GRAD, GUARD_LOSS, GUARD_SKIP_IN, GUARD_NORM = 1, 2, 4, 8
+
+
+def _guard_record(record, device):
+    torch = _torch()
+    if record is None:
+        return torch.zeros((4,), dtype=torch.float32, device=device)
+    _check(record, "record: a contiguous float32 device tensor of 4 elements", None, (4,))
+    if record.data_ptr() % 16:
+        raise ValueError("record: 16-byte aligned storage")
+    return record
+
+
+def grad_norm(entries, rescale, clip, device, loss3=None, skip=None, record=None):
+    """The global norm of the gradients in entries ([(w, grad, m, v, wd)] as adam_step takes them; only grad is read), two
+    launches (apz_grad_norm) -> record, a float32 device tensor of 4 words {norm, rescale_eff, skip, why} (the last two are
+    uint32: record.view(torch.int32)); read_guard_record() brings it to the host.  norm = sqrt(sum grad^2) * rescale; clip
+    (None or <= 0: off): the norm above which rescale_eff = rescale * clip / norm; loss3: three device floats, skip: a device
+    int32 word -- a non-finite gradient element (why bit 1), a non-finite loss3 (2), a skip word that is not zero (4) or a norm
+    beyond float32 under clipping (8) set skip.  record: such a tensor to fill (16-byte aligned), else a new one."""
+    tab = _adam_table(entries)
     L, hnd, stream = _ctx(device)
-    _ck(L, L.apz_adam_step_unless(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, _ptr(skip), stream))
+    record = _guard_record(record, device)
+    _ck(L, L.apz_grad_norm(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), rescale, clip or 0.0, _ptr(loss3), _ptr(skip),
+                           record.data_ptr(), stream))
+    return record
+
+
+def adam_step_guarded(entries, lr_t, b1, b2, eps, rescale, clip, device, loss3=None, skip=None, record=None):
+    """grad_norm's two launches and then adam_step with the record's rescale_eff in place of rescale, skipped on the device
+    when the record says skip (apz_adam_step_guarded) -> record.  Without a clip and without a skip: adam_step's bits."""
+    tab = _adam_table(entries)
+    L, hnd, stream = _ctx(device)
+    record = _guard_record(record, device)
+    _ck(L, L.apz_adam_step_guarded(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), lr_t, b1, b2, eps, rescale, clip or 0.0,
+                                   _ptr(loss3), _ptr(skip), record.data_ptr(), stream))
+    return record
+
+
+def read_guard_record(words):
+    """Four float32 words as a host array (a record copied back) -> (norm, rescale_eff, skip, why)"""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.float32).reshape(4)
+    u = w.view(np.uint32)
+    return float(w[0]), np.float32(w[1]), bool(u[2]), int(u[3])
+
+
+def guard_reason(why):
+    """The why bits in words"""
+    names = ((GUARD_GRAD, "non-finite gradient"), (GUARD_LOSS, "non-finite loss"), (GUARD_SKIP_IN, "f16x2 overflow"),
+             (GUARD_NORM, "gradient norm beyond float32"))
+    return ", ".join(n for b, n in names if why & b) or None

@@ -158,8 +158,8 @@ class TrainPipeline(object):
         monitor, checkpoints and the arena; default: a second HIP PolicyValueNet, or `policy_value_net` itself when one
         was passed in.  distributed: None = on iff alphapig_amd.dist holds a process group.
         resume: the directory of a checkpoint (save_checkpoint; conf key checkpoint_every) written by a pipeline of the same
-        board, net, batch_size, buffer_size, replay, train_framed, concurrent_games and world size: run() goes on where that
-        one stood."""
+        board, net, batch_size, buffer_size, replay, train_framed, step_guard, clip_norm, concurrent_games and world size:
+        run() goes on where that one stood."""
         self.async_update = bool(conf.get("async_update", True))
         self.round_seconds = float(conf.get("round_seconds", 0.5))
         self.round_steps = conf.get("round_steps")
@@ -220,6 +220,16 @@ class TrainPipeline(object):
                 if self.train_arith != "f32":
                     raise ValueError("train_framed on a %dx%d board takes train_arith='f32', not %r: the f16x2 trunk's "
                                      "statistics epilogue and scales see off-board cells" % (bw, bh, self.train_arith))
+        # step_guard / clip_norm (default off / None): HipTrainer's guarded optimiser step -- a step whose gradients or
+        # losses are not finite is skipped on the device instead of reaching the weights, the moments and, through them,
+        # every self-play evaluator and the next checkpoint; clip_norm (a finite positive number; implies the guard) clips
+        # the global gradient norm.  The history record counts skipped and clipped steps; a skipped one is logged.
+        self.clip_norm = conf.get("clip_norm")
+        if self.clip_norm is not None:
+            self.clip_norm = float(self.clip_norm)
+            if not (np.isfinite(self.clip_norm) and self.clip_norm > 0):
+                raise ValueError("clip_norm must be None or a finite positive number, not %r" % (conf.get("clip_norm"),))
+        self.step_guard = bool(conf.get("step_guard", False)) or self.clip_norm is not None
         if self.replay == "device":
             import torch
             if not torch.cuda.is_available():
@@ -242,6 +252,8 @@ class TrainPipeline(object):
                                                      "batch_size", "buffer_size", "concurrent_games")}
         self._conf_match["replay"] = self.replay
         self._conf_match["train_framed"] = self.train_framed
+        self._conf_match["step_guard"] = self.step_guard
+        self._conf_match["clip_norm"] = self.clip_norm
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -383,13 +395,22 @@ class TrainPipeline(object):
             # a re-created trainer (set_params dropped the old one) continues the dropout mask sequence instead of replaying it
             net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                       device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
-                                      trunk_arith=self.train_arith, framed=self.train_framed)
+                                      trunk_arith=self.train_arith, framed=self.train_framed, step_guard=self.step_guard,
+                                      clip_norm=self.clip_norm)
         return net._trainer
 
     def _note_overflows(self, rec, trainer):
-        """train_arith f16x2: the update record carries the trainer's count of steps repeated on the exact kernels"""
+        """train_arith f16x2: the update record carries the trainer's count of steps repeated on the exact kernels;
+        step_guard / clip_norm: its counts of skipped and clipped steps so far and the last step's gradient norm"""
         if self.train_arith == "f16x2":
             rec["trunk_overflows"] = int(getattr(trainer, "trunk_overflows", 0))
+        if self.step_guard:
+            rec["skipped_steps"] = int(getattr(trainer, "skipped_steps", 0))
+            rec["clipped_steps"] = int(getattr(trainer, "clipped_steps", 0))
+            # (a skipped step's norm is NaN or inf: None in the record, which travels into a checkpoint's state.json --
+            # json.dump would write the tokens NaN / Infinity, which strict JSON readers refuse)
+            norm = getattr(trainer, "last_grad_norm", None)
+            rec["grad_norm"] = float(norm) if norm is not None and np.isfinite(norm) else None
 
     def _note_act_scale(self, rec):
         """Every round / batch record carries the self-play evaluator's count of forwards repeated on the exact kernel
@@ -426,6 +447,10 @@ class TrainPipeline(object):
         self.last_monitors = mon                          # train_mxnet.py:222-239: the value head's explained variance
         _logger.info("kl:%.4f lr:%.1e lr_multiplier:%.3f loss:%.4f entropy:%.4f explained_var_old:%.3f explained_var_new:%.3f",
                      kl, mon["learn_rate"], self.lr_multiplier, loss, entropy, mon["explained_var_old"], mon["explained_var_new"])
+        if mon.get("skipped_steps"):        # a guarded trainer refused steps: the mini-batch or the activations were not finite
+            _logger.warning("policy_update: %d optimiser step(s) skipped (%s), %d so far; grad_norm %r", mon["skipped_steps"],
+                            getattr(trainer, "last_skip_reason", None), int(getattr(trainer, "skipped_steps", 0)),
+                            mon.get("grad_norm"))
         return loss, entropy, kl
 
     def _exchange_update(self, rec):
@@ -609,7 +634,7 @@ class TrainPipeline(object):
     def _resume(self, path):
         state = checkpoint.read_state(path)
         for k, mine in self._conf_match.items():
-            theirs = state["conf"].get(k, False if k == "train_framed" else None)   # (a checkpoint from before the key: off)
+            theirs = state["conf"].get(k, False if k in ("train_framed", "step_guard") else None)   # (a checkpoint from before the key: off)
             if theirs != mine:
                 raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
                                  (path, k, theirs, k, mine))
@@ -746,7 +771,7 @@ class TrainPipeline(object):
                 if trainer is None:
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                          device_index=net._device, seed=self._seed, trunk_arith=self.train_arith,
-                                         framed=self.train_framed)
+                                         framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm)
                 self._async_trainer = trainer
                 tstate = getattr(self, "_async_trainer_state", None)
                 if tstate is not None:                  # resume=: the trainer this thread built continues the saved one

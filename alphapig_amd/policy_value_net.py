@@ -61,7 +61,8 @@ def act_exponent_for(m, k_min=None, k_max=None):
 class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
-                 uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0, train_framed=False):
+                 uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0, train_framed=False,
+                 train_step_guard=False, train_clip_norm=None):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -89,7 +90,9 @@ class PolicyValueNet(object):
           "mean8"  the mean of the eight folded answers, from ONE forward of 8 n boards: equivariant by construction.  The
                    engine is then created with max_batch = 8 * batch_size, `batchsize` stays the caller's, and the trunk
                    arithmetic a batch gets is that of 8 n boards (five positions under "auto": a 40-board f16x2 forward).
-        forward_planes / policy_value (the KL monitor, calibrate_trunk, prewarm) are not concerned."""
+        forward_planes / policy_value (the KL monitor, calibrate_trunk, prewarm) are not concerned.
+        train_step_guard / train_clip_norm: HipTrainer's step_guard / clip_norm for the trainer train_step builds -- a step
+        whose gradients or losses are not finite is skipped instead of reaching the weights; global-norm clipping."""
         check_leaf_symmetry(leaf_symmetry)
         self.L = _native.hip()
         self.board_width, self.board_height = int(board_width), int(board_height)
@@ -98,6 +101,7 @@ class PolicyValueNet(object):
         self._n_blocks, self._n_filter = int(n_blocks), int(n_filter)
         self.net_kind = net_kind
         self.train_framed = bool(train_framed)
+        self.train_step_guard, self.train_clip_norm = bool(train_step_guard), train_clip_norm
         self._device = int(device)
         self.hw = self.board_width * self.board_height
         self.code_stride = (self.hw + 1 + 15) // 16 * 16
@@ -430,7 +434,8 @@ class PolicyValueNet(object):
         from .train import HipTrainer
         if getattr(self, "_trainer", None) is None:
             self._trainer = HipTrainer(self.params(), self.net_kind, self._n_blocks, batch_size=self.batchsize,
-                                       device_index=self._device, framed=self.train_framed)
+                                       device_index=self._device, framed=self.train_framed,
+                                       step_guard=self.train_step_guard, clip_norm=self.train_clip_norm)
         loss, entropy = self._trainer.train_step(state_batch, mcts_probs, winner_batch, learning_rate)
         self._trainer.sync_evaluator(self)
         return np.array([loss], dtype=np.float32), np.array([entropy], dtype=np.float32)

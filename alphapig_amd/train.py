@@ -14,6 +14,9 @@ the self-play path.  The module needs the HIP library and a GPU; without them co
             1/batch_size on top of the mean loss; wd = 1e-4 on *_weight and *_gamma only), m/v moments,
             lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t), eps 1e-8
   policy_update   epochs x train_step with the KL-adaptive learning-rate multiplier and the 4 * kl_targ early stop
+  guard     opt-in (step_guard / clip_norm; csrc/grad_guard.h): the global gradient norm taken on the device in front of
+            Adam, global-norm clipping inside Adam's rescale factor, and a step whose gradients or losses are not finite
+            skipped on the device -- weights, moments, moving statistics and t as if it had not been asked for
 
 The 10-block / 128-filter / 15x15 network keeps its trunk activations in the self-play kernels' padded-row layout
 [n][128][15][16] from the stem's BatchNorm to the heads (forward and data gradient on the fused Winograd kernel of
@@ -77,7 +80,8 @@ def check_trainable_board(params, framed=False, net_kind="resnet", trunk_arith="
 
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
-                 seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False):
+                 seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False, step_guard=False,
+                 clip_norm=None):
         """params: name -> array, in any order.  height / width: the board (default: square, from the policy head's size).
         seed / dropout_step0: the dropout masks are a stateless hash of (seed, dropout_step0 + step, element) -- a trainer
         that is re-created (set_params, a resumed checkpoint) or one of several ranks passes its own seed / the steps
@@ -92,9 +96,23 @@ class HipTrainer(object):
         only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)
         framed: opt in to the training step on the framed boards (6x6, 7x7, 9x9, 11x11 .. 14x14; check_trainable_board):
         the residual net of 128 filters on the 15x15 trunk kernels, the board mask in the BatchNorm passes.  Without it
-        those boards raise ValueError as they always did; 15x15 and 8x8 train as they always did whatever it says."""
+        those boards raise ValueError as they always did; 15x15 and 8x8 train as they always did whatever it says.
+        step_guard: opt in to the guarded optimiser step (csrc/grad_guard.h): two reduction launches in front of Adam take
+        the global norm of the step's gradients (last_grad_norm: of grad / batch_size, what Adam sees before weight decay)
+        and look for non-finite values in the gradients and the three losses; a step that has one is SKIPPED on the device
+        -- weights, moments, moving statistics, t and with it the next dropout masks are as if it had not been asked for
+        (skipped_steps, last_skip_reason) -- and train_step still returns that step's (non-finite) loss.  The verdict
+        travels in the step's one read-back: no second synchronisation.  A step that is not skipped has the unguarded
+        step's bits.  On "f16x2" the overflow word is one more reason to skip: the step is repeated on the exact kernels as
+        always, and the repeat is guarded in turn.
+        clip_norm: None, or a finite positive number -- global-norm clipping (implies step_guard): a step whose gradient
+        norm exceeds it has its gradient scaled to that norm (clipped_steps), inside Adam's rescale factor."""
         if trunk_arith not in ("f32", "f16x2"):
             raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
+        if clip_norm is not None:
+            clip_norm = float(clip_norm)
+            if not (np.isfinite(clip_norm) and clip_norm > 0):
+                raise ValueError("clip_norm must be None or a finite positive number, not %r" % (clip_norm,))
         if "fc_3_1_1_bias" in params:
             # before anything touches the GPU: today's failure would come from the first step
             check_trainable_board(params, framed, net_kind, trunk_arith)
@@ -170,6 +188,18 @@ class HipTrainer(object):
                 kb = k[:-len("_weight")] + "_bias"
                 self._trunk_b[j].copy_(self.p[kb])
                 self.p[kb] = self._trunk_b[j]
+            self._u16 = None
+        # the guarded step (csrc/grad_guard.h) skips on the device; what it must not move either lives in the same
+        # arrangement, for every net kind and arithmetic: the statistics in one buffer with a snapshot, and the guard's
+        # 16-byte record behind the overflow word (16 bytes in: aligned), all in the step's ONE device -> host copy
+        self.clip_norm = clip_norm
+        self.step_guard = bool(step_guard) or clip_norm is not None
+        self.last_grad_norm = None     # of the last guarded train_step (grad / batch_size, before weight decay)
+        self.skipped_steps = 0         # guarded steps that left everything as it was
+        self.clipped_steps = 0         # guarded steps taken with the gradient scaled to clip_norm
+        self.last_skip_reason = None   # of the last guarded train_step: None (taken), or the record's why bits in words
+        self.last_rescale_eff = None   # of the last guarded train_step: the `rescale` Adam ran with (float32)
+        if trunk_arith == "f16x2" or self.step_guard:
             self._stat_buf = torch.empty((sum(self.p[k].numel() for k in self.stat_names),), dtype=torch.float32, device=self.device)
             off = 0
             for k in self.stat_names:
@@ -178,9 +208,10 @@ class HipTrainer(object):
                 self.p[k] = v
                 off += v.numel()
             self._stat_snap = torch.empty_like(self._stat_buf)
-            self._word = torch.zeros((4,), dtype=torch.float32, device=self.device)   # [loss3][overflow word]
-            self._flag = self._word[3:]
-            self._u16 = None
+            # [loss3][overflow word] (+ [record])
+            self._word = torch.zeros((8 if self.step_guard else 4,), dtype=torch.float32, device=self.device)
+            self._flag = self._word[3:4]
+            self._record = self._word[4:8] if self.step_guard else None
         self._eval = None
         self._eval_t = -1
         self.tape = None
@@ -429,13 +460,13 @@ class HipTrainer(object):
         self._stat_snap.copy_(self._stat_buf)
         return state_batch, self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True, loss3=loss3)
 
-    def _repeat_exact(self, batch, keep_tape):
+    def _repeat_exact(self, batch, keep_tape, loss3=None):
         """An f16x2 launch of the pass just queued left the fp16 range: its gradients never reached Adam; the moving
         statistics go back to their values at the start of the pass, which is then taken again on the exact kernels
         -> loss3."""
         self.trunk_overflows += 1
         self._stat_buf.copy_(self._stat_snap)
-        return self._loss_and_grads(batch, keep_tape=keep_tape)
+        return self._loss_and_grads(batch, keep_tape=keep_tape, loss3=loss3)
 
     def relu_masks(self):
         """{layer: [n][C][H][W] bool} -- which activations of the kept forward pass were positive.  (A comparator that
@@ -454,7 +485,9 @@ class HipTrainer(object):
 
     def train_step(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape=False):
         """One optimiser step -> (loss, entropy).  state_batch may be upload()'s DeviceBatch (mcts_probs / winner_batch are
-        then ignored)."""
+        then ignored).  step_guard: see __init__ -- a skipped step returns its own losses, NaN included."""
+        if self.step_guard:
+            return self._train_step_guarded(state_batch, mcts_probs, winner_batch, learning_rate, keep_tape)
         if self.trunk_arith == "f16x2":
             batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=self._word[:3])
             self.t += 1
@@ -471,12 +504,62 @@ class HipTrainer(object):
         l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
         return float(l3[0] + l3[1]), float(l3[2])
 
-    def _adam(self, learning_rate, skip=None):
+    def _train_step_guarded(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape):
+        """train_step with the guard on: snapshot, pass, guard and guarded Adam queued; ONE read-back of [loss3][overflow
+        word][record]; a record that says skip puts the statistics back and takes t back."""
+        loss3 = self._word[:3]
+        if self.trunk_arith == "f16x2":
+            batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=loss3)
+            self.t += 1
+            self._adam(learning_rate, skip=self._flag, guarded=True)      # (the overflow word is one of the guard's reasons)
+            w8 = self._word.cpu().numpy()
+            if w8[3:4].view(np.uint32)[0] != 0:
+                # overflowed: nothing reached Adam.  The exact repeat as always (the snapshot still holds the statistics at
+                # the start of the step), guarded in turn; its word 3 stays set and says nothing about the repeat.
+                self.t -= 1
+                self._repeat_exact(batch, keep_tape, loss3=loss3)
+                self.t += 1
+                self._adam(learning_rate, guarded=True)
+                w8 = self._word.cpu().numpy()
+        else:
+            batch = state_batch if isinstance(state_batch, DeviceBatch) else self.upload(state_batch, mcts_probs, winner_batch)
+            self._stat_snap.copy_(self._stat_buf)
+            self._loss_and_grads(batch, keep_tape=keep_tape, loss3=loss3)
+            self.t += 1
+            self._adam(learning_rate, guarded=True)
+            w8 = self._word.cpu().numpy()      # the losses and the record: still the step's only synchronisation
+        norm, eff, skip, why = self.ops.read_guard_record(w8[4:8])
+        self.last_grad_norm, self.last_rescale_eff = norm, eff
+        self.last_skip_reason = self.ops.guard_reason(why)
+        if skip:
+            self._stat_buf.copy_(self._stat_snap)
+            self.t -= 1                 # (the next step draws this step's dropout masks; the internal evaluator is not stale)
+            self.skipped_steps += 1
+        elif eff != np.float32(1.0 / self.batch_size):
+            self.clipped_steps += 1
+        return float(w8[0] + w8[1]), float(w8[2])
+
+    def _entries(self):
+        return [(self.p[k], self.grad[k], self.m[k], self.v[k], self.wd if k.endswith(("_weight", "_gamma")) else 0.0)
+                for k in self.train_names]
+
+    def _adam(self, learning_rate, skip=None, guarded=False):
         b1, b2, eps = 0.9, 0.999, 1e-8
         lr_t = learning_rate * (1.0 - b2 ** self.t) ** 0.5 / (1.0 - b1 ** self.t)
-        entries = [(self.p[k], self.grad[k], self.m[k], self.v[k], self.wd if k.endswith(("_weight", "_gamma")) else 0.0)
-                   for k in self.train_names]
-        self.ops.adam_step(entries, lr_t, b1, b2, eps, 1.0 / self.batch_size, self.device, skip=skip)
+        if guarded:
+            self.ops.adam_step_guarded(self._entries(), lr_t, b1, b2, eps, 1.0 / self.batch_size, self.clip_norm, self.device,
+                                       loss3=self._word[:3], skip=skip, record=self._record)
+        else:
+            self.ops.adam_step(self._entries(), lr_t, b1, b2, eps, 1.0 / self.batch_size, self.device, skip=skip)
+
+    def grad_norm(self):
+        """The global norm of self.grad after a loss_and_grads, as the guard measures it: of grad / batch_size, the gradient
+        Adam sees before weight decay -- the scale clip_norm is compared with.  Two launches and a read-back (a
+        synchronisation); works with the guard off as well."""
+        if not self.grad:
+            raise RuntimeError("grad_norm() needs the gradients of a loss_and_grads or train_step")
+        rec = self.ops.grad_norm(self._entries(), 1.0 / self.batch_size, None, self.device)
+        return self.ops.read_guard_record(rec.cpu().numpy())[0]
 
     def sync_evaluator(self, net):
         """Give `net` (a PolicyValueNet of the same architecture) this trainer's current weights, device to device:
@@ -511,12 +594,15 @@ class HipTrainer(object):
 
     # ---- checkpoint -----------------------------------------------------------------------------------------------
     def state(self):
-        """Everything the next train_step reads, as host values: {"meta": t, dropout_step0, seed, trunk_overflows and the
-        net's kind (the dropout masks are keyed by seed and dropout_step0 + t), "p/<name>": every parameter and BatchNorm
-        statistic, "m/<name>" / "v/<name>": Adam's moments} -- what load_state takes."""
+        """Everything the next train_step reads, as host values: {"meta": t, dropout_step0, seed, trunk_overflows, the guard's
+        two settings and two counters and the net's kind (the dropout masks are keyed by seed and dropout_step0 + t),
+        "p/<name>": every parameter and BatchNorm statistic, "m/<name>" / "v/<name>": Adam's moments} -- what load_state
+        takes."""
         out = {"meta": {"t": int(self.t), "dropout_step0": int(self.dropout_step0), "seed": int(self.seed),
                         "trunk_overflows": int(self.trunk_overflows), "net_kind": self.kind, "n_blocks": int(self.n_blocks),
-                        "trunk_arith": self.trunk_arith, "framed": self.framed}}
+                        "trunk_arith": self.trunk_arith, "framed": self.framed, "step_guard": self.step_guard,
+                        "clip_norm": self.clip_norm, "skipped_steps": int(self.skipped_steps),
+                        "clipped_steps": int(self.clipped_steps)}}
         for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
             for k, t in group.items():
                 out["%s/%s" % (tag, k)] = t.cpu().numpy()
@@ -547,6 +633,10 @@ class HipTrainer(object):
         self.dropout_step0 = int(meta["dropout_step0"])
         self.seed = int(meta["seed"])
         self.trunk_overflows = int(meta["trunk_overflows"])
+        # (a state from before the guard: zeros.  Whether THIS trainer guards and clips is its constructor's word; the
+        # state's own step_guard / clip_norm say what the run that wrote it did.)
+        self.skipped_steps = int(meta.get("skipped_steps", 0))
+        self.clipped_steps = int(meta.get("clipped_steps", 0))
         self._eval_t = -1
         self.tape = None
 
@@ -573,6 +663,9 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
     PolicyValueNet) supplies old/new predictions when given, else the trainer's own inference
     graph.  -> (loss, entropy, kl, lr_multiplier); `monitors` (a dict, optional) receives the reference's value-head
     monitors explained_var_old / explained_var_new (train_mxnet.py:222-227) and the learning rate used.
+    A trainer with the guard's counters (HipTrainer: skipped_steps, clipped_steps, last_grad_norm) also gets grad_norm (of
+    the update's last step), skipped_steps and clipped_steps (of this update) into `monitors`, and an update whose every
+    step was skipped leaves lr_multiplier alone: it changed nothing, so its KL is 0 and would otherwise raise it.
     mini_batch may also be the DeviceBatch a code replay buffer draws (alphapig_amd/replay.py), already stacked.  NumPy
     arrays (CompactReplayBuffer): uploaded once, like the list's.  Device tensors (DeviceReplayBuffer): no stacking and no
     upload; the KL monitor's forwards read the planes where they are (`policy_value_dev`; an evaluator without it gets them
@@ -600,8 +693,14 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
     new_v = old_v
     loss = entropy = kl = 0.0
     lr_used = lr_multiplier                               # (the reference logs learn_rate * the multiplier the epochs ran with)
+    # a guarded trainer (HipTrainer(step_guard=True)) counts the steps it refused; one without the guard or the counters
+    # behaves as before
+    guarded = bool(getattr(trainer, "step_guard", hasattr(trainer, "skipped_steps")))
+    skipped0, clipped0 = (int(trainer.skipped_steps), int(getattr(trainer, "clipped_steps", 0))) if guarded else (0, 0)
+    steps = 0
     for _ in range(epochs):
         loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
+        steps += 1
         if evaluator is not None:
             if hasattr(trainer, "sync_evaluator") and hasattr(evaluator, "load_device_params"):
                 trainer.sync_evaluator(evaluator)
@@ -611,10 +710,17 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
         kl = float(np.mean(np.sum(old_probs * (np.log(old_probs + 1e-10) - np.log(new_probs + 1e-10)), axis=1)))
         if kl > kl_targ * 4:
             break
-    if kl > kl_targ * 2 and lr_multiplier > 0.05:        # train_mxnet.py:215-218
+    skipped = int(trainer.skipped_steps) - skipped0 if guarded else 0
+    if steps > 0 and skipped == steps:
+        pass            # every step was skipped: nothing changed, the KL is 0 and says nothing about the learning rate
+    elif kl > kl_targ * 2 and lr_multiplier > 0.05:        # train_mxnet.py:215-218
         lr_multiplier /= 1.5
     elif kl < kl_targ / 2 and lr_multiplier < 20:
         lr_multiplier *= 1.5
+    if monitors is not None and guarded:
+        monitors["grad_norm"] = getattr(trainer, "last_grad_norm", None)       # of the update's last step
+        monitors["skipped_steps"] = skipped                                      # in this update
+        monitors["clipped_steps"] = int(getattr(trainer, "clipped_steps", 0)) - clipped0
     if monitors is not None:
         monitors["explained_var_old"] = explained_variance(zs, old_v)
         monitors["explained_var_new"] = explained_variance(zs, new_v)

@@ -280,6 +280,34 @@ int apz_bn_bwd_max(apz_engine *e, const void *dy_dev, const void *x_dev, const v
                    int layout, int relu, void *stream);
 int apz_adam_step_unless(apz_engine *e, const void *table_host, int ntensors, float lr_t, float b1, float b2,
                          float eps, float rescale, const void *skip_dev, void *stream);
+/* The guarded optimiser step (csrc/grad_guard.h; HipTrainer(step_guard=True, clip_norm=...)): the global norm of the
+ * gradients in the Adam table, global-norm clipping and a refusal of non-finite steps, decided on the device.
+ *   apz_grad_norm          two launches over the table's g tensors (w, m, v are not read): per-workgroup sums of squares in
+ *                          double (no atomics, a fixed order: the same bits on every run and for every alignment of g), then
+ *                          one workgroup that writes the 16-byte record at record_dev (16-byte aligned).  The order, for a
+ *                          reader who wants the bits: grid (32, ntensors) x 256 threads; thread j of workgroup b of tensor t
+ *                          adds the squares of elements 4 q .. 4 q + 3, q = 256 b + j, + 8192, ..., in index order; the
+ *                          workgroup's 256 sums go through a 64-lane shuffle tree (offsets 32, 16, .., 1) and the four
+ *                          wave sums are added in wave order; the fold adds tensor t's 32 workgroup sums in index order
+ *                          and then the ntensors tensor sums in index order (two levels, not one chain over all 32 *
+ *                          ntensors partials).  The record:
+ *                            { float norm; float rescale_eff; uint32 skip; uint32 why; }
+ *                          norm = sqrt(sum g^2) * rescale (the float64 value rounded once);
+ *                          why: bit 1  a gradient element is not finite
+ *                               bit 2  one of the three floats at loss3_dev (NULL: not looked at) is not finite
+ *                               bit 4  the 32-bit word at skip_in_dev (NULL: none; the f16x2 overflow word) is not zero
+ *                               bit 8  clip > 0 and norm, finite in double, does not fit a finite float
+ *                          skip = (why != 0);
+ *                          rescale_eff = rescale when clip <= 0 or norm <= clip, else the fp32 product
+ *                          rescale * (float)(clip / norm): the gradient scaled to norm `clip`.
+ *   apz_adam_step_guarded  the same two launches and then apz_adam_step with rescale_eff in place of rescale -- nothing is
+ *                          updated when skip is set.  A step that neither clips nor skips has apz_adam_step's bits.
+ * Arguments are checked as apz_adam_step's; no stream synchronisation. */
+int apz_grad_norm(apz_engine *e, const void *table_host, int ntensors, float rescale, float clip, const void *loss3_dev,
+                  const void *skip_in_dev, void *record_dev, void *stream);
+int apz_adam_step_guarded(apz_engine *e, const void *table_host, int ntensors, float lr_t, float b1, float b2, float eps,
+                          float rescale, float clip, const void *loss3_dev, const void *skip_in_dev, void *record_dev,
+                          void *stream);
 int apz_bn_bwd_splits(apz_engine *e, int n, int C, int layout);
 int apz_colsum(apz_engine *e, const void *in_dev, void *out_dev, int rows, int cols, float scale, void *stream);
 

@@ -4,7 +4,8 @@ this repository) beside the same graph in PyTorch (MIOpen convolutions; tests/to
 trainer is tested against), 10-block net, 15x15.  --arith f32,f16x2: the product trainer with each trunk arithmetic
 (HipTrainer trunk_arith), the two alternating --reps times on the same box, step times side by side.  --side 15,9,13: the
 product trainer per board side (framed sides: HipTrainer framed=True), alternating in one process in the same way, each
-side's step time and its ratio to the first."""
+side's step time and its ratio to the first.  --step-guard: the product trainer without and with the guarded optimiser step
+(HipTrainer step_guard; --clip-norm adds clipping), alternating in the same way, per --arith arithmetic (default f32)."""
 import argparse
 import json
 import os
@@ -30,12 +31,16 @@ def main():
     ap.add_argument("--arith", default=None, help="comma list of HipTrainer trunk arithmetics (f32,f16x2): alternating runs")
     ap.add_argument("--reps", type=int, default=3, help="--arith / --side: alternating repetitions")
     ap.add_argument("--side", default=None, help="comma list of board sides (15 and framed sides 6, 7, 9, 11 .. 14): alternating runs")
+    ap.add_argument("--step-guard", action="store_true", help="HipTrainer step_guard off / on: alternating runs")
+    ap.add_argument("--clip-norm", type=float, default=None, help="--step-guard: the guarded trainer's clip_norm")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
     out = {}
     if args.side:
         return side_ab(args, rs)
+    if args.step_guard:
+        return guard_ab(args, prm, rs)
     if args.arith:
         return arith_ab(args, prm, rs)
     for B in [int(x) for x in args.batches.split(",")]:
@@ -107,6 +112,47 @@ def arith_ab(args, prm, rs):
               flush=True)
         for tr in trs.values():
             tr.close()
+    print(json.dumps(out))
+
+
+def guard_ab(args, prm, rs):
+    """The step without and with the guard per batch size (and --arith arithmetic), alternating like arith_ab: one trainer
+    each from the same weights, `--reps` rounds of (warm-up step, `--steps` timed steps on an uploaded mini-batch) in turn;
+    the median step time of each, all runs (their spread is the yardstick for the difference), the guarded trainer's
+    counters."""
+    import torch
+    out = {}
+    for B in [int(x) for x in args.batches.split(",")]:
+        states = (rs.rand(B, 9, 15, 15) > 0.7).astype(np.float32)
+        pis = rs.dirichlet(np.ones(225), size=B).astype(np.float32)
+        zs = rs.choice([-1.0, 1.0], size=B).astype(np.float32)
+        for a in (args.arith or "f32").split(","):
+            trs = {"plain": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a),
+                   "guarded": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a, step_guard=True,
+                                         clip_norm=args.clip_norm)}
+            batches = {k: tr.upload(states, pis, zs) for k, tr in trs.items()}
+            times = {k: [] for k in trs}
+            for _ in range(args.reps):
+                for k, tr in trs.items():
+                    tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    for _ in range(args.steps):
+                        tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    times[k].append(1e3 * (time.perf_counter() - t) / args.steps)
+            med = {k: float(np.median(times[k])) for k in trs}
+            g = trs["guarded"]
+            for k in trs:
+                out["B%d_%s_%s" % (B, a, k)] = {"ms_per_step": med[k], "runs_ms": [round(x, 3) for x in times[k]]}
+            out["B%d_%s_guarded" % (B, a)].update(skipped_steps=g.skipped_steps, clipped_steps=g.clipped_steps,
+                                                  grad_norm=g.last_grad_norm)
+            print("batch %4d %-5s  " % (B, a) +
+                  "   ".join("%s %.3f ms/step (runs %s)" % (k, med[k], ", ".join("%.3f" % x for x in times[k])) for k in trs) +
+                  "   ratio guarded/plain %.4f   grad_norm %.4g skipped %d clipped %d" %
+                  (med["guarded"] / med["plain"], g.last_grad_norm, g.skipped_steps, g.clipped_steps), flush=True)
+            for tr in trs.values():
+                tr.close()
     print(json.dumps(out))
 
 

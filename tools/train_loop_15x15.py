@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--checkpoint-selfplay", default="games", choices=("games", "none"),
                     help="save the games in flight with their trees, or abandon them")
     ap.add_argument("--side", type=int, default=15, help="board side: 15, or a framed side (6, 7, 9, 11 .. 14) with train_framed")
+    ap.add_argument("--step-guard", action="store_true",
+                    help="skip optimiser steps whose gradients or losses are not finite (TrainPipeline step_guard)")
+    ap.add_argument("--clip-norm", type=float, default=None, help="clip the global gradient norm (TrainPipeline clip_norm; implies --step-guard)")
     ap.add_argument("--resume", default=None, help="a checkpoint directory, or 'latest' for the newest complete one in --checkpoint-dir")
     args = ap.parse_args()
     conf = dict(board_width=args.side, board_height=args.side, train_framed=args.side != 15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
@@ -76,7 +79,8 @@ def main():
                 model_dir="/tmp/apz_models_15", async_update=not args.lock_step, round_seconds=0.25,
                 max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith,
                 act_scale=args.act_scale, replay=args.replay, checkpoint_every=args.checkpoint_every,
-                checkpoint_dir=args.checkpoint_dir, checkpoint_selfplay=args.checkpoint_selfplay)
+                checkpoint_dir=args.checkpoint_dir, checkpoint_selfplay=args.checkpoint_selfplay,
+                step_guard=args.step_guard, clip_norm=args.clip_norm)
     resume = args.resume
     if resume == "latest":
         from alphapig_amd import checkpoint
