@@ -122,7 +122,7 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_conv3x3_fwd", "apz_conv3x3_wgrad", "apz_wino_packed_size", "apz_wino_pack", "apz_wino_pack_many", "apz_wino_conv",
                "apz_wino_conv_add", "apz_wino_conv_stats", "apz_bn_fwd", "apz_bn_fwd_stats", "apz_bn_bwd", "apz_bn_bwd_splits", "apz_colsum", "apz_adam_step", "apz_wgrad_wino",
                "apz_wino3h_packed_size", "apz_wino3h_pack_many", "apz_wino3h_conv_stats", "apz_wino3h_conv_dgrad", "apz_bn_bwd_max", "apz_wgrad_wino_f16x2",
-               "apz_adam_step_unless", "apz_grad_norm", "apz_adam_step_guarded",
+               "apz_adam_step_unless", "apz_grad_norm", "apz_adam_step_guarded", "apz_ema_update",
                "apz_conv1x1_fwd", "apz_conv1x1_bwd", "apz_conv1x1_bwd2", "apz_fc_fwd", "apz_fc_bwd", "apz_dropout", "apz_pv_loss",
                "apz_layout_convert", "apz_bias_grad", "apz_add", "apz_load_weights_dev",
                "apz_sync", "apz_stream", "apz_set_forward_graphs",
@@ -265,6 +265,7 @@ def hip():
         "apz_grad_norm": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]),
         "apz_adam_step_guarded": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp,
                                             vp, vp]),
+        "apz_ema_update": (C.c_int, [vp, vp, C.c_int, C.c_float, vp, vp, vp]),
         "apz_wino3h_packed_size": (C.c_int64, []),
         "apz_wino3h_pack_many": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp]),
         "apz_wino3h_conv_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp]),

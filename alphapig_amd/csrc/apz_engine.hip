@@ -31,6 +31,7 @@
 #include "conv_train.h"
 #include "bn_frame.h"
 #include "grad_guard.h"
+#include "ema.h"
 #include "heads_train.h"
 #include "weights_pack.h"
 #include "act_max.h"
@@ -2339,6 +2340,24 @@ int apz_adam_step_guarded(apz_engine* e, const void* table_host, int ntensors, f
         if (int rc = queue_grad_guard(e, table_host, ntensors, rescale, clip, loss3_dev, skip_in_dev, record_dev)) return rc;
         hipLaunchKernelGGL(apz::adam_step_guarded_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
                            e->adam_tab.as<const apz::AdamTensor>(), lr_t, b1, b2, eps, (const apz::GuardRecord*)record_dev);
+        return APZ_OK;
+    });
+}
+
+// ---- the averaged weights (csrc/ema.h)
+int apz_ema_update(apz_engine* e, const void* table_host, int ntensors, float c, const void* skip_a_dev, const void* skip_b_dev,
+                   void* stream) {
+    if (!e || ntensors < 0 || ntensors > 4096 || (ntensors > 0 && !table_host)) return fail(APZ_E_ARG, "bad argument");
+    static_assert(sizeof(apz::EmaTensor) == 24, "apz_ema_tensor layout");
+    if (ntensors == 0) return APZ_OK;       // an empty table: nothing to launch (a grid of (32, 0) is not one)
+    return train_call(e, stream, [&]() -> int {
+        // the table travels as apz_adam_step_unless's does, through the same device buffer: the copy queues behind the
+        // Adam launch in front of it, which read its own table there
+        const size_t bytes = (size_t)ntensors * sizeof(apz::EmaTensor);
+        if (int rc = e->adam_tab.reserve(bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(apz::ema_update_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
+                           e->adam_tab.as<const apz::EmaTensor>(), c, (const unsigned*)skip_a_dev, (const unsigned*)skip_b_dev);
         return APZ_OK;
     });
 }

@@ -552,6 +552,40 @@ def _adam_table(entries):
     return tab
 
 
+def ema_update(entries, c, device, skip=None, skip2=None):
+    """The averaged weights' step, one launch over all tensors (apz_ema_update; csrc/ema.h): entries [(shadow, weight)] of
+    float32 device tensors, shadow = shadow + c * (weight - shadow) in three separately rounded float32 operations.  skip /
+    skip2: device int32 words; when either is not zero at the time the launch runs, nothing is written.  entries may also be
+    the table ema_table(entries) returned: a caller whose tensors stay where they are (HipTrainer) builds it once."""
+    import numpy as np
+    if isinstance(entries, np.ndarray):
+        tab = entries
+        if tab.dtype != _EMA_ENTRY or tab.ndim != 1 or not tab.flags.c_contiguous:
+            raise ValueError("ema_update takes [(shadow, weight)] or the table ema_table() built, not an array of dtype %s" % tab.dtype)
+    else:
+        tab = ema_table(entries)
+    L, hnd, stream = _ctx(device)
+    _ck(L, L.apz_ema_update(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), float(c), _ptr(skip), _ptr(skip2), stream))
+
+
+_EMA_ENTRY = [("s", "u8"), ("w", "u8"), ("n", "i8")]     # apz_ema_update's 24-byte entry
+
+
+def ema_table(entries):
+    """[(shadow, weight)] -> the host table of apz_ema_update (24-byte entries), shapes and layouts checked.  It holds
+    addresses: the tensors must stay alive and in place for as long as it is used."""
+    import numpy as np
+    tab = np.zeros(len(entries), dtype=_EMA_ENTRY)
+    f32 = _torch().float32
+    for i, (s, w) in enumerate(entries):
+        if not (s.is_cuda and w.is_cuda and s.dtype == f32 and w.dtype == f32):
+            raise ValueError("shadow %d: float32 device tensors" % i)
+        if s.shape != w.shape or not s.is_contiguous() or not w.is_contiguous():
+            raise ValueError("shadow %d: shape / layout mismatch" % i)
+        tab[i] = (s.data_ptr(), w.data_ptr(), w.numel())
+    return tab
+
+
 # why bits of the guard record (csrc/grad_guard.h)
 GUARD_GRAD, GUARD_LOSS, GUARD_SKIP_IN, GUARD_NORM = 1, 2, 4, 8
 

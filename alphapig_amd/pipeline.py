@@ -230,6 +230,26 @@ class TrainPipeline(object):
             if not (np.isfinite(self.clip_norm) and self.clip_norm > 0):
                 raise ValueError("clip_norm must be None or a finite positive number, not %r" % (conf.get("clip_norm"),))
         self.step_guard = bool(conf.get("step_guard", False)) or self.clip_norm is not None
+        # ema_decay / ema_warmup (default None / True): HipTrainer's averaged weights.  With ema_decay set, everything that
+        # leaves the trainer for play -- the weights the self-play evaluators receive, the arena's, the saved .model files --
+        # is the exponential moving average of the weights; the raw weights go on being trained, and every forward of the KL
+        # monitor runs on them.  With None, today's code paths run untouched.
+        from .train import check_ema_decay
+        self.ema_decay = check_ema_decay(conf.get("ema_decay"))
+        self.ema_warmup = bool(conf.get("ema_warmup", True))
+        if self.ema_decay is not None and trainer is not None:
+            # (a HipTrainer built without ema_decay has both names: ema_p is None and ema_params() raises)
+            keeps = (getattr(trainer, "ema_p", None) is not None or
+                     (not hasattr(trainer, "ema_p") and callable(getattr(trainer, "ema_params", None))))
+            if not keeps or (hasattr(trainer, "ema_decay") and trainer.ema_decay is None):
+                raise ValueError("ema_decay=%r needs a trainer that keeps averaged weights (ema_p / ema_params()); %r has "
+                                 "none" % (self.ema_decay, trainer))
+            own_kl_net = self.async_update and eval_net is not None and eval_net is not policy_value_net
+            if not own_kl_net and not hasattr(trainer, "policy_value"):
+                raise ValueError("ema_decay=%r: the self-play evaluator holds the averaged weights, so the KL monitor needs "
+                                 "a trainer with policy_value (its own evaluator on the raw weights), or eval_net on the "
+                                 "asynchronous schedule; %r has none" % (self.ema_decay, trainer))
+        self._kl_net_averaged = False           # the trainer thread's evaluator holds the average (an arena or a save put it there)
         if self.replay == "device":
             import torch
             if not torch.cuda.is_available():
@@ -254,6 +274,8 @@ class TrainPipeline(object):
         self._conf_match["train_framed"] = self.train_framed
         self._conf_match["step_guard"] = self.step_guard
         self._conf_match["clip_norm"] = self.clip_norm
+        self._conf_match["ema_decay"] = self.ema_decay
+        self._conf_match["ema_warmup"] = self.ema_warmup
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -392,12 +414,41 @@ class TrainPipeline(object):
             return self._trainer_override
         from .train import HipTrainer
         if getattr(net, "_trainer", None) is None:
+            if self.ema_decay is not None and self._train_steps > 0:
+                # none of this pipeline's own paths drops the trainer; an outside set_params on the evaluator does.  With
+                # ema_decay the evaluator holds the AVERAGE, so the new trainer's raw weights start from it
+                _logger.warning("the trainer was dropped (set_params on the self-play evaluator?): with ema_decay=%r the new "
+                                "trainer starts its raw weights, its moments and its average from the averaged weights "
+                                "the evaluator holds", self.ema_decay)
             # a re-created trainer (set_params dropped the old one) continues the dropout mask sequence instead of replaying it
             net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                       device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
                                       trunk_arith=self.train_arith, framed=self.train_framed, step_guard=self.step_guard,
-                                      clip_norm=self.clip_norm)
+                                      clip_norm=self.clip_norm, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         return net._trainer
+
+    # ---- the averaged weights (conf ema_decay): what plays is the average, what the KL monitor reads is the raw weights
+    def _ema_host(self, trainer):
+        """The trainer's averaged weights as host arrays"""
+        if hasattr(trainer, "ema_params"):
+            return trainer.ema_params()
+        return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in trainer.ema_p.items()}
+
+    def _install_average(self, trainer, net):
+        """The averaged weights into evaluator `net`: device to device where both sides can, else through the host"""
+        if hasattr(trainer, "sync_evaluator") and hasattr(trainer, "ema_p") and hasattr(net, "load_device_params"):
+            trainer.sync_evaluator(net, ema=True)
+        else:
+            net.set_params(self._ema_host(trainer), _keep_trainer=True)
+
+    def _average_for_play(self, trainer, net):
+        """Before an arena or a save on the trainer thread's evaluator: it gets the averaged weights, and the next update
+        puts the raw ones back before its first forward (policy_update).  The self-play evaluator already holds the average
+        (every installation carries it)."""
+        if self.ema_decay is None or net is self.policy_value_net:
+            return
+        self._install_average(trainer, net)
+        self._kl_net_averaged = True
 
     def _note_overflows(self, rec, trainer):
         """train_arith f16x2: the update record carries the trainer's count of steps repeated on the exact kernels;
@@ -411,6 +462,8 @@ class TrainPipeline(object):
             # json.dump would write the tokens NaN / Infinity, which strict JSON readers refuse)
             norm = getattr(trainer, "last_grad_norm", None)
             rec["grad_norm"] = float(norm) if norm is not None and np.isfinite(norm) else None
+        if self.ema_decay is not None:      # averaging steps applied so far (a skipped optimiser step is none)
+            rec["ema_updates"] = int(getattr(trainer, "ema_updates", 0))
 
     def _note_act_scale(self, rec):
         """Every round / batch record carries the self-play evaluator's count of forwards repeated on the exact kernel
@@ -435,14 +488,30 @@ class TrainPipeline(object):
     def policy_update(self, trainer=None, kl_net=None):
         """train_mxnet.py:194-240 (rank 0 of a multi-rank run; see `_exchange_update` / `_trainer_main`).  Lock step: the
         self-play evaluator itself supplies the old / new predictions of the KL monitor (re-folded per epoch);
-        asynchronous: the trainer thread's own evaluator `kl_net` does, and the self-play evaluator is left alone."""
+        asynchronous: the trainer thread's own evaluator `kl_net` does, and the self-play evaluator is left alone.
+        ema_decay: every forward of the KL monitor runs on the RAW weights.  Where the monitor's evaluator would be the
+        self-play evaluator (lock step), which holds the average, the trainer's own evaluator takes its place; the trainer
+        thread's `kl_net` gets the raw weights back first when an arena or a save left the average in it.  The caller
+        installs the average in the self-play evaluator."""
         mini = self.data_buffer.sample(self._rng, self.batch_size)
         net = self.policy_value_net if kl_net is None else kl_net
         trainer = self._trainer() if trainer is None else trainer
         t_before = getattr(trainer, "t", 0)
         mon = {}
+        if self.ema_decay is None:
+            evaluator = _KeepTrainer(net)
+        elif net is self.policy_value_net:
+            evaluator = None
+        else:
+            evaluator = _KeepTrainer(net)
+            if self._kl_net_averaged:
+                if hasattr(trainer, "sync_evaluator") and hasattr(net, "load_device_params"):
+                    trainer.sync_evaluator(net)
+                else:
+                    evaluator.set_params(trainer.get_params())
+                self._kl_net_averaged = False
         loss, entropy, kl, self.lr_multiplier = policy_update(trainer, mini, self.learn_rate, self.lr_multiplier,
-                                                              self.epochs, self.kl_targ, evaluator=_KeepTrainer(net), monitors=mon)
+                                                              self.epochs, self.kl_targ, evaluator=evaluator, monitors=mon)
         self._train_steps += max(0, getattr(trainer, "t", 0) - t_before)
         self.last_monitors = mon                          # train_mxnet.py:222-239: the value head's explained variance
         _logger.info("kl:%.4f lr:%.1e lr_multiplier:%.3f loss:%.4f entropy:%.4f explained_var_old:%.3f explained_var_new:%.3f",
@@ -461,6 +530,8 @@ class TrainPipeline(object):
             if do:
                 rec["loss"], rec["entropy"], rec["kl"] = self.policy_update()
                 self._note_overflows(rec, self._trainer())
+                if self.ema_decay is not None:      # the games that follow are played by the average
+                    self._install_average(self._trainer(), self.policy_value_net)
             return
         head = [0.0, 0.0, 0.0, 0.0, self.lr_multiplier]
         if do:
@@ -475,7 +546,12 @@ class TrainPipeline(object):
         net = self.policy_value_net
         if self.rank == 0:
             tr = self._trainer()
-            src = tr.p if hasattr(tr, "p") else tr.get_params()
+            if self.ema_decay is not None:
+                # the broadcast carries the average, and rank 0's own evaluator, which the KL monitor no longer touches, gets it too
+                src = tr.ema_p if (hasattr(tr, "ema_p") and hasattr(tr, "torch")) else self._ema_host(tr)
+                self._install_average(tr, net)
+            else:
+                src = tr.p if hasattr(tr, "p") else tr.get_params()
         else:
             src = self._param_template()
         got = dist.broadcast_params({k: src[k] for k in sorted(src)}, src=0)
@@ -635,6 +711,8 @@ class TrainPipeline(object):
         state = checkpoint.read_state(path)
         for k, mine in self._conf_match.items():
             theirs = state["conf"].get(k, False if k in ("train_framed", "step_guard") else None)   # (a checkpoint from before the key: off)
+            if k == "ema_warmup" and k not in state["conf"]:
+                continue                        # (from before the averaged weights: ema_decay, compared above, was off)
             if theirs != mine:
                 raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
                                  (path, k, theirs, k, mine))
@@ -680,12 +758,16 @@ class TrainPipeline(object):
             net.set_params({k: v for k, v in w.items() if k != "meta"}, _keep_trainer=True)
         else:
             weights = {k[2:]: v for k, v in tstate.items() if k.startswith("p/")}
+            if self.ema_decay is not None and any(k.startswith("e/") for k in tstate):
+                weights = {k[2:]: v for k, v in tstate.items() if k.startswith("e/")}       # what plays is the average
             if self.rank == 0 and (self._trainer_override is not None or not self.async_update):
                 tr = self._trainer()
                 if not hasattr(tr, "load_state"):
                     raise RuntimeError("resume needs a trainer with state() / load_state(); %r has none" % (tr,))
                 tr.load_state(tstate)
-                if hasattr(tr, "sync_evaluator") and hasattr(net, "load_device_params"):
+                if self.ema_decay is not None:
+                    self._install_average(tr, net)
+                elif hasattr(tr, "sync_evaluator") and hasattr(net, "load_device_params"):
                     tr.sync_evaluator(net)
                 else:
                     net.set_params(tr.get_params(), _keep_trainer=True)
@@ -696,6 +778,11 @@ class TrainPipeline(object):
         if "act_exponents" in state and hasattr(net, "set_trunk_act_exponents") and any(state["act_exponents"]):
             net.set_trunk_act_exponents(state["act_exponents"])
         self._async_resume = {"games_recv": state.get("games_recv", 0), "batches_done": state.get("trainer_batches_done", 0)}
+        if self.ema_decay is not None:
+            # the asynchronous schedule's trainer thread builds its evaluator from the self-play evaluator's weights, which are
+            # now the average (and one passed in holds whatever it held): the first update puts the raw weights into it
+            # before its first forward, as after an arena or a save
+            self._kl_net_averaged = True
         if self.async_update:
             self.weights_version = max(self.weights_version, int(self.updates_done))   # (versions count updates; the evaluator holds the trainer's)
         _logger.info("resumed from %s: next batch %d, %d games taken so far", path, self._batches_done, self._taken)
@@ -724,13 +811,16 @@ class TrainPipeline(object):
             if time.perf_counter() >= t_end:
                 return
 
-    def _schedule_after_batch(self, i, rec, net, first=None):
+    def _schedule_after_batch(self, i, rec, net, first=None, trainer=None):
         """The reference's per-batch schedule behind the update (train_mxnet.py:283-298): checkpoint every 50 batches,
         arena every check_freq.  i = 0-based game-batch index.  `first` (asynchronous schedule): the update covered the
         game batches first ... i (a cluster of games finished in one round); the weights are the same for all of them, so a
-        checkpoint / an arena evaluation runs ONCE if the range crosses a multiple, not once per skipped index."""
+        checkpoint / an arena evaluation runs ONCE if the range crosses a multiple, not once per skipped index.
+        ema_decay: the saved model and the arena's player are the averaged weights of `trainer`."""
         lo = i if first is None else first
         crosses = lambda m: (i + 1) // m > lo // m          # some k in (lo, i + 1] is a multiple of m
+        if trainer is not None and (crosses(50) or crosses(self.check_freq)):
+            self._average_for_play(trainer, net)
         if crosses(50):
             os.makedirs(self.model_dir, exist_ok=True)
             net.save_model(os.path.join(self.model_dir, "current_policy.model"))
@@ -771,7 +861,8 @@ class TrainPipeline(object):
                 if trainer is None:
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                          device_index=net._device, seed=self._seed, trunk_arith=self.train_arith,
-                                         framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm)
+                                         framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm,
+                                         ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
                 self._async_trainer = trainer
                 tstate = getattr(self, "_async_trainer_state", None)
                 if tstate is not None:                  # resume=: the trainer this thread built continues the saved one
@@ -805,7 +896,7 @@ class TrainPipeline(object):
                             self._fresh = (self.updates_done, snap)
                         rec.update(loss=loss, entropy=entropy, kl=kl)
                         self._note_overflows(rec, trainer)
-                    self._schedule_after_batch(i, rec, kl_net)
+                    self._schedule_after_batch(i, rec, kl_net, trainer=trainer)
                     with self._lock:
                         self.trainer_history.append(rec)
                 self._sgf_done.set()
@@ -860,7 +951,7 @@ class TrainPipeline(object):
                             self._fresh = (self.updates_done, snap)
                         rec.update(loss=loss, entropy=entropy, kl=kl)
                         self._note_overflows(rec, trainer)
-                    self._schedule_after_batch(batches_done - 1, rec, kl_net, first=first)
+                    self._schedule_after_batch(batches_done - 1, rec, kl_net, first=first, trainer=trainer)
                     with self._lock:
                         self.trainer_history.append(rec)
         except BaseException as e:          # surfaces in the main thread at the next round (or in the bootstrap hold)
@@ -872,9 +963,12 @@ class TrainPipeline(object):
         return min(int(self.sgf_batches), int(self.game_batch_num)) if self._training_data else 0
 
     def _snapshot(self, trainer):
-        """A private copy of the trainer's weights for the main thread to broadcast / load while the trainer goes on."""
+        """A private copy of the trainer's weights for the main thread to broadcast / load while the trainer goes on
+        (ema_decay: of its averaged weights)."""
+        if self.ema_decay is not None and not (hasattr(trainer, "ema_p") and hasattr(trainer, "torch")):
+            return dict(self._ema_host(trainer))
         if hasattr(trainer, "p") and hasattr(trainer, "torch"):
-            snap = {k: v.clone() for k, v in trainer.p.items()}
+            snap = {k: v.clone() for k, v in (trainer.p if self.ema_decay is None else trainer.ema_p).items()}
             trainer.torch.cuda.current_stream(trainer.device).synchronize()
             return snap
         return trainer.get_params()

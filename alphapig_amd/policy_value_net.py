@@ -62,7 +62,7 @@ class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
                  uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0, train_framed=False,
-                 train_step_guard=False, train_clip_norm=None):
+                 train_step_guard=False, train_clip_norm=None, ema_decay=None, ema_warmup=True):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -92,8 +92,13 @@ class PolicyValueNet(object):
                    arithmetic a batch gets is that of 8 n boards (five positions under "auto": a 40-board f16x2 forward).
         forward_planes / policy_value (the KL monitor, calibrate_trunk, prewarm) are not concerned.
         train_step_guard / train_clip_norm: HipTrainer's step_guard / clip_norm for the trainer train_step builds -- a step
-        whose gradients or losses are not finite is skipped instead of reaching the weights; global-norm clipping."""
+        whose gradients or losses are not finite is skipped instead of reaching the weights; global-norm clipping.
+        ema_decay / ema_warmup: HipTrainer's averaged weights for the trainer train_step builds (ema_params() hands them
+        out); this net's own evaluator keeps the RAW weights after train_step, as the reference's predict-module re-sync
+        does."""
         check_leaf_symmetry(leaf_symmetry)
+        from .train import check_ema_decay
+        self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         self.L = _native.hip()
         self.board_width, self.board_height = int(board_width), int(board_height)
         self.batchsize = int(batch_size)
@@ -435,10 +440,17 @@ class PolicyValueNet(object):
         if getattr(self, "_trainer", None) is None:
             self._trainer = HipTrainer(self.params(), self.net_kind, self._n_blocks, batch_size=self.batchsize,
                                        device_index=self._device, framed=self.train_framed,
-                                       step_guard=self.train_step_guard, clip_norm=self.train_clip_norm)
+                                       step_guard=self.train_step_guard, clip_norm=self.train_clip_norm,
+                                       ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         loss, entropy = self._trainer.train_step(state_batch, mcts_probs, winner_batch, learning_rate)
         self._trainer.sync_evaluator(self)
         return np.array([loss], dtype=np.float32), np.array([entropy], dtype=np.float32)
+
+    def ema_params(self):
+        """The averaged weights of this net's trainer as host arrays (HipTrainer.ema_params); None before a trainer exists
+        (no train_step yet, or set_params dropped it)."""
+        tr = getattr(self, "_trainer", None)
+        return None if tr is None else tr.ema_params()
 
     # ---- measurement hooks
     def conv_bench(self, layer, n, iters=100, warmup=20):

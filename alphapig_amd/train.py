@@ -17,6 +17,9 @@ the self-play path.  The module needs the HIP library and a GPU; without them co
   guard     opt-in (step_guard / clip_norm; csrc/grad_guard.h): the global gradient norm taken on the device in front of
             Adam, global-norm clipping inside Adam's rescale factor, and a step whose gradients or losses are not finite
             skipped on the device -- weights, moments, moving statistics and t as if it had not been asked for
+  average   opt-in (ema_decay; csrc/ema.h): an exponential moving average of every parameter and statistic in a shadow copy
+            on the device, moved by one launch behind every Adam launch under that launch's skip rule -- what self-play, the
+            arena and the saved models of TrainPipeline read while the raw weights go on being trained
 
 The 10-block / 128-filter / 15x15 network keeps its trunk activations in the self-play kernels' padded-row layout
 [n][128][15][16] from the stem's BatchNorm to the heads (forward and data gradient on the fused Winograd kernel of
@@ -40,6 +43,28 @@ DeviceBatch = collections.namedtuple("DeviceBatch", "states pis zs")     # HipTr
 # and 1 / std of each BatchNorm, k: its ReLU decisions as a bit mask, padded rows only)
 ConvAct = collections.namedtuple("ConvAct", "name x y a mean invstd layout")
 Block = collections.namedtuple("Block", "x ya ha ma ia yb out mb ib ka kb")
+
+
+def check_ema_decay(ema_decay):
+    """-> None or a float; ValueError unless ema_decay is None or a finite number with 0 < d < 1.  Needs no GPU."""
+    if ema_decay is None:
+        return None
+    try:
+        d = float(ema_decay)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if not (np.isfinite(d) and 0.0 < d < 1.0):
+        raise ValueError("ema_decay must be None or a finite number with 0 < ema_decay < 1, not %r" % (ema_decay,))
+    return d
+
+
+def ema_coefficient(decay, n, warmup):
+    """The coefficient c of the averaged weights' step s = s + c * (w - s) (csrc/ema.h) after n steps have been applied ->
+    np.float32.  warmup: the decay rises as (1 + n) / (10 + n) until it reaches `decay` (0.1, 0.18, 0.25, ...: the first
+    steps move the average most of the way, so it does not sit on the initial weights for 1 / (1 - decay) steps).  Computed
+    in Python floats and rounded once."""
+    decay_t = min(float(decay), (1.0 + n) / (10.0 + n)) if warmup else float(decay)
+    return np.float32(1.0 - decay_t)
 
 
 TRAINABLE_SIDES = (15, 8)
@@ -81,7 +106,7 @@ def check_trainable_board(params, framed=False, net_kind="resnet", trunk_arith="
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
                  seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False, step_guard=False,
-                 clip_norm=None):
+                 clip_norm=None, ema_decay=None, ema_warmup=True):
         """params: name -> array, in any order.  height / width: the board (default: square, from the policy head's size).
         seed / dropout_step0: the dropout masks are a stateless hash of (seed, dropout_step0 + step, element) -- a trainer
         that is re-created (set_params, a resumed checkpoint) or one of several ranks passes its own seed / the steps
@@ -106,13 +131,22 @@ class HipTrainer(object):
         step's bits.  On "f16x2" the overflow word is one more reason to skip: the step is repeated on the exact kernels as
         always, and the repeat is guarded in turn.
         clip_norm: None, or a finite positive number -- global-norm clipping (implies step_guard): a step whose gradient
-        norm exceeds it has its gradient scaled to that norm (clipped_steps), inside Adam's rescale factor."""
+        norm exceeds it has its gradient scaled to that norm (clipped_steps), inside Adam's rescale factor.
+        ema_decay: None (default: nothing is allocated and nothing launched), or a finite number in (0, 1) -- the averaged
+        weights (csrc/ema.h): ema_p, a shadow of every tensor of p (statistics and pinned gammas included), starts as a copy
+        of p and follows it by ema_p += c * (p - ema_p), c = ema_coefficient(ema_decay, ema_updates, ema_warmup), in one
+        launch queued directly behind every Adam launch of train_step with that launch's skip condition: a step that was
+        skipped (the guard's verdict) or repeated (an f16x2 overflow) moves the average exactly as often as it moved the
+        weights.  ema_updates counts the steps applied, from the read-back the step makes anyway.  The raw weights, the
+        moments and the losses are those of a trainer without it, bit for bit: the launch only reads them.
+        ema_params() / sync_evaluator(net, ema=True) hand the average out."""
         if trunk_arith not in ("f32", "f16x2"):
             raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
         if clip_norm is not None:
             clip_norm = float(clip_norm)
             if not (np.isfinite(clip_norm) and clip_norm > 0):
                 raise ValueError("clip_norm must be None or a finite positive number, not %r" % (clip_norm,))
+        ema_decay = check_ema_decay(ema_decay)
         if "fc_3_1_1_bias" in params:
             # before anything touches the GPU: today's failure would come from the first step
             check_trainable_board(params, framed, net_kind, trunk_arith)
@@ -212,6 +246,21 @@ class HipTrainer(object):
             self._word = torch.zeros((8 if self.step_guard else 4,), dtype=torch.float32, device=self.device)
             self._flag = self._word[3:4]
             self._record = self._word[4:8] if self.step_guard else None
+        # the averaged weights (csrc/ema.h): a shadow of every tensor of p, in p's order, as views of ONE flat buffer (a
+        # broadcast sends one piece) -- allocated last, when every tensor of p has moved to where it stays
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema_updates = 0           # averaging steps applied (a skipped step is none)
+        self.ema_p = None
+        if ema_decay is not None:
+            self._ema_buf = torch.empty((sum(v.numel() for v in self.p.values()),), dtype=torch.float32, device=self.device)
+            self.ema_p = collections.OrderedDict()
+            off = 0
+            for k, v in self.p.items():
+                self.ema_p[k] = self._ema_buf[off:off + v.numel()].view(v.shape)
+                self.ema_p[k].copy_(v)
+                off += v.numel()
+            # (the launch's table, once: from here on the tensors of p and ema_p are only ever written INTO)
+            self._ema_tab = hipconv.ema_table([(self.ema_p[k], self.p[k]) for k in self.p])
         self._eval = None
         self._eval_t = -1
         self.tape = None
@@ -492,8 +541,10 @@ class HipTrainer(object):
             batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=self._word[:3])
             self.t += 1
             self._adam(learning_rate, skip=self._flag)      # skipped on the device when the overflow word is set
+            self._ema(skip=self._flag)         # (and the average with it)
             w4 = self._word.cpu().numpy()      # the losses and the overflow word: still the step's only synchronisation
             if w4[3:].view(np.uint32)[0] == 0:
+                self._ema_applied()
                 return float(w4[0] + w4[1]), float(w4[2])
             self.t -= 1
             loss3 = self._repeat_exact(batch, keep_tape)
@@ -501,6 +552,8 @@ class HipTrainer(object):
             loss3 = self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
         self.t += 1
         self._adam(learning_rate)
+        self._ema()
+        self._ema_applied()
         l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
         return float(l3[0] + l3[1]), float(l3[2])
 
@@ -512,6 +565,7 @@ class HipTrainer(object):
             batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=loss3)
             self.t += 1
             self._adam(learning_rate, skip=self._flag, guarded=True)      # (the overflow word is one of the guard's reasons)
+            self._ema(skip=self._record[2:3])  # the record's skip word: the overflow bit is among its reasons
             w8 = self._word.cpu().numpy()
             if w8[3:4].view(np.uint32)[0] != 0:
                 # overflowed: nothing reached Adam.  The exact repeat as always (the snapshot still holds the statistics at
@@ -520,6 +574,7 @@ class HipTrainer(object):
                 self._repeat_exact(batch, keep_tape, loss3=loss3)
                 self.t += 1
                 self._adam(learning_rate, guarded=True)
+                self._ema(skip=self._record[2:3])       # (the repeat's record)
                 w8 = self._word.cpu().numpy()
         else:
             batch = state_batch if isinstance(state_batch, DeviceBatch) else self.upload(state_batch, mcts_probs, winner_batch)
@@ -527,6 +582,7 @@ class HipTrainer(object):
             self._loss_and_grads(batch, keep_tape=keep_tape, loss3=loss3)
             self.t += 1
             self._adam(learning_rate, guarded=True)
+            self._ema(skip=self._record[2:3])
             w8 = self._word.cpu().numpy()      # the losses and the record: still the step's only synchronisation
         norm, eff, skip, why = self.ops.read_guard_record(w8[4:8])
         self.last_grad_norm, self.last_rescale_eff = norm, eff
@@ -535,8 +591,10 @@ class HipTrainer(object):
             self._stat_buf.copy_(self._stat_snap)
             self.t -= 1                 # (the next step draws this step's dropout masks; the internal evaluator is not stale)
             self.skipped_steps += 1
-        elif eff != np.float32(1.0 / self.batch_size):
-            self.clipped_steps += 1
+        else:
+            self._ema_applied()
+            if eff != np.float32(1.0 / self.batch_size):
+                self.clipped_steps += 1
         return float(w8[0] + w8[1]), float(w8[2])
 
     def _entries(self):
@@ -552,6 +610,25 @@ class HipTrainer(object):
         else:
             self.ops.adam_step(self._entries(), lr_t, b1, b2, eps, 1.0 / self.batch_size, self.device, skip=skip)
 
+    def _ema(self, skip=None):
+        """The averaged weights' launch behind an Adam launch (nothing without ema_decay).  skip: that Adam launch's skip
+        word.  The coefficient belongs to ema_updates as it stands: a launch that skips on the device is followed by one
+        with the same coefficient."""
+        if self.ema_p is None:
+            return
+        c = ema_coefficient(self.ema_decay, self.ema_updates, self.ema_warmup)
+        self.ops.ema_update(self._ema_tab, c, self.device, skip=skip)
+
+    def _ema_applied(self):
+        if self.ema_p is not None:
+            self.ema_updates += 1
+
+    def ema_params(self):
+        """The averaged weights as host arrays, in get_params()'s order (ValueError without ema_decay)"""
+        if self.ema_p is None:
+            raise ValueError("this trainer keeps no averaged weights (ema_decay=None)")
+        return collections.OrderedDict((k, v.cpu().numpy()) for k, v in self.ema_p.items())
+
     def grad_norm(self):
         """The global norm of self.grad after a loss_and_grads, as the guard measures it: of grad / batch_size, the gradient
         Adam sees before weight decay -- the scale clip_norm is compared with.  Two launches and a read-back (a
@@ -561,11 +638,14 @@ class HipTrainer(object):
         rec = self.ops.grad_norm(self._entries(), 1.0 / self.batch_size, None, self.device)
         return self.ops.read_guard_record(rec.cpu().numpy())[0]
 
-    def sync_evaluator(self, net):
+    def sync_evaluator(self, net, ema=False):
         """Give `net` (a PolicyValueNet of the same architecture) this trainer's current weights, device to device:
-        folding and packing run as kernels behind the optimiser step on the same stream (apz_load_weights_dev)."""
+        folding and packing run as kernels behind the optimiser step on the same stream (apz_load_weights_dev).
+        ema=True: the averaged weights instead (ValueError without ema_decay)."""
+        if ema and self.ema_p is None:
+            raise ValueError("this trainer keeps no averaged weights (ema_decay=None)")
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        net.load_device_params(self.p, stream)
+        net.load_device_params(self.ema_p if ema else self.p, stream)
 
     def policy_value(self, state_batch):
         """Inference-mode (moving statistics) probabilities and values for the KL monitor: the self-play path's own
@@ -597,13 +677,17 @@ class HipTrainer(object):
         """Everything the next train_step reads, as host values: {"meta": t, dropout_step0, seed, trunk_overflows, the guard's
         two settings and two counters and the net's kind (the dropout masks are keyed by seed and dropout_step0 + t),
         "p/<name>": every parameter and BatchNorm statistic, "m/<name>" / "v/<name>": Adam's moments} -- what load_state
-        takes."""
+        takes.  With ema_decay: "e/<name>", the averaged weights, and meta's ema_decay, ema_warmup and ema_updates."""
         out = {"meta": {"t": int(self.t), "dropout_step0": int(self.dropout_step0), "seed": int(self.seed),
                         "trunk_overflows": int(self.trunk_overflows), "net_kind": self.kind, "n_blocks": int(self.n_blocks),
                         "trunk_arith": self.trunk_arith, "framed": self.framed, "step_guard": self.step_guard,
                         "clip_norm": self.clip_norm, "skipped_steps": int(self.skipped_steps),
                         "clipped_steps": int(self.clipped_steps)}}
-        for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
+        groups = [("p", self.p), ("m", self.m), ("v", self.v)]
+        if self.ema_p is not None:
+            out["meta"].update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=int(self.ema_updates))
+            groups.append(("e", self.ema_p))
+        for tag, group in groups:
             for k, t in group.items():
                 out["%s/%s" % (tag, k)] = t.cpu().numpy()
         return out
@@ -612,7 +696,9 @@ class HipTrainer(object):
         """Continue where the trainer that returned `state` stood (same net: names and shapes are checked before anything
         is written).  The values are copied INTO the existing tensors: the trunk weights, biases and statistics are views
         into the packed buffers the kernels read.  The internal evaluator is stale afterwards and re-synchronises on its
-        next use."""
+        next use.  The averaged weights: a state that holds them ("e/<name>") continues them in a trainer built with
+        ema_decay and is read without them by one built without; a state that holds none starts the average of a trainer
+        built with ema_decay at the loaded weights, ema_updates = 0."""
         meta = state["meta"]
         if meta["net_kind"] != self.kind or int(meta["n_blocks"]) != self.n_blocks:
             raise ValueError("this trainer state belongs to a %s net of %s blocks" % (meta["net_kind"], meta["n_blocks"]))
@@ -620,7 +706,11 @@ class HipTrainer(object):
             raise ValueError("this trainer state was written with framed=%s, the trainer was built with framed=%s" %
                              (bool(meta.get("framed", False)), self.framed))
         todo = []
-        for tag, group in (("p", self.p), ("m", self.m), ("v", self.v)):
+        groups = [("p", self.p), ("m", self.m), ("v", self.v)]
+        with_ema = self.ema_p is not None and any(k.startswith("e/") for k in state)
+        if with_ema:
+            groups.append(("e", self.ema_p))
+        for tag, group in groups:
             for k, t in group.items():
                 a = state.get("%s/%s" % (tag, k))
                 if a is None or tuple(np.shape(a)) != tuple(t.shape):
@@ -628,6 +718,9 @@ class HipTrainer(object):
                 todo.append((t, np.ascontiguousarray(a, dtype=np.float32)))
         for t, a in todo:
             t.copy_(self.torch.from_numpy(a))
+        if self.ema_p is not None and not with_ema:
+            for k, t in self.ema_p.items():
+                t.copy_(self.p[k])
         self.torch.cuda.current_stream(self.device).synchronize()
         self.t = int(meta["t"])
         self.dropout_step0 = int(meta["dropout_step0"])
@@ -637,6 +730,8 @@ class HipTrainer(object):
         # state's own step_guard / clip_norm say what the run that wrote it did.)
         self.skipped_steps = int(meta.get("skipped_steps", 0))
         self.clipped_steps = int(meta.get("clipped_steps", 0))
+        if self.ema_p is not None:
+            self.ema_updates = int(meta.get("ema_updates", 0)) if with_ema else 0
         self._eval_t = -1
         self.tape = None
 

@@ -308,6 +308,20 @@ int apz_grad_norm(apz_engine *e, const void *table_host, int ntensors, float res
 int apz_adam_step_guarded(apz_engine *e, const void *table_host, int ntensors, float lr_t, float b1, float b2, float eps,
                           float rescale, float clip, const void *loss3_dev, const void *skip_in_dev, void *record_dev,
                           void *stream);
+/* The trainer's averaged weights (csrc/ema.h; HipTrainer(ema_decay=...)): one launch over ntensors pairs of device tensors,
+ * grid (32, ntensors) x 256 like apz_adam_step.  table_host: ntensors entries { float *s; const float *w; int64 n; }
+ * (24 bytes) in HOST memory -- s the shadow (the average), w the weight, n floats each.  Per element, for a reader who
+ * wants the bits:
+ *     d = w - s;  p = c * d;  s = s + p      three float32 operations, each rounded to nearest even on its own
+ * never a fused multiply-add (the kernel is compiled with floating-point contraction off, by pragma and by the build's
+ * -ffp-contract=off): the NumPy float32 expression s + c * (w - s) gives the same bits.  w == s leaves the value as
+ * it is (w - s = +0).  Only s is written, element by element: s and w may start anywhere on the float grid.
+ * skip_a_dev / skip_b_dev (each may be NULL): 32-bit device words; when either is not zero at the time the launch runs,
+ * nothing is written (the f16x2 overflow word, or the skip word at byte 8 of apz_grad_norm's record -- the launch queued
+ * behind an Adam launch skips exactly when that one did).  Arguments are checked as apz_adam_step's and the table travels
+ * the same way, except that ntensors = 0 is accepted and launches nothing; no stream synchronisation. */
+int apz_ema_update(apz_engine *e, const void *table_host, int ntensors, float c, const void *skip_a_dev,
+                   const void *skip_b_dev, void *stream);
 int apz_bn_bwd_splits(apz_engine *e, int n, int C, int layout);
 int apz_colsum(apz_engine *e, const void *in_dev, void *out_dev, int rows, int cols, float scale, void *stream);
 

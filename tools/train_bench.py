@@ -5,7 +5,9 @@ trainer is tested against), 10-block net, 15x15.  --arith f32,f16x2: the product
 (HipTrainer trunk_arith), the two alternating --reps times on the same box, step times side by side.  --side 15,9,13: the
 product trainer per board side (framed sides: HipTrainer framed=True), alternating in one process in the same way, each
 side's step time and its ratio to the first.  --step-guard: the product trainer without and with the guarded optimiser step
-(HipTrainer step_guard; --clip-norm adds clipping), alternating in the same way, per --arith arithmetic (default f32)."""
+(HipTrainer step_guard; --clip-norm adds clipping), alternating in the same way, per --arith arithmetic (default f32).
+--ema: the product trainer without and with the averaged weights (HipTrainer ema_decay; --ema-decay), alternating in the same
+way, and the averaging launch on its own between two events."""
 import argparse
 import json
 import os
@@ -33,12 +35,16 @@ def main():
     ap.add_argument("--side", default=None, help="comma list of board sides (15 and framed sides 6, 7, 9, 11 .. 14): alternating runs")
     ap.add_argument("--step-guard", action="store_true", help="HipTrainer step_guard off / on: alternating runs")
     ap.add_argument("--clip-norm", type=float, default=None, help="--step-guard: the guarded trainer's clip_norm")
+    ap.add_argument("--ema", action="store_true", help="HipTrainer ema_decay off / on: alternating runs")
+    ap.add_argument("--ema-decay", type=float, default=0.999, help="--ema: the averaging trainer's ema_decay")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
     out = {}
     if args.side:
         return side_ab(args, rs)
+    if args.ema:
+        return ema_ab(args, prm, rs)
     if args.step_guard:
         return guard_ab(args, prm, rs)
     if args.arith:
@@ -151,6 +157,58 @@ def guard_ab(args, prm, rs):
                   "   ".join("%s %.3f ms/step (runs %s)" % (k, med[k], ", ".join("%.3f" % x for x in times[k])) for k in trs) +
                   "   ratio guarded/plain %.4f   grad_norm %.4g skipped %d clipped %d" %
                   (med["guarded"] / med["plain"], g.last_grad_norm, g.skipped_steps, g.clipped_steps), flush=True)
+            for tr in trs.values():
+                tr.close()
+    print(json.dumps(out))
+
+
+def ema_ab(args, prm, rs):
+    """The step without and with the averaged weights per batch size (and --arith arithmetic), alternating like guard_ab: one
+    trainer each from the same weights, `--reps` rounds of (warm-up step, `--steps` timed steps on an uploaded mini-batch) in
+    turn; the median step time of each and all runs (their spread is the yardstick for the difference).  Then the averaging
+    launch alone: 100 launches between two events, `--reps` times -- back to back, so the 25 MB it reads and the 12.7 MB it
+    writes may still sit in the last-level cache from the launch before; behind a training step they come from HBM."""
+    import torch
+    out = {}
+    for B in [int(x) for x in args.batches.split(",")]:
+        states = (rs.rand(B, 9, 15, 15) > 0.7).astype(np.float32)
+        pis = rs.dirichlet(np.ones(225), size=B).astype(np.float32)
+        zs = rs.choice([-1.0, 1.0], size=B).astype(np.float32)
+        for a in (args.arith or "f32").split(","):
+            trs = {"plain": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a),
+                   "ema": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a, ema_decay=args.ema_decay)}
+            batches = {k: tr.upload(states, pis, zs) for k, tr in trs.items()}
+            times = {k: [] for k in trs}
+            for _ in range(args.reps):
+                for k, tr in trs.items():
+                    tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    for _ in range(args.steps):
+                        tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    times[k].append(1e3 * (time.perf_counter() - t) / args.steps)
+            med = {k: float(np.median(times[k])) for k in trs}
+            e = trs["ema"]
+            launch_us = []
+            for _ in range(args.reps):
+                e._ema()
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for _ in range(100):
+                    e._ema()
+                t1.record()
+                torch.cuda.synchronize()
+                launch_us.append(1e3 * t0.elapsed_time(t1) / 100)
+            for k in trs:
+                out["B%d_%s_%s" % (B, a, k)] = {"ms_per_step": med[k], "runs_ms": [round(x, 3) for x in times[k]]}
+            nbytes = 12 * sum(v.numel() for v in e.p.values())
+            out["B%d_%s_ema" % (B, a)].update(ema_updates=e.ema_updates, launch_us=[round(x, 2) for x in launch_us],
+                                              launch_bytes=nbytes)
+            print("batch %4d %-5s  " % (B, a) +
+                  "   ".join("%s %.3f ms/step (runs %s)" % (k, med[k], ", ".join("%.3f" % x for x in times[k])) for k in trs) +
+                  "   ratio ema/plain %.4f   launch alone %s us (%.1f MB moved)   ema_updates %d" %
+                  (med["ema"] / med["plain"], ", ".join("%.2f" % x for x in launch_us), nbytes / 1e6, e.ema_updates), flush=True)
             for tr in trs.values():
                 tr.close()
     print(json.dumps(out))
