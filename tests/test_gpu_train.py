@@ -1,8 +1,12 @@
 """The training graph's HIP operators (alphapig_amd/hipconv.py over include/alphapig_hip.h) against
 torch float64 autograd on the same tensors, and the product trainer (alphapig_amd/train.py: explicit forward / backward
 on those operators, no autograd) against the PyTorch comparator tests/torch_trainer.py."""
+import time
+
 import numpy as np
 import pytest
+
+import generic_nets as gn
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -26,6 +30,13 @@ def pad16(t):
                                         (200, 128, 128, 15)])
 def test_conv3x3_fwd_dgrad_wgrad_bias(n, ci, co, hw):
     """Dense tensors: direct MFMA kernel, and from 192 boards of the trunk shape the Winograd kernel."""
+    _conv3x3_against_float64(n, ci, co, hw)
+
+
+def _conv3x3_against_float64(n, ci, co, hw, sum_growth=1.0):
+    """conv3x3_fwd (plain and with ReLU), conv3x3_wgrad, bias_grad and, for 64 / 128 / 256 input channels, conv3x3_dgrad
+    (plain and with `add`) against float64 autograd.  sum_growth: the factor on the bar of the two gradients that are sums
+    over n * hw * hw terms (1 up to the longest sum of the first list, 200 * 225).  -> {quantity: error / bar}"""
     from alphapig_amd import hipconv
     g = torch.Generator().manual_seed(n * 1000 + ci + co)
     x = torch.randn(n, ci, hw, hw, generator=g)
@@ -44,16 +55,55 @@ def test_conv3x3_fwd_dgrad_wgrad_bias(n, ci, co, hw):
     dw = hipconv.conv3x3_wgrad(xc, dyc)
     db = hipconv.bias_grad(dyc)
     torch.cuda.synchronize()
-    assert err(y, y64) < tol(y64)
-    assert err(dw, w64.grad) < 5 * tol(w64.grad)
-    assert err(db, b64.grad) < 5 * tol(b64.grad)
+    got = {"fwd": (err(y, y64), tol(y64)), "wgrad": (err(dw, w64.grad), 5 * sum_growth * tol(w64.grad)),
+           "bias_grad": (err(db, b64.grad), 5 * sum_growth * tol(b64.grad))}
     yr = hipconv.conv3x3_fwd(xc, wc, bc, relu=True)
-    assert err(yr, torch.relu(y64)) < tol(y64)
+    got["fwd_relu"] = (err(yr, torch.relu(y64)), tol(y64))
     if need_dx:
         dx = hipconv.conv3x3_dgrad(dyc, wc)
-        assert err(dx, x64.grad) < tol(x64.grad)
+        got["dgrad"] = (err(dx, x64.grad), tol(x64.grad))
         dx2 = hipconv.conv3x3_dgrad(dyc, wc, add=skip.cuda())
-        assert err(dx2, x64.grad + skip.double()) < tol(x64.grad)
+        got["dgrad_add"] = (err(dx2, x64.grad + skip.double()), tol(x64.grad))
+    ratio = {k: e / bar for k, (e, bar) in got.items()}
+    print((n, ci, co, hw), {k: "%.4f" % v for k, v in ratio.items()})
+    for k, (e, bar) in got.items():
+        assert e < bar, (k, e, bar)
+    return ratio
+
+
+# (n as a multiple of the CU count plus one, C_in, C_out, side): what the case is there for
+DIRECT_ABOVE_GRID = {"one_tile": (1, 256, 64, 8), "two_tiles": (1, 256, 128, 8), "four_tiles": (1, 256, 256, 8),
+                     "two_chunks": (1, 256, 64, 15), "full_tile": (1, 128, 64, 15), "stem": (4, 9, 64, 8),
+                     "stem15": (4, 9, 64, 15)}     # (9 * 225 is odd: the only input whose alignment head is not 0 on every board)
+LONGEST_SUM = 200 * 225          # the longest weight-gradient sum of test_conv3x3_fwd_dgrad_wgrad_bias's list
+DIRECT_TABLE = gn.Table("r25_direct_operator")
+
+
+@pytest.mark.parametrize("case", sorted(DIRECT_ABOVE_GRID))
+def test_conv3x3_direct_above_its_grid_and_in_its_wide_forms(case):
+    """conv3x3_mfma_kernel is persistent: grid = min(n, CUs * per_cu) workgroups, each taking boards b, b + grid, ...  The list
+    above never has more boards than the grid and always ends at one 64-channel tile per workgroup (apz_conv3x3_fwd's
+    `groups` rule), so the second trip of the board loop -- the barrier in front of the restaged tile, the pad channels and
+    halo cells zeroed once before the loop, the 16-byte alignment head that changes from board to board (9 planes of 225
+    cells: case stem15), the two LDS chunks of 256 channels at 15x15 -- and the 2- and 4-tile template forms ran nowhere.
+    Here every case has one board more than its grid; the predicate it rests on is restated from the device's CU count
+    (tests/generic_nets.py) and asserted.  Bars: the file's `tol` on the forward and the data gradient (an output
+    element's error does not depend on n); 5 * tol on the weight and bias gradient up to the list's longest sum
+    (200 * 225 terms), times sqrt(terms / 45 000) above it: the random-walk growth of rounding error in a sum."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    mult, ci, co, hw = DIRECT_ABOVE_GRID[case]
+    n = mult * cus + 1
+    f = gn.operator_form(n, ci, co, hw, cus)
+    assert f.groups == 1 and f.ct == co // 64 and f.per_cu == mult and f.grid == mult * cus and f.grid < n, f
+    assert f.chunks == (2 if case == "two_chunks" else 1), f
+    terms = n * hw * hw
+    growth = max(1.0, float(np.sqrt(terms / float(LONGEST_SUM))))
+    t0 = time.time()
+    ratio = _conv3x3_against_float64(n, ci, co, hw, growth)
+    back = gn.operator_form(n, co, ci, hw, cus) if ci >= 64 else None
+    DIRECT_TABLE.add(case=case, shape=[n, ci, co, hw], forward_form=gn.form_name(f),
+                     dgrad_form=gn.form_name(back) if back else None, sum_terms=terms, sum_growth=growth,
+                     err_over_bar=ratio, seconds=round(time.time() - t0, 3))
 
 
 @pytest.mark.parametrize("n", [1, 6, 64, 131])
