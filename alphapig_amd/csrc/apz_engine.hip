@@ -151,7 +151,7 @@ struct DeviceBuffer {
     }
     template <class T>
     T* as() const { return (T*)ptr; }
-    operator void*() const { return ptr; }   // (hipMemcpyAsync(e->adam_tab, ...): a copy's error text names the buffer as before)
+    operator void*() const { return ptr; }
     void release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
@@ -2275,6 +2275,23 @@ int apz_wgrad_wino_f16x2(apz_engine* e, const void* x_dev, const void* dy_dev, v
                                              stream, (const float*)dymax_dev, dymax_count, (unsigned*)flag_dev);
 }
 
+extern "C++" {
+namespace {
+// A host table of `count` T (the optimiser's and the average's tensor entries, the gather's entry words) into the device
+// buffer the next launch reads it from, inside a train_call -> *dev.  Stream-ordered: the copy queues behind the previous
+// launch that read the same buffer, and for pageable host memory hipMemcpyAsync returns once the few KB have been staged, so
+// the caller's table need not outlive the call.  (No stream synchronisation: the optimiser step does not drain the GPU.)
+template <class T>
+int upload_table(apz_engine* e, DeviceBuffer& buf, const void* table_host, int count, const T** dev) {
+    const size_t bytes = (size_t)count * sizeof(T);
+    if (int rc = buf.reserve(bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(buf, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+    *dev = buf.as<const T>();
+    return APZ_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
                   float rescale, void* stream) {
     return apz_adam_step_unless(e, table_host, ntensors, lr_t, b1, b2, eps, rescale, nullptr, stream);
@@ -2285,13 +2302,8 @@ int apz_adam_step_unless(apz_engine* e, const void* table_host, int ntensors, fl
     if (!e || !table_host || ntensors < 1 || ntensors > 4096) return fail(APZ_E_ARG, "bad argument");
     static_assert(sizeof(apz::AdamTensor) == 48, "apz_adam_tensor layout");
     return train_call(e, stream, [&]() -> int {
-        const size_t bytes = (size_t)ntensors * sizeof(apz::AdamTensor);
-        if (int rc = e->adam_tab.reserve(bytes)) return rc;
-        const auto* tab = e->adam_tab.as<const apz::AdamTensor>();
-        // Stream-ordered upload: the copy queues behind the previous step's kernel (which read the same device table), and
-        // for pageable host memory hipMemcpyAsync returns once the 6 KB have been staged, so the caller's buffer need
-        // not outlive the call.  (No stream synchronisation: the optimiser step no longer drains the GPU.)
-        HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+        const apz::AdamTensor* tab;
+        if (int rc = upload_table(e, e->adam_tab, table_host, ntensors, &tab)) return rc;
         if (skip_dev)      // (two kernels with two signatures)
             hipLaunchKernelGGL(apz::adam_step_unless_kernel, dim3(32, ntensors), dim3(256), 0, e->stream, tab, lr_t, b1, b2, eps,
                                rescale, (const unsigned*)skip_dev);
@@ -2306,16 +2318,15 @@ namespace {
 bool guard_args_ok(const apz_engine* e, const void* table_host, int ntensors, const void* record_dev) {
     return e && table_host && ntensors >= 1 && ntensors <= 4096 && record_dev && ((uintptr_t)record_dev & 15) == 0;
 }
-// inside a train_call: the table uploaded (stream-ordered, as apz_adam_step_unless does), the two reduction launches queued
+// inside a train_call: the table uploaded, the two reduction launches queued
 int queue_grad_guard(apz_engine* e, const void* table_host, int ntensors, float rescale, float clip, const void* loss3_dev,
                      const void* skip_in_dev, void* record_dev) {
-    const size_t bytes = (size_t)ntensors * sizeof(apz::AdamTensor), parts = (size_t)ntensors * apz::GUARD_SPLITS;
-    if (int rc = e->adam_tab.reserve(bytes)) return rc;
+    const size_t parts = (size_t)ntensors * apz::GUARD_SPLITS;
     if (int rc = e->guard_part.reserve(parts * (sizeof(double) + sizeof(unsigned)))) return rc;
-    const auto* tab = e->adam_tab.as<const apz::AdamTensor>();
     double* part = e->guard_part.as<double>();
     unsigned* bad = (unsigned*)(part + parts);
-    HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
+    const apz::AdamTensor* tab;
+    if (int rc = upload_table(e, e->adam_tab, table_host, ntensors, &tab)) return rc;
     hipLaunchKernelGGL(apz::grad_sumsq_kernel, dim3(apz::GUARD_SPLITS, ntensors), dim3(256), 0, e->stream, tab, part, bad);
     hipLaunchKernelGGL(apz::grad_guard_fold_kernel, dim3(1), dim3(256), 0, e->stream, (const double*)part, (const unsigned*)bad,
                        ntensors, rescale, clip, (const float*)loss3_dev, (const unsigned*)skip_in_dev, (apz::GuardRecord*)record_dev);
@@ -2351,13 +2362,11 @@ int apz_ema_update(apz_engine* e, const void* table_host, int ntensors, float c,
     static_assert(sizeof(apz::EmaTensor) == 24, "apz_ema_tensor layout");
     if (ntensors == 0) return APZ_OK;       // an empty table: nothing to launch (a grid of (32, 0) is not one)
     return train_call(e, stream, [&]() -> int {
-        // the table travels as apz_adam_step_unless's does, through the same device buffer: the copy queues behind the
-        // Adam launch in front of it, which read its own table there
-        const size_t bytes = (size_t)ntensors * sizeof(apz::EmaTensor);
-        if (int rc = e->adam_tab.reserve(bytes)) return rc;
-        HIP_TRY(hipMemcpyAsync(e->adam_tab, table_host, bytes, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(apz::ema_update_kernel, dim3(32, ntensors), dim3(256), 0, e->stream,
-                           e->adam_tab.as<const apz::EmaTensor>(), c, (const unsigned*)skip_a_dev, (const unsigned*)skip_b_dev);
+        // through Adam's device buffer: the copy queues behind the Adam launch in front of it, which read its own table there
+        const apz::EmaTensor* tab;
+        if (int rc = upload_table(e, e->adam_tab, table_host, ntensors, &tab)) return rc;
+        hipLaunchKernelGGL(apz::ema_update_kernel, dim3(32, ntensors), dim3(256), 0, e->stream, tab, c,
+                           (const unsigned*)skip_a_dev, (const unsigned*)skip_b_dev);
         return APZ_OK;
     });
 }
@@ -2583,13 +2592,12 @@ int apz_replay_gather(apz_engine* e, const void* codes_dev, const void* pi_dev, 
             return fail(APZ_E_ARG, "replay gather: entry " + std::to_string(j) + " = " + std::to_string(entries_host[j]) +
                                        " lies outside [0, 8 * capacity = " + std::to_string(8 * capacity) + ")");
     return train_call(e, stream, [&]() -> int {
-        if (int rc = e->gather_entries.reserve((size_t)n * sizeof(int32_t))) return rc;
-        // stream-ordered upload behind the previous gather's kernel (apz_adam_step's table travels the same way)
-        HIP_TRY(hipMemcpyAsync(e->gather_entries, entries_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+        const int* entries;
+        if (int rc = upload_table(e, e->gather_entries, entries_host, n, &entries)) return rc;
         const long total = (long)n * e->hw;
         hipLaunchKernelGGL(apz::replay_gather_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 16)), dim3(256), 0,
                            e->stream, (const unsigned char*)codes_dev, (const float*)pi_dev, (const float*)z_dev,
-                           e->gather_entries.as<const int>(), e->perm_s, e->perm_p, (float*)planes_out_dev, (float*)pi_out_dev,
+                           entries, e->perm_s, e->perm_p, (float*)planes_out_dev, (float*)pi_out_dev,
                            (float*)z_out_dev, n, e->cfg.height, e->cfg.width, e->code_stride, n_planes);
         return APZ_OK;
     });

@@ -40,8 +40,9 @@ SIMPLE_CONVS = ("conv1", "conv2", "conv3", "conv4", "conv5", "conv_final")
 DeviceBatch = collections.namedtuple("DeviceBatch", "states pis zs")     # HipTrainer.upload()
 # what the forward pass leaves on the tape for the backward pass: one conv_act layer (x -> Convolution y -> BatchNorm,
 # relu a), and one residual block (x -> convA ya -> bnA, relu ha -> convB yb -> bnB + x, relu out; m / i: the batch mean
-# and 1 / std of each BatchNorm, k: its ReLU decisions as a bit mask, padded rows only)
-ConvAct = collections.namedtuple("ConvAct", "name x y a mean invstd layout")
+# and 1 / std of each BatchNorm, k: its ReLU decisions as a bit mask, padded rows only; layout: the convolution's, blay /
+# side: its BatchNorm's -- side only where that runs behind to_rows16 with the board mask, the stem of a framed board)
+ConvAct = collections.namedtuple("ConvAct", "name x y a mean invstd layout blay side")
 Block = collections.namedtuple("Block", "x ya ha ma ia yb out mb ib ka kb")
 
 
@@ -203,10 +204,7 @@ class HipTrainer(object):
         self._trunk_w = self._upk = None
         if self.rows16:
             self._trunk_names = ["conv%s%d_weight" % (ab, i) for i in range(1, n_blocks + 1) for ab in "AB"]
-            self._trunk_w = torch.empty((len(self._trunk_names), 128, 128, 3, 3), dtype=torch.float32, device=self.device)
-            for j, k in enumerate(self._trunk_names):
-                self._trunk_w[j].copy_(self.p[k])
-                self.p[k] = self._trunk_w[j]
+            self._trunk_w = self._flat(self._trunk_names, self.p).view(-1, 128, 128, 3, 3)
         self.trunk_arith = trunk_arith
         self.trunk_overflows = 0       # f16x2: steps (and loss_and_grads calls) repeated on the exact kernels
         self._fast = False             # the pass being queued runs its trunk on the f16x2 kernel
@@ -217,11 +215,7 @@ class HipTrainer(object):
             # the trunk biases back to back as well (wino3h_pack_many packs them with the weights), the moving statistics in
             # one buffer (one copy snapshots them at the start of a step: a repeated step must not move them twice), and
             # a word after the step's three losses: the overflow word, read with the losses in ONE device -> host copy
-            self._trunk_b = torch.empty((len(self._trunk_names), 128), dtype=torch.float32, device=self.device)
-            for j, k in enumerate(self._trunk_names):
-                kb = k[:-len("_weight")] + "_bias"
-                self._trunk_b[j].copy_(self.p[kb])
-                self.p[kb] = self._trunk_b[j]
+            self._trunk_b = self._flat([k[:-len("_weight")] + "_bias" for k in self._trunk_names], self.p).view(-1, 128)
             self._u16 = None
         # the guarded step (csrc/grad_guard.h) skips on the device; what it must not move either lives in the same
         # arrangement, for every net kind and arithmetic: the statistics in one buffer with a snapshot, and the guard's
@@ -233,16 +227,11 @@ class HipTrainer(object):
         self.clipped_steps = 0         # guarded steps taken with the gradient scaled to clip_norm
         self.last_skip_reason = None   # of the last guarded train_step: None (taken), or the record's why bits in words
         self.last_rescale_eff = None   # of the last guarded train_step: the `rescale` Adam ran with (float32)
+        self._word = None              # (a plain f32 trainer has none: its read-back is loss3)
         if trunk_arith == "f16x2" or self.step_guard:
-            self._stat_buf = torch.empty((sum(self.p[k].numel() for k in self.stat_names),), dtype=torch.float32, device=self.device)
-            off = 0
-            for k in self.stat_names:
-                v = self._stat_buf[off:off + self.p[k].numel()].view(self.p[k].shape)
-                v.copy_(self.p[k])
-                self.p[k] = v
-                off += v.numel()
+            self._stat_buf = self._flat(self.stat_names, self.p)
             self._stat_snap = torch.empty_like(self._stat_buf)
-            # [loss3][overflow word] (+ [record])
+            # [loss3][overflow word] (+ [record]): _attempt says which of them a read-back holds
             self._word = torch.zeros((8 if self.step_guard else 4,), dtype=torch.float32, device=self.device)
             self._flag = self._word[3:4]
             self._record = self._word[4:8] if self.step_guard else None
@@ -252,74 +241,63 @@ class HipTrainer(object):
         self.ema_updates = 0           # averaging steps applied (a skipped step is none)
         self.ema_p = None
         if ema_decay is not None:
-            self._ema_buf = torch.empty((sum(v.numel() for v in self.p.values()),), dtype=torch.float32, device=self.device)
             self.ema_p = collections.OrderedDict()
-            off = 0
-            for k, v in self.p.items():
-                self.ema_p[k] = self._ema_buf[off:off + v.numel()].view(v.shape)
-                self.ema_p[k].copy_(v)
-                off += v.numel()
+            self._ema_buf = self._flat(list(self.p), self.ema_p)
             # (the launch's table, once: from here on the tensors of p and ema_p are only ever written INTO)
             self._ema_tab = hipconv.ema_table([(self.ema_p[k], self.p[k]) for k in self.p])
         self._eval = None
         self._eval_t = -1
         self.tape = None
 
+    def _flat(self, names, into):
+        """The tensors of p named `names`, copied back to back into ONE new contiguous buffer -> the buffer, flat;
+        into[name] = the tensor's view of it (into = self.p: the tensor lives there from now on)"""
+        torch, src = self.torch, [self.p[k] for k in names]
+        buf = torch.empty((sum(t.numel() for t in src),), dtype=torch.float32, device=self.device)
+        off = 0
+        for k, t in zip(names, src):
+            into[k] = buf[off:off + t.numel()].view(t.shape)
+            into[k].copy_(t)
+            off += t.numel()
+        return buf
+
     # ---- forward: every activation the backward pass reads goes on the tape -----------------------------------------
-    def _conv_act_fwd(self, x, name, layout):
-        """conv_act of the reference (policy_value_net_mxnet.py:28-39): Convolution -> BatchNorm(fix_gamma) -> relu"""
+    def _conv_act_fwd(self, x, name, layout, frame=False):
+        """conv_act of the reference (policy_value_net_mxnet.py:28-39): Convolution -> BatchNorm(fix_gamma) -> relu
+        -> (a, ConvAct).  On a framed board a 1x1 convolution (a head) reads the S x S window of its padded-row input and
+        everything behind it is dense S x S.  frame (the stem of a framed board): the planes go into the 15x15 frame first,
+        and the BatchNorm runs BEHIND to_rows16 (the dense convolution leaves bias-and-neighbour values off the board; the
+        framed BatchNorm is the mask): x = the framed planes, y / a padded rows."""
         o, p = self.ops, self.p
         w = p[name + "_weight"]
+        if frame:
+            x = o.frame_planes(x)
         if w.shape[2] == 1:
-            y = o.conv1x1_fwd(x, w, p[name + "_bias"], layout)
-            blay = o.DENSE
+            y, blay = o.conv1x1_fwd(x, w, p[name + "_bias"], layout, side=self.frame_side), o.DENSE
         else:
-            y = o.conv3x3_fwd(x, w, p[name + "_bias"], layout)
-            blay = layout
+            y, blay = o.conv3x3_fwd(x, w, p[name + "_bias"], layout), layout
+        side = self.frame_side if frame else None
+        if frame:
+            y, blay = o.to_rows16(y), o.ROWS16
         a, mean, invstd = o.bn_fwd(y, None, p[name + "_beta"], p[name + "_mean"], p[name + "_var"], None, True, blay,
-                                   1.0 - BN_MOMENTUM, BN_EPS)
-        return a, ConvAct(name, x, y, a, mean, invstd, layout)
+                                   1.0 - BN_MOMENTUM, BN_EPS, side=side)
+        return a, ConvAct(name, x, y, a, mean, invstd, layout, blay, side)
 
-    def _conv_act_bwd(self, da, rec, need_dx, dx_acc=None):
-        o, p, g = self.ops, self.p, self.grad
-        name, x, y, a, mean, invstd, layout = rec
-        w = p[name + "_weight"]
-        one = w.shape[2] == 1
-        dy, _, _, g[name + "_beta"] = o.bn_bwd(da, y, a, None, mean, invstd, True, False, o.DENSE if one else layout)
-        if one:
-            dx, g[name + "_weight"], g[name + "_bias"] = o.conv1x1_bwd(x, w, dy, layout, dx_acc)
-            return dx
-        g[name + "_weight"] = o.conv3x3_wgrad(x, dy, layout)
-        g[name + "_bias"] = o.bias_grad(dy, layout)
-        return o.conv3x3_dgrad(dy, w, layout) if need_dx else None
+    def _act_bwd(self, da, rec):
+        """conv_act's BatchNorm and relu backwards -> dy in the layout its convolution wrote (framed stem: off-board cells
+        zero, so the dense 15x15 gradients behind it are the S x S board's)"""
+        o = self.ops
+        dy, _, _, self.grad[rec.name + "_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, rec.blay,
+                                                         side=rec.side)
+        return o.from_rows16(dy) if rec.side else dy
 
-    def _stem_fwd_framed(self, states):
-        """The stem on a framed board: the planes into the 15x15 frame, the dense 15x15 convolution, and the BatchNorm
-        BEHIND to_rows16 (the convolution leaves bias-and-neighbour values off the board; the framed BatchNorm is the mask)
-        -> (a, ConvAct): x = the framed planes, y / a padded rows"""
-        o, p, S = self.ops, self.p, self.frame_side
-        xf = o.frame_planes(states)
-        y = o.to_rows16(o.conv3x3_fwd(xf, p["res_conv1_weight"], p["res_conv1_bias"], o.DENSE))
-        a, mean, invstd = o.bn_fwd(y, None, p["res_conv1_beta"], p["res_conv1_mean"], p["res_conv1_var"], None, True, o.ROWS16,
-                                   1.0 - BN_MOMENTUM, BN_EPS, side=S)
-        return a, ConvAct("res_conv1", xf, y, a, mean, invstd, o.ROWS16)
-
-    def _stem_bwd_framed(self, da, rec):
+    def _conv_act_bwd(self, da, rec, need_dx):
+        """conv_act backwards, 3x3 (the two 1x1 heads share their input: _backward runs them as a pair)"""
         o, g = self.ops, self.grad
-        dy, _, _, g["res_conv1_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, o.ROWS16,
-                                                 side=self.frame_side)
-        dy = o.from_rows16(dy)              # off-board cells zero: the dense 15x15 gradients below are the S x S board's
-        g["res_conv1_weight"] = o.conv3x3_wgrad(rec.x, dy, o.DENSE)
-        g["res_conv1_bias"] = o.bias_grad(dy, o.DENSE)
-
-    def _head_fwd_framed(self, x, name):
-        """conv_act of a head on a framed board: the 1x1 convolution reads the S x S window of the padded-row trunk output,
-        everything behind it is dense S x S"""
-        o, p = self.ops, self.p
-        y = o.conv1x1_fwd(x, p[name + "_weight"], p[name + "_bias"], o.ROWS16, side=self.frame_side)
-        a, mean, invstd = o.bn_fwd(y, None, p[name + "_beta"], p[name + "_mean"], p[name + "_var"], None, True, o.DENSE,
-                                   1.0 - BN_MOMENTUM, BN_EPS)
-        return a, ConvAct(name, x, y, a, mean, invstd, o.ROWS16)
+        dy = self._act_bwd(da, rec)
+        g[rec.name + "_weight"] = o.conv3x3_wgrad(rec.x, dy, rec.layout)
+        g[rec.name + "_bias"] = o.bias_grad(dy, rec.layout)
+        return o.conv3x3_dgrad(dy, self.p[rec.name + "_weight"], rec.layout) if need_dx else None
 
     def _trunk_conv(self, j):
         """Trunk convolution j = 2 i - 2 (A of block i) or 2 i - 1 (B): its parameter prefix"""
@@ -355,11 +333,7 @@ class HipTrainer(object):
         tape = {"blocks": [], "stack": []}
         if self.kind == "resnet":
             S = self.frame_side
-            if S:
-                x, rec = self._stem_fwd_framed(states)
-            else:
-                x, rec = self._conv_act_fwd(states, "res_conv1", o.DENSE)
-            tape["stem"] = rec
+            x, tape["stem"] = self._conv_act_fwd(states, "res_conv1", o.DENSE, frame=bool(S))
             lay = o.ROWS16 if self.rows16 else o.DENSE
             if self.rows16:             # every trunk layer's weights packed for this pass's kernel, both orientations, one launch
                 if not S:
@@ -387,12 +361,8 @@ class HipTrainer(object):
                 tape["stack"].append(rec)
         tape["layout"] = lay
         n = int(x.shape[0])
-        if self.frame_side:
-            pol, tape["pol"] = self._head_fwd_framed(x, "conv3_1_1")
-            val, tape["val"] = self._head_fwd_framed(x, "conv3_2_1")
-        else:
-            pol, tape["pol"] = self._conv_act_fwd(x, "conv3_1_1", lay)
-            val, tape["val"] = self._conv_act_fwd(x, "conv3_2_1", lay)
+        pol, tape["pol"] = self._conv_act_fwd(x, "conv3_1_1", lay)
+        val, tape["val"] = self._conv_act_fwd(x, "conv3_2_1", lay)
         pol, val = pol.view(n, -1), val.view(n, -1)
         if self.dropout > 0:
             keep = 1.0 - self.dropout
@@ -415,10 +385,8 @@ class HipTrainer(object):
             dpol = o.dropout(dpol, keep, self.seed, 2 * (self.dropout_step0 + tape["step"]))
             dval = o.dropout(dval, keep, self.seed, 2 * (self.dropout_step0 + tape["step"]) + 1)
         # the two heads share their input: both BatchNorm backward passes, then ONE pass over the trunk output for dx
-        dys = []
-        for da, rec in ((dpol.view(n, 4, self.side, self.side), tape["pol"]), (dval.view(n, 2, self.side, self.side), tape["val"])):
-            dy, _, _, g[rec.name + "_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, o.DENSE)
-            dys.append(dy)
+        dys = [self._act_bwd(dpol.view(n, 4, self.side, self.side), tape["pol"]),
+               self._act_bwd(dval.view(n, 2, self.side, self.side), tape["val"])]
         dx, g["conv3_1_1_weight"], g["conv3_1_1_bias"], g["conv3_2_1_weight"], g["conv3_2_1_bias"] = o.conv1x1_bwd_pair(
             tape["pol"].x, p["conv3_1_1_weight"], dys[0], p["conv3_2_1_weight"], dys[1], tape["pol"].layout, side=self.frame_side)
         if self.kind == "resnet":
@@ -448,12 +416,9 @@ class HipTrainer(object):
             for i in range(1, nb + 1):
                 g["convA%d_bias" % i] = db[(2 * i - 2) * nf:(2 * i - 1) * nf]
                 g["convB%d_bias" % i] = db[(2 * i - 1) * nf:2 * i * nf]
-            if S:
-                self._stem_bwd_framed(dx, tape["stem"])
-            else:
-                if self.rows16:
-                    dx = o.from_rows16(dx)
-                self._conv_act_bwd(dx, tape["stem"], False)
+            if self.rows16 and not S:      # (the framed stem's BatchNorm takes padded rows)
+                dx = o.from_rows16(dx)
+            self._conv_act_bwd(dx, tape["stem"], False)
         else:
             for j in range(len(SIMPLE_CONVS) - 1, -1, -1):
                 dx = self._conv_act_bwd(dx, tape["stack"][j], j > 0)
@@ -476,46 +441,65 @@ class HipTrainer(object):
         the saved activations afterwards (relu_masks(); tests).  state_batch: host array, or upload()'s DeviceBatch.
         trunk_arith "f16x2": the call reads the overflow word (a synchronisation) and repeats itself on the exact kernels
         when it is set (train_step does the same without the extra synchronisation)."""
-        if self.trunk_arith == "f32":
-            return self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
-        batch, loss3 = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape)
-        if int(self._flag.view(self.torch.int32).item()) == 0:
-            return loss3
-        return self._repeat_exact(batch, keep_tape)
+        return self._attempts(state_batch, mcts_probs, winner_batch, None, keep_tape)[0]
 
-    def _loss_and_grads(self, state_batch, mcts_probs=None, winner_batch=None, keep_tape=False, fast=False, loss3=None):
-        if isinstance(state_batch, DeviceBatch):
-            states, pis, zs = state_batch
-        else:
-            states, pis, zs = self.upload(state_batch, mcts_probs, winner_batch)
+    def _pass(self, batch, fast, keep_tape, loss3):
+        """Forward and backward of one DeviceBatch, the trunk on the f16x2 kernels if `fast` -> loss3 (given, or new)"""
         self.grad = {}
         self._fast = fast
         try:
-            logits, vlogit, tape = self._forward(states, self.t)
+            logits, vlogit, tape = self._forward(batch.states, self.t)
             tape["step"] = self.t
-            out = self.ops.pv_loss(logits, vlogit, pis, zs, grads=True, loss3=loss3)
+            out = self.ops.pv_loss(logits, vlogit, batch.pis, batch.zs, grads=True, loss3=loss3)
             self._backward(tape, out["dlogits"], out["dvlogit"])
         finally:
             self._fast = False
         self.tape = tape if keep_tape else None
         return out["loss3"]
 
-    def _fast_pass(self, state_batch, mcts_probs, winner_batch, keep_tape, loss3=None):
-        """trunk_arith "f16x2": the moving statistics snapshotted (a repeated pass must not move them twice), then the pass
-        on the f16x2 kernels -> (the mini-batch on the device, loss3).  The caller reads the overflow word and, when it is
-        set, calls _repeat_exact."""
-        if not isinstance(state_batch, DeviceBatch):
-            state_batch = self.upload(state_batch, mcts_probs, winner_batch)
-        self._stat_snap.copy_(self._stat_buf)
-        return state_batch, self._loss_and_grads(state_batch, keep_tape=keep_tape, fast=True, loss3=loss3)
+    def _attempt(self, batch, fast, learning_rate, keep_tape, snapshot=True):
+        """One attempt at a step, queued: the pass (fast: on the f16x2 kernels) and, with a learning rate (None:
+        loss_and_grads), t += 1, Adam and the average's launch -> (loss3 on the device, the read-back).  The rules of the
+        step's words live here and nowhere else:
+          snapshot   of the moving statistics, where something may refuse the attempt: an f16x2 pass or a guarded step
+                     (snapshot=False: the repeat of a pass, the snapshot still holds the statistics at the start of the step)
+          skip word  of Adam: the overflow word on a fast attempt (the guard counts it among its reasons); of the average: the
+                     guard record's skip word under the guard, else Adam's
+          read-back  ONE device -> host copy, the attempt's only synchronisation: the word buffer [loss3][overflow word]
+                     (+ [record]: guarded) where the trainer has one, else loss3; none for an exact pass without a step.
+                     loss3 means something after a step, word 3 after a fast attempt, the record after a guarded step."""
+        step = learning_rate is not None
+        guarded = step and self.step_guard
+        if snapshot and (fast or guarded):
+            self._stat_snap.copy_(self._stat_buf)
+        loss3 = self._pass(batch, fast, keep_tape, self._word[:3] if (step and self._word is not None) else None)
+        if step:
+            self.t += 1
+            overflow = self._flag if fast else None
+            self._adam(learning_rate, skip=overflow, guarded=guarded)
+            self._ema(skip=self._record[2:3] if guarded else overflow)
+        back = self._word if (self._word is not None and (step or fast)) else loss3 if step else None
+        return loss3, (None if back is None else back.cpu().numpy())
 
-    def _repeat_exact(self, batch, keep_tape, loss3=None):
-        """An f16x2 launch of the pass just queued left the fp16 range: its gradients never reached Adam; the moving
-        statistics go back to their values at the start of the pass, which is then taken again on the exact kernels
-        -> loss3."""
-        self.trunk_overflows += 1
+    def _attempts(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape):
+        """The attempt on the trainer's arithmetic and, when an f16x2 launch of it left the fp16 range (nothing reached Adam
+        or the average: the overflow word skipped them), everything taken back and the exact attempt -> what that returns;
+        its word 3 is still set and says nothing"""
+        batch = state_batch if isinstance(state_batch, DeviceBatch) else self.upload(state_batch, mcts_probs, winner_batch)
+        fast = self.trunk_arith == "f16x2"
+        loss3, w = self._attempt(batch, fast, learning_rate, keep_tape)
+        if fast and w[3:4].view(np.uint32)[0] != 0:
+            self.trunk_overflows += 1
+            self._take_back(learning_rate is not None)
+            loss3, w = self._attempt(batch, False, learning_rate, keep_tape, snapshot=False)
+        return loss3, w
+
+    def _take_back(self, stepped=True):
+        """A refused attempt: the moving statistics as at its start, and t (the next attempt draws the same dropout masks; the
+        internal evaluator is not stale)"""
         self._stat_buf.copy_(self._stat_snap)
-        return self._loss_and_grads(batch, keep_tape=keep_tape, loss3=loss3)
+        if stepped:
+            self.t -= 1
 
     def relu_masks(self):
         """{layer: [n][C][H][W] bool} -- which activations of the kept forward pass were positive.  (A comparator that
@@ -535,67 +519,25 @@ class HipTrainer(object):
     def train_step(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape=False):
         """One optimiser step -> (loss, entropy).  state_batch may be upload()'s DeviceBatch (mcts_probs / winner_batch are
         then ignored).  step_guard: see __init__ -- a skipped step returns its own losses, NaN included."""
-        if self.step_guard:
-            return self._train_step_guarded(state_batch, mcts_probs, winner_batch, learning_rate, keep_tape)
-        if self.trunk_arith == "f16x2":
-            batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=self._word[:3])
-            self.t += 1
-            self._adam(learning_rate, skip=self._flag)      # skipped on the device when the overflow word is set
-            self._ema(skip=self._flag)         # (and the average with it)
-            w4 = self._word.cpu().numpy()      # the losses and the overflow word: still the step's only synchronisation
-            if w4[3:].view(np.uint32)[0] == 0:
-                self._ema_applied()
-                return float(w4[0] + w4[1]), float(w4[2])
-            self.t -= 1
-            loss3 = self._repeat_exact(batch, keep_tape)
-        else:
-            loss3 = self._loss_and_grads(state_batch, mcts_probs, winner_batch, keep_tape)
-        self.t += 1
-        self._adam(learning_rate)
-        self._ema()
-        self._ema_applied()
-        l3 = loss3.cpu().numpy()           # the step's only device -> host copy (12 bytes), and its synchronisation
-        return float(l3[0] + l3[1]), float(l3[2])
+        _, w = self._attempts(state_batch, mcts_probs, winner_batch, learning_rate, keep_tape)
+        self._verdict(w)
+        return float(w[0] + w[1]), float(w[2])
 
-    def _train_step_guarded(self, state_batch, mcts_probs, winner_batch, learning_rate, keep_tape):
-        """train_step with the guard on: snapshot, pass, guard and guarded Adam queued; ONE read-back of [loss3][overflow
-        word][record]; a record that says skip puts the statistics back and takes t back."""
-        loss3 = self._word[:3]
-        if self.trunk_arith == "f16x2":
-            batch, _ = self._fast_pass(state_batch, mcts_probs, winner_batch, keep_tape, loss3=loss3)
-            self.t += 1
-            self._adam(learning_rate, skip=self._flag, guarded=True)      # (the overflow word is one of the guard's reasons)
-            self._ema(skip=self._record[2:3])  # the record's skip word: the overflow bit is among its reasons
-            w8 = self._word.cpu().numpy()
-            if w8[3:4].view(np.uint32)[0] != 0:
-                # overflowed: nothing reached Adam.  The exact repeat as always (the snapshot still holds the statistics at
-                # the start of the step), guarded in turn; its word 3 stays set and says nothing about the repeat.
-                self.t -= 1
-                self._repeat_exact(batch, keep_tape, loss3=loss3)
-                self.t += 1
-                self._adam(learning_rate, guarded=True)
-                self._ema(skip=self._record[2:3])       # (the repeat's record)
-                w8 = self._word.cpu().numpy()
-        else:
-            batch = state_batch if isinstance(state_batch, DeviceBatch) else self.upload(state_batch, mcts_probs, winner_batch)
-            self._stat_snap.copy_(self._stat_buf)
-            self._loss_and_grads(batch, keep_tape=keep_tape, loss3=loss3)
-            self.t += 1
-            self._adam(learning_rate, guarded=True)
-            self._ema(skip=self._record[2:3])
-            w8 = self._word.cpu().numpy()      # the losses and the record: still the step's only synchronisation
-        norm, eff, skip, why = self.ops.read_guard_record(w8[4:8])
-        self.last_grad_norm, self.last_rescale_eff = norm, eff
-        self.last_skip_reason = self.ops.guard_reason(why)
-        if skip:
-            self._stat_buf.copy_(self._stat_snap)
-            self.t -= 1                 # (the next step draws this step's dropout masks; the internal evaluator is not stale)
-            self.skipped_steps += 1
-        else:
-            self._ema_applied()
+    def _verdict(self, w):
+        """What the step's last read-back says of it.  Guarded: the record -- a skip takes the step back; a rescale other than
+        1 / batch_size is a clip.  A step that stands has moved the average."""
+        if self.step_guard:
+            norm, eff, skip, why = self.ops.read_guard_record(w[4:8])
+            self.last_grad_norm, self.last_rescale_eff = norm, eff
+            self.last_skip_reason = self.ops.guard_reason(why)
+            if skip:
+                self._take_back()
+                self.skipped_steps += 1
+                return
             if eff != np.float32(1.0 / self.batch_size):
                 self.clipped_steps += 1
-        return float(w8[0] + w8[1]), float(w8[2])
+        if self.ema_p is not None:
+            self.ema_updates += 1
 
     def _entries(self):
         return [(self.p[k], self.grad[k], self.m[k], self.v[k], self.wd if k.endswith(("_weight", "_gamma")) else 0.0)
@@ -618,10 +560,6 @@ class HipTrainer(object):
             return
         c = ema_coefficient(self.ema_decay, self.ema_updates, self.ema_warmup)
         self.ops.ema_update(self._ema_tab, c, self.device, skip=skip)
-
-    def _ema_applied(self):
-        if self.ema_p is not None:
-            self.ema_updates += 1
 
     def ema_params(self):
         """The averaged weights as host arrays, in get_params()'s order (ValueError without ema_decay)"""
@@ -673,6 +611,10 @@ class HipTrainer(object):
         return collections.OrderedDict((k, v.cpu().numpy()) for k, v in self.p.items())
 
     # ---- checkpoint -----------------------------------------------------------------------------------------------
+    def _groups(self, ema):
+        """The tensor groups of a state by their key prefix; ema: the averaged weights among them"""
+        return [("p", self.p), ("m", self.m), ("v", self.v)] + ([("e", self.ema_p)] if ema else [])
+
     def state(self):
         """Everything the next train_step reads, as host values: {"meta": t, dropout_step0, seed, trunk_overflows, the guard's
         two settings and two counters and the net's kind (the dropout masks are keyed by seed and dropout_step0 + t),
@@ -683,11 +625,9 @@ class HipTrainer(object):
                         "trunk_arith": self.trunk_arith, "framed": self.framed, "step_guard": self.step_guard,
                         "clip_norm": self.clip_norm, "skipped_steps": int(self.skipped_steps),
                         "clipped_steps": int(self.clipped_steps)}}
-        groups = [("p", self.p), ("m", self.m), ("v", self.v)]
         if self.ema_p is not None:
             out["meta"].update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=int(self.ema_updates))
-            groups.append(("e", self.ema_p))
-        for tag, group in groups:
+        for tag, group in self._groups(self.ema_p is not None):
             for k, t in group.items():
                 out["%s/%s" % (tag, k)] = t.cpu().numpy()
         return out
@@ -706,11 +646,8 @@ class HipTrainer(object):
             raise ValueError("this trainer state was written with framed=%s, the trainer was built with framed=%s" %
                              (bool(meta.get("framed", False)), self.framed))
         todo = []
-        groups = [("p", self.p), ("m", self.m), ("v", self.v)]
         with_ema = self.ema_p is not None and any(k.startswith("e/") for k in state)
-        if with_ema:
-            groups.append(("e", self.ema_p))
-        for tag, group in groups:
+        for tag, group in self._groups(with_ema):
             for k, t in group.items():
                 a = state.get("%s/%s" % (tag, k))
                 if a is None or tuple(np.shape(a)) != tuple(t.shape):
