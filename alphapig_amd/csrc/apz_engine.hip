@@ -2069,6 +2069,90 @@ int bn_splits(const apz_engine* e, int n, int C, int layout) {
     const int per = layout == APZ_LAYOUT_ROWS16 ? (n + 3) / 4 : n;
     return std::max(1, std::min({per, (e->num_cu * (layout == APZ_LAYOUT_ROWS16 ? 8 : 4)) / C, BN_SPLITS}));
 }
+// framed boards in the training step (csrc/bn_frame.h, csrc/frame15.h): a board of side S on the 15x15 engine
+int frame_train_check(const apz_engine* e, int side, const char* who) {
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, std::string(who) + ": the 15x15 engine only");
+    if (!(apz::Frame15::framed_side(side) || side == 15))
+        return fail(APZ_E_UNSUPPORTED, std::string(who) + ": side must be 6, 7, 9, 11, 12, 13, 14 or 15");
+    return APZ_OK;
+}
+
+// The BatchNorm forward on checked arguments: scratch, splits, the statistics launch and the apply launch.  side 0: the
+// engine's board in `layout` (ps, rs from bn_geometry); else a framed board on padded rows (csrc/bn_frame.h): count n side side.
+int bn_fwd_launch(apz_engine* e, const void* x_dev, const void* resid_dev, const void* gamma_dev, const void* beta_dev,
+                  void* run_mean_dev, void* run_var_dev, void* y_dev, void* mean_dev, void* invstd_dev, const void* stats_dev,
+                  void* mask_dev, int n, int C, int layout, int relu, float momentum, float eps, int side, int ps, int rs,
+                  void* stream) {
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int H = side ? side : e->cfg.height, W = side ? side : e->cfg.width;
+        const int splits = bn_splits(e, n, C, layout);
+        const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev, (double)n * H * W, eps,
+                               momentum};
+        auto rows = [&](auto board) {
+            using B = decltype(board);
+            // statistics from the producer (apz_wino_conv_stats: one pair of sums per channel and board): no pass over x for them
+            if (!stats_dev)
+                hipLaunchKernelGGL(apz::bn_stats_rows_kernel<B>, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part,
+                                   n, C, board);
+            hipLaunchKernelGGL(apz::bn_apply_rows_kernel<B>, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
+                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev,
+                               stats_dev ? (const double*)stats_dev : part, stats_dev ? n : splits, fin, (float*)y_dev,
+                               (unsigned char*)mask_dev, n, C, relu, board);
+        };
+        if (side) {
+            rows(apz::BoardFrame{side});
+        } else if (layout == APZ_LAYOUT_ROWS16) {
+            rows(apz::Board15{});
+        } else {
+            hipLaunchKernelGGL(apz::bn_stats_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C, ps,
+                               rs, H, W);
+            hipLaunchKernelGGL(apz::bn_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
+                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, part, splits, fin,
+                               (float*)y_dev, n, C, ps, rs, H, W, relu);
+        }
+        return APZ_OK;
+    });
+}
+
+// ... and the backward: the reduce launch and the apply launch
+int bn_bwd_launch(apz_engine* e, const void* dy_dev, const void* x_dev, const void* out_dev, const void* mask_dev,
+                  const void* gamma_dev, const void* mean_dev, const void* invstd_dev, void* dx_dev, void* dres_dev,
+                  void* dgamma_dev, void* dbeta_dev, void* dxsum_dev, int dxsum_ld, void* dxmax_dev, int n, int C, int layout,
+                  int relu, int side, int ps, int rs, void* stream) {
+    return train_call(e, stream, [&]() -> int {
+        if (int rc = bn_scratch(e)) return rc;
+        double* part = e->bn_part.as<double>();
+        const int H = side ? side : e->cfg.height, W = side ? side : e->cfg.width;
+        const int splits = bn_splits(e, n, C, layout);
+        auto rows = [&](auto board) {
+            using B = decltype(board);
+            hipLaunchKernelGGL(apz::bn_bwd_reduce_rows_kernel<B>, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev, part,
+                               (const unsigned char*)mask_dev, n, C, relu, board);
+            hipLaunchKernelGGL(apz::bn_bwd_apply_rows_kernel<B>, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
+                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev, (float*)dgamma_dev,
+                               (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C, relu,
+                               (double)n * H * W, (float*)dxmax_dev, board);
+        };
+        if (side) {
+            rows(apz::BoardFrame{side});
+        } else if (layout == APZ_LAYOUT_ROWS16) {
+            rows(apz::Board15{});
+        } else {
+            hipLaunchKernelGGL(apz::bn_bwd_reduce_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev, part,
+                               n, C, ps, rs, H, W, relu);
+            hipLaunchKernelGGL(apz::bn_bwd_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
+                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
+                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev, (float*)dgamma_dev,
+                               (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu, (double)n * H * W);
+        }
+        return APZ_OK;
+    });
+}
 }  // namespace
 
 int apz_bn_fwd(apz_engine* e, const void* x_dev, const void* resid_dev, const void* gamma_dev, const void* beta_dev,
@@ -2087,30 +2171,8 @@ int apz_bn_fwd_stats(apz_engine* e, const void* x_dev, const void* resid_dev, co
     if ((stats_dev || mask_dev) && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_fwd_stats: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    return train_call(e, stream, [&]() -> int {
-        if (int rc = bn_scratch(e)) return rc;
-        double* part = e->bn_part.as<double>();
-        const int H = e->cfg.height, W = e->cfg.width;
-        const int splits = bn_splits(e, n, C, layout);
-        const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev, (double)n * H * W, eps,
-                               momentum};
-        if (layout == APZ_LAYOUT_ROWS16) {
-            // statistics from the producer (apz_wino_conv_stats: one pair of sums per channel and board): no pass over x for them
-            if (!stats_dev)
-                hipLaunchKernelGGL(apz::bn_stats_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C);
-            hipLaunchKernelGGL(apz::bn_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
-                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev,
-                               stats_dev ? (const double*)stats_dev : part, stats_dev ? n : splits, fin,
-                               (float*)y_dev, (unsigned char*)mask_dev, n, C, relu);
-        } else {
-            hipLaunchKernelGGL(apz::bn_stats_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C,
-                               ps, rs, H, W);
-            hipLaunchKernelGGL(apz::bn_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
-                               (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, part,
-                               splits, fin, (float*)y_dev, n, C, ps, rs, H, W, relu);
-        }
-        return APZ_OK;
-    });
+    return bn_fwd_launch(e, x_dev, resid_dev, gamma_dev, beta_dev, run_mean_dev, run_var_dev, y_dev, mean_dev, invstd_dev, stats_dev,
+                         mask_dev, n, C, layout, relu, momentum, eps, 0, ps, rs, stream);
 }
 
 int apz_bn_bwd_splits(apz_engine* e, int n, int C, int layout) {
@@ -2135,44 +2197,12 @@ int apz_bn_bwd_max(apz_engine* e, const void* dy_dev, const void* x_dev, const v
     if (dxmax_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_max: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    return train_call(e, stream, [&]() -> int {
-        if (int rc = bn_scratch(e)) return rc;
-        double* part = e->bn_part.as<double>();
-        const int H = e->cfg.height, W = e->cfg.width;
-        const int splits = bn_splits(e, n, C, layout);
-        if (layout == APZ_LAYOUT_ROWS16) {
-            hipLaunchKernelGGL(apz::bn_bwd_reduce_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
-                               part, (const unsigned char*)mask_dev, n, C, relu);
-            hipLaunchKernelGGL(apz::bn_bwd_apply_r16_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
-                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev,
-                               (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C,
-                               relu, (double)n * H * W, (float*)dxmax_dev);
-        } else {
-            hipLaunchKernelGGL(apz::bn_bwd_reduce_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                               (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev,
-                               part, n, C, ps, rs, H, W, relu);
-            hipLaunchKernelGGL(apz::bn_bwd_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                               (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
-                               (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev,
-                               (float*)dgamma_dev, (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu,
-                               (double)n * H * W);
-        }
-        return APZ_OK;
-    });
+    return bn_bwd_launch(e, dy_dev, x_dev, out_dev, mask_dev, gamma_dev, mean_dev, invstd_dev, dx_dev, dres_dev, dgamma_dev,
+                         dbeta_dev, dxsum_dev, dxsum_ld, dxmax_dev, n, C, layout, relu, 0, ps, rs, stream);
 }
 
-// ---- framed boards in the training step (csrc/bn_frame.h): the padded-row BatchNorm with a board mask, on the 15x15 engine
-namespace {
-int frame_train_check(const apz_engine* e, int side, const char* who) {
-    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, std::string(who) + ": the 15x15 engine only");
-    if (!(apz::Frame15::framed_side(side) || side == 15))
-        return fail(APZ_E_UNSUPPORTED, std::string(who) + ": side must be 6, 7, 9, 11, 12, 13, 14 or 15");
-    return APZ_OK;
-}
-}  // namespace
-
+// ... on framed boards: the same launches with the board mask (no statistics from a convolution's epilogue: those cover
+// all 225 cells)
 int apz_bn_fwd_frame(apz_engine* e, const void* x_dev, const void* resid_dev, const void* gamma_dev, const void* beta_dev,
                      void* run_mean_dev, void* run_var_dev, void* y_dev, void* mean_dev, void* invstd_dev, void* mask_dev, int n,
                      int C, int layout, int relu, float momentum, float eps, int side, void* stream) {
@@ -2180,18 +2210,8 @@ int apz_bn_fwd_frame(apz_engine* e, const void* x_dev, const void* resid_dev, co
         return fail(APZ_E_ARG, "bad argument");
     if (layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_fwd_frame: padded-row layout only");
     if (int rc = frame_train_check(e, side, "bn_fwd_frame")) return rc;
-    return train_call(e, stream, [&]() -> int {
-        if (int rc = bn_scratch(e)) return rc;
-        double* part = e->bn_part.as<double>();
-        const int splits = bn_splits(e, n, C, layout);
-        const apz::BnFinal fin{(float*)mean_dev, (float*)invstd_dev, (float*)run_mean_dev, (float*)run_var_dev,
-                               (double)n * side * side, eps, momentum};
-        hipLaunchKernelGGL(apz::bn_stats_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev, part, n, C, side);
-        hipLaunchKernelGGL(apz::bn_apply_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)x_dev,
-                           (const float*)resid_dev, (const float*)gamma_dev, (const float*)beta_dev, part, splits, fin,
-                           (float*)y_dev, (unsigned char*)mask_dev, n, C, relu, side);
-        return APZ_OK;
-    });
+    return bn_fwd_launch(e, x_dev, resid_dev, gamma_dev, beta_dev, run_mean_dev, run_var_dev, y_dev, mean_dev, invstd_dev, nullptr,
+                         mask_dev, n, C, layout, relu, momentum, eps, side, 0, 0, stream);
 }
 
 int apz_bn_bwd_frame(apz_engine* e, const void* dy_dev, const void* x_dev, const void* out_dev, const void* mask_dev,
@@ -2203,20 +2223,8 @@ int apz_bn_bwd_frame(apz_engine* e, const void* dy_dev, const void* x_dev, const
         return fail(APZ_E_ARG, "bad argument");
     if (layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_frame: padded-row layout only");
     if (int rc = frame_train_check(e, side, "bn_bwd_frame")) return rc;
-    return train_call(e, stream, [&]() -> int {
-        if (int rc = bn_scratch(e)) return rc;
-        double* part = e->bn_part.as<double>();
-        const int splits = bn_splits(e, n, C, layout);
-        hipLaunchKernelGGL(apz::bn_bwd_reduce_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)mean_dev, (const float*)invstd_dev, part,
-                           (const unsigned char*)mask_dev, n, C, relu, side);
-        hipLaunchKernelGGL(apz::bn_bwd_apply_frame_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
-                           (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
-                           (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev, (float*)dgamma_dev,
-                           (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, (const unsigned char*)mask_dev, n, C, relu,
-                           (double)n * side * side, (float*)dxmax_dev, side);
-        return APZ_OK;
-    });
+    return bn_bwd_launch(e, dy_dev, x_dev, out_dev, mask_dev, gamma_dev, mean_dev, invstd_dev, dx_dev, dres_dev, dgamma_dev,
+                         dbeta_dev, dxsum_dev, dxsum_ld, dxmax_dev, n, C, layout, relu, side, 0, 0, stream);
 }
 
 int apz_colsum(apz_engine* e, const void* in_dev, void* out_dev, int rows, int cols, float scale, void* stream) {
@@ -2386,19 +2394,61 @@ void launch_sgemm(apz_engine* e, const float* a, const float* b, const float* bi
 }
 }  // namespace
 
-int apz_conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C,
-                    int CO, int layout, void* stream) {
+namespace {
+// the window a 1x1 head convolution walks: H x W cells in planes of `ps` floats, rows of `rs`
+struct HeadGeo { int H, W, ps, rs; };
+// frame null: the engine's board in `layout`; else the side x side window of a padded-row trunk tensor (framed boards;
+// frame = the entry point's name for the refusal)
+int head_geometry(apz_engine* e, int layout, int side, const char* frame, HeadGeo* g) {
+    if (frame) {
+        *g = {side, side, apz::Frame15::GPLANE, apz::Frame15::GROW};
+        return frame_train_check(e, side, frame);
+    }
+    g->H = e->cfg.height, g->W = e->cfg.width;
+    return bn_geometry(e, layout, &g->ps, &g->rs);
+}
+
+int conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C, int CO,
+                int layout, int side, const char* frame, void* stream) {
     if (!e || !x_dev || !w_dev || !y_dev || n < 1 || C < 1 || C > 1024 || CO < 1 || CO > 8) return fail(APZ_E_ARG, "bad argument");
-    int ps, rs;
-    if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
+    HeadGeo g;
+    if (int rc = head_geometry(e, layout, side, frame, &g)) return rc;
     return train_call(e, stream, [&]() -> int {
         const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
         if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
-        hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (e->cfg.height * e->cfg.width + 63) / 64), dim3(256), lds, e->stream,
-                           (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, e->cfg.height,
-                           e->cfg.width, ps, rs);
+        hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (g.H * g.W + 63) / 64), dim3(256), lds, e->stream, (const float*)x_dev,
+                           (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, g.H, g.W, g.ps, g.rs);
         return APZ_OK;
     });
+}
+
+int conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const void* dy1_dev, int CO1, const void* w2_dev,
+                 const void* dy2_dev, int CO2, void* dx_dev, void* dw_dev, int n, int C, int layout, int side, const char* frame,
+                 int accumulate_dx, void* stream) {
+    if (!e || !x_dev || !w1_dev || !dy1_dev || !dw_dev || n < 1 || C < 1 || C > 1024 || CO1 < 1 || CO2 < 0 || CO1 + CO2 > 8 ||
+        (CO2 > 0 && (!w2_dev || !dy2_dev)))
+        return fail(APZ_E_ARG, "bad argument");
+    HeadGeo g;
+    if (int rc = head_geometry(e, layout, side, frame, &g)) return rc;
+    return train_call(e, stream, [&]() -> int {
+        const int P = g.H * g.W, CO = CO1 + CO2;
+        if (int rc = e->head_scratch.reserve((size_t)n * CO * C * sizeof(float))) return rc;
+        float* part = e->head_scratch.as<float>();      // dw per board
+        const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
+        if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
+        hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
+                           (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
+                           part, C, CO1, CO2, g.H, g.W, g.ps, g.rs, accumulate_dx);
+        hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)part,
+                           (float*)dw_dev, n, CO * C, 1.0f);
+        return APZ_OK;
+    });
+}
+}  // namespace
+
+int apz_conv1x1_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C,
+                    int CO, int layout, void* stream) {
+    return conv1x1_fwd(e, x_dev, w_dev, bias_dev, y_dev, n, C, CO, layout, 0, nullptr, stream);
 }
 
 int apz_conv1x1_bwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* dy_dev, void* dx_dev, void* dw_dev,
@@ -2412,24 +2462,8 @@ int apz_conv1x1_bwd(apz_engine* e, const void* x_dev, const void* w_dev, const v
 int apz_conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const void* dy1_dev, int CO1, const void* w2_dev,
                      const void* dy2_dev, int CO2, void* dx_dev, void* dw_dev, int n, int C, int layout, int accumulate_dx,
                      void* stream) {
-    if (!e || !x_dev || !w1_dev || !dy1_dev || !dw_dev || n < 1 || C < 1 || C > 1024 || CO1 < 1 || CO2 < 0 || CO1 + CO2 > 8 ||
-        (CO2 > 0 && (!w2_dev || !dy2_dev)))
-        return fail(APZ_E_ARG, "bad argument");
-    int ps, rs;
-    if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
-    return train_call(e, stream, [&]() -> int {
-        const int P = e->cfg.height * e->cfg.width, CO = CO1 + CO2;
-        if (int rc = e->head_scratch.reserve((size_t)n * CO * C * sizeof(float))) return rc;
-        float* part = e->head_scratch.as<float>();      // dw per board
-        const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
-        if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
-        hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
-                           (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
-                           part, C, CO1, CO2, e->cfg.height, e->cfg.width, ps, rs, accumulate_dx);
-        hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)part,
-                           (float*)dw_dev, n, CO * C, 1.0f);
-        return APZ_OK;
-    });
+    return conv1x1_bwd2(e, x_dev, w1_dev, dy1_dev, CO1, w2_dev, dy2_dev, CO2, dx_dev, dw_dev, n, C, layout, 0, nullptr,
+                        accumulate_dx, stream);
 }
 
 // ... on the S x S window of a padded-row trunk tensor (framed boards): the same two kernels with H = W = side on planes of
@@ -2437,38 +2471,14 @@ int apz_conv1x1_bwd2(apz_engine* e, const void* x_dev, const void* w1_dev, const
 // side .. 15 zero), rows side .. 14 are NOT -- apz_bn_bwd_frame, the consumer, selects them away.
 int apz_conv1x1_fwd_frame(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, void* y_dev, int n, int C,
                           int CO, int side, void* stream) {
-    if (!e || !x_dev || !w_dev || !y_dev || n < 1 || C < 1 || C > 1024 || CO < 1 || CO > 8) return fail(APZ_E_ARG, "bad argument");
-    if (int rc = frame_train_check(e, side, "conv1x1_fwd_frame")) return rc;
-    return train_call(e, stream, [&]() -> int {
-        const int lds = (CO * C + 4 * 8 * 64) * (int)sizeof(float);
-        if (int rc = need_lds(e, (const void*)apz::conv1x1_fwd_kernel, lds)) return rc;
-        hipLaunchKernelGGL(apz::conv1x1_fwd_kernel, dim3(n, (side * side + 63) / 64), dim3(256), lds, e->stream,
-                           (const float*)x_dev, (const float*)w_dev, (const float*)bias_dev, (float*)y_dev, C, CO, side, side,
-                           apz::Frame15::GPLANE, apz::Frame15::GROW);
-        return APZ_OK;
-    });
+    return conv1x1_fwd(e, x_dev, w_dev, bias_dev, y_dev, n, C, CO, APZ_LAYOUT_ROWS16, side, "conv1x1_fwd_frame", stream);
 }
 
 int apz_conv1x1_bwd2_frame(apz_engine* e, const void* x_dev, const void* w1_dev, const void* dy1_dev, int CO1, const void* w2_dev,
                            const void* dy2_dev, int CO2, void* dx_dev, void* dw_dev, int n, int C, int side, int accumulate_dx,
                            void* stream) {
-    if (!e || !x_dev || !w1_dev || !dy1_dev || !dw_dev || n < 1 || C < 1 || C > 1024 || CO1 < 1 || CO2 < 0 || CO1 + CO2 > 8 ||
-        (CO2 > 0 && (!w2_dev || !dy2_dev)))
-        return fail(APZ_E_ARG, "bad argument");
-    if (int rc = frame_train_check(e, side, "conv1x1_bwd2_frame")) return rc;
-    return train_call(e, stream, [&]() -> int {
-        const int P = side * side, CO = CO1 + CO2;
-        if (int rc = e->head_scratch.reserve((size_t)n * CO * C * sizeof(float))) return rc;
-        float* part = e->head_scratch.as<float>();      // dw per board
-        const int lds = (CO * 32 + CO * P) * (int)sizeof(float);
-        if (int rc = need_lds(e, (const void*)apz::conv1x1_bwd_kernel, lds)) return rc;
-        hipLaunchKernelGGL(apz::conv1x1_bwd_kernel, dim3(n, (C + 31) / 32), dim3(256), lds, e->stream, (const float*)x_dev,
-                           (const float*)w1_dev, (const float*)dy1_dev, (const float*)w2_dev, (const float*)dy2_dev, (float*)dx_dev,
-                           part, C, CO1, CO2, side, side, apz::Frame15::GPLANE, apz::Frame15::GROW, accumulate_dx);
-        hipLaunchKernelGGL(apz::colsum_kernel, dim3((CO * C + 63) / 64), dim3(256), 0, e->stream, (const float*)part,
-                           (float*)dw_dev, n, CO * C, 1.0f);
-        return APZ_OK;
-    });
+    return conv1x1_bwd2(e, x_dev, w1_dev, dy1_dev, CO1, w2_dev, dy2_dev, CO2, dx_dev, dw_dev, n, C, APZ_LAYOUT_ROWS16, side,
+                        "conv1x1_bwd2_frame", accumulate_dx, stream);
 }
 
 int apz_bias_grad(apz_engine* e, const void* dy_dev, void* db_dev, int n, int C, int layout, void* stream) {

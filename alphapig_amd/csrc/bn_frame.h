@@ -1,21 +1,32 @@
-// The four padded-row BatchNorm kernels of conv_train.h for framed boards (csrc/frame15.h): the training step of a
-// board of side S < 15 on the 15x15 trunk kernels.
+// Padded-row BatchNorm, whole board or framed: the four passes of the training step on the trunk's layout
+// [n][C][15][16] (plane = 60 float4), each one kernel body on a compile-time board policy.
 //
-// The trunk's convolutions and their data gradients write whole 15x15 planes, so every tensor a BatchNorm pass reads
-// may hold anything in its off-board cells (bias-and-neighbour values after a convolution; uninitialised memory, NaN
-// and inf included, in the rows the heads' backward pass never writes).  What a convolution READS must be zero there.
-// The mask therefore sits in these four passes and nowhere else:
+//  bn_stats_rows_kernel        per-(channel, split) sums of x and x^2
+//  bn_apply_rows_kernel        y = act(x sc + shift (+ resid)) and the ReLU byte mask
+//  bn_bwd_reduce_rows_kernel   per-(channel, split) sums of dz and dz xhat
+//  bn_bwd_apply_rows_kernel    dx and dres; dxsum / dxmax per split
 //
-//  bn_stats_frame_kernel        sums over on-board cells only (the caller's count is n S S)
-//  bn_apply_frame_kernel        y and the ReLU byte mask: off-board cells exactly +0 / bit 0
-//  bn_bwd_reduce_frame_kernel   dz and xhat selected before they are summed (relu = 0 has no ReLU bit to hide behind)
-//  bn_bwd_apply_frame_kernel    dx and dres: off-board cells exactly +0; dxsum / dxmax from the masked values
+// 16-byte accesses, no per-element index division; a workgroup walks four boards per trip (4 x 60 of its 256 threads), and
+// a thread owns one float4 index k of a plane for the whole launch (row k >> 2, columns 4 (k & 3) .. + 3).
 //
-// Masking is by selection (keep ? v : 0), never by multiplication: 0 * NaN is NaN.  A thread owns one float4 index k of
-// the 60 of a plane for the whole launch (row k >> 2, columns 4 (k & 3) .. + 3), so its mask is four bits computed once:
-// bit e = [row < S and 4 (k & 3) + e < S].  S = 15 gives conv_train.h's pad-column rule, and with it those kernels' bits:
-// the operation order within a thread, the block_sum_256 / channel_sums tree, the grid and the 16-byte accesses are
-// theirs.  S is a runtime argument: one code object per kernel serves every size.
+// Board15 is the 15x15 board: the pad elements are zero on input, so they add nothing to any sum, and are written back
+// as zero (the pad-column rule (k & 3) == 3); nothing else is selected.  The policy is empty: one argument byte nobody reads.
+//
+// BoardFrame is a board of side S < 15 on the 15x15 trunk kernels (csrc/frame15.h).  The trunk's convolutions and their
+// data gradients write whole 15x15 planes, so every tensor a BatchNorm pass reads may hold anything in its off-board cells
+// (bias-and-neighbour values after a convolution; uninitialised memory, NaN and inf included, in the rows the heads'
+// backward pass never writes).  What a convolution READS must be zero there.  The mask therefore sits in these four
+// passes and nowhere else:
+//
+//  statistics       sums over on-board cells only (the caller's count is n S S)
+//  apply            y and the ReLU byte mask: off-board cells exactly +0 / bit 0
+//  backward reduce  dz and xhat selected before they are summed (relu = 0 has no ReLU bit to hide behind)
+//  backward apply   dx and dres: off-board cells exactly +0; dxsum / dxmax from the masked values
+//
+// Masking is by selection (keep ? v : 0), never by multiplication: 0 * NaN is NaN.  A thread's mask is four bits computed
+// once: bit e = [row < S and 4 (k & 3) + e < S].  S = 15 gives the pad-column rule, and with it Board15's bits: the
+// operation order within a thread, the block_sum_256 / channel_sums tree, the grid and the 16-byte accesses are the same.
+// S is a runtime argument: one code object per kernel serves every size.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,16 +49,44 @@ __device__ __forceinline__ f32x4 frame_select(f32x4 v, unsigned keep) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void bn_stats_frame_kernel(const float* __restrict__ x, double* __restrict__ part, int n, int C,
-                                                             int S) {
+struct Board15 {
+    static constexpr bool FRAME = false;
+    __device__ __forceinline__ unsigned keep_bits(int) const { return 0; }      // (not looked at)
+};
+struct BoardFrame {
+    static constexpr bool FRAME = true;
+    int S;                                   // the board's side
+    __device__ __forceinline__ unsigned keep_bits(int k) const { return frame_keep_bits(k, S); }
+};
+
+// what a pass reads before it sums: the framed board's cells only (Board15: the pad elements are zero already)
+template <class B>
+__device__ __forceinline__ f32x4 rows_read(f32x4 v, unsigned keep) {
+    if constexpr (B::FRAME) return frame_select(v, keep);
+    return v;
+}
+
+// what a pass writes: off the board (the pad column included) exactly +0
+template <class B>
+__device__ __forceinline__ f32x4 rows_written(f32x4 v, unsigned keep, int k) {
+    if constexpr (B::FRAME) return frame_select(v, keep);
+    if ((k & 3) == 3) v[3] = 0.f;            // the pad column (60 float4 per plane: 4 per row)
+    return v;
+}
+
+template <class B>
+__global__ __launch_bounds__(256) void bn_stats_rows_kernel(const float* __restrict__ x, double* __restrict__ part, int n, int C,
+                                                            B board) {
     __shared__ double sh[4];
     const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;   // 4 boards per trip, 60 float4 each
-    const unsigned keep = frame_keep_bits(k, S);
+    const unsigned keep = board.keep_bits(k);
     double s1 = 0.0, s2 = 0.0;
     if (sub < 4)
         for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
-            const f32x4 v = frame_select(reinterpret_cast<const f32x4*>(x + ((size_t)b * C + c) * 240)[k], keep);
-            const double d0 = v[0], d1 = v[1], d2 = v[2], d3 = v[3];      // (squares and sums in double: bn_stats_r16_kernel)
+            const f32x4 v = rows_read<B>(reinterpret_cast<const f32x4*>(x + ((size_t)b * C + c) * 240)[k], keep);
+            // squares and sums in double, as bn_stats_kernel: an fp32 (v0^2 + v1^2) + ... loses (1 + mean^2 / var) ulps of the
+            // variance to the cancellation in sum x^2 / M - mean^2 (the kernel is bound by its loads)
+            const double d0 = v[0], d1 = v[1], d2 = v[2], d3 = v[3];
             s1 += (d0 + d1) + (d2 + d3);
             s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
@@ -59,18 +98,19 @@ __global__ __launch_bounds__(256) void bn_stats_frame_kernel(const float* __rest
     }
 }
 
-__global__ __launch_bounds__(256) void bn_apply_frame_kernel(const float* __restrict__ x, const float* __restrict__ resid,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const double* __restrict__ part, int psplits, BnFinal fin,
-                                                             float* __restrict__ y, unsigned char* __restrict__ mask, int n,
-                                                             int C, int relu, int S) {
+template <class B>
+__global__ __launch_bounds__(256) void bn_apply_rows_kernel(const float* __restrict__ x, const float* __restrict__ resid,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const double* __restrict__ part, int psplits, BnFinal fin,
+                                                            float* __restrict__ y, unsigned char* __restrict__ mask, int n,
+                                                            int C, int relu, B board) {
     __shared__ double sh[4];
     const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
     float m, is;
     channel_stats(part, c, psplits, sh, fin, m, is);
     const float sc = is * (gamma ? gamma[c] : 1.f), shf = beta[c] - m * sc;
     if (sub >= 4) return;
-    const unsigned keep = frame_keep_bits(k, S);
+    const unsigned keep = board.keep_bits(k);
     for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
         const size_t o = ((size_t)b * C + c) * 60 + k;
         f32x4 a = reinterpret_cast<const f32x4*>(x)[o];
@@ -80,16 +120,22 @@ __global__ __launch_bounds__(256) void bn_apply_frame_kernel(const float* __rest
 #pragma unroll
             for (int e = 0; e < 4; e++) a[e] = fmaxf(a[e], 0.f);
         }
-        a = frame_select(a, keep);               // off the board (the pad column included): exactly +0
+        a = rows_written<B>(a, keep, k);
         reinterpret_cast<f32x4*>(y)[o] = a;
+        // the ReLU decisions of these four elements for the backward pass: one byte per 16 bytes of y (bn_bwd_* then read
+        // 3.9 MB instead of the 63 MB output tensor per 512-board layer, twice)
         if (mask) mask[o] = (unsigned char)((a[0] > 0.f) | ((a[1] > 0.f) << 1) | ((a[2] > 0.f) << 2) | ((a[3] > 0.f) << 3));
     }
 }
 
-// dz of one float4: dy behind the ReLU decision (the byte mask, else the forward output), then behind the board mask
-__device__ __forceinline__ f32x4 frame_dz(const float* __restrict__ dy, const float* __restrict__ out,
-                                          const unsigned char* __restrict__ mask, size_t o, int relu, unsigned keep) {
+// dz of one float4: dy behind the ReLU decision (the byte mask, else the forward output), then behind the board mask; and
+// the float4 of x beside it -> xv.  Board15 issues both loads in front of the ReLU branch, BoardFrame loads x behind the
+// selection: the order each kernel has always had, kept so that its device code stays what was measured.
+template <class B>
+__device__ __forceinline__ f32x4 rows_dz(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ out,
+                                         const unsigned char* __restrict__ mask, size_t o, int relu, unsigned keep, f32x4& xv) {
     f32x4 g = reinterpret_cast<const f32x4*>(dy)[o];
+    if constexpr (!B::FRAME) xv = reinterpret_cast<const f32x4*>(x)[o];
     if (relu && mask) {
         const unsigned bits = mask[o];
 #pragma unroll
@@ -99,30 +145,39 @@ __device__ __forceinline__ f32x4 frame_dz(const float* __restrict__ dy, const fl
 #pragma unroll
         for (int e = 0; e < 4; e++) g[e] = ov[e] > 0.f ? g[e] : 0.f;
     }
-    return frame_select(g, keep);
+    g = rows_read<B>(g, keep);
+    if constexpr (B::FRAME) xv = reinterpret_cast<const f32x4*>(x)[o];
+    return g;
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_reduce_frame_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                  const float* __restrict__ out, const float* __restrict__ mean,
-                                                                  const float* __restrict__ invstd, double* __restrict__ part,
-                                                                  const unsigned char* __restrict__ mask, int n, int C, int relu,
-                                                                  int S) {
+// xhat of element e as the backward sums take it: off the framed board 0 (0 * NaN is NaN: x is selected too)
+template <class B>
+__device__ __forceinline__ float rows_xhat(float x, float m, float is, unsigned keep, int e) {
+    if constexpr (B::FRAME) return (keep >> e) & 1u ? (x - m) * is : 0.f;
+    return (x - m) * is;
+}
+
+template <class B>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_rows_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                 const float* __restrict__ out, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, double* __restrict__ part,
+                                                                 const unsigned char* __restrict__ mask, int n, int C, int relu,
+                                                                 B board) {
     __shared__ double sh[4];
     const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
-    const unsigned keep = frame_keep_bits(k, S);
+    const unsigned keep = board.keep_bits(k);
     const float m = mean[c], is = invstd[c];
     double s1 = 0.0, s2 = 0.0;
     if (sub < 4)
         for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
             const size_t o = ((size_t)b * C + c) * 60 + k;
-            const f32x4 g = frame_dz(dy, out, mask, o, relu, keep);
-            const f32x4 xv = reinterpret_cast<const f32x4*>(x)[o];
+            f32x4 xv;
+            const f32x4 g = rows_dz<B>(dy, x, out, mask, o, relu, keep, xv);
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                const float xhat = (keep >> e) & 1u ? (xv[e] - m) * is : 0.f;     // (0 * NaN is NaN: x is selected too)
                 a1 += g[e];
-                a2 += g[e] * xhat;
+                a2 += g[e] * rows_xhat<B>(xv[e], m, is, keep, e);
             }
             s1 += a1;
             s2 += a2;
@@ -135,18 +190,19 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_frame_kernel(const float* _
     }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_frame_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                 const float* __restrict__ out, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                 const double* __restrict__ part, int psplits,
-                                                                 float* __restrict__ dx, float* __restrict__ dres,
-                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                 float* __restrict__ dxsum, int dxsum_ld,
-                                                                 const unsigned char* __restrict__ mask, int n, int C, int relu,
-                                                                 double M, float* __restrict__ dxmax, int S) {
+template <class B>
+__global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                const float* __restrict__ out, const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const double* __restrict__ part, int psplits,
+                                                                float* __restrict__ dx, float* __restrict__ dres,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                float* __restrict__ dxsum, int dxsum_ld,
+                                                                const unsigned char* __restrict__ mask, int n, int C, int relu,
+                                                                double M, float* __restrict__ dxmax, B board) {
     __shared__ double sh[4];
     const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
-    const unsigned keep = frame_keep_bits(k, S);
+    const unsigned keep = board.keep_bits(k);
     double s1, s2;
     channel_sums(part, c, psplits, sh, s1, s2);
     if (blockIdx.y == 0 && t == 0) {
@@ -160,12 +216,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_frame_kernel(const float* __
     if (sub < 4)
         for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
             const size_t o = ((size_t)b * C + c) * 60 + k;
-            const f32x4 g = frame_dz(dy, out, mask, o, relu, keep);
-            const f32x4 xv = reinterpret_cast<const f32x4*>(x)[o];
+            f32x4 xv;
+            f32x4 g = rows_dz<B>(dy, x, out, mask, o, relu, keep, xv);
             f32x4 r;
 #pragma unroll
             for (int e = 0; e < 4; e++) r[e] = gi * (g[e] - k0 - (xv[e] - m) * is * k1);
-            r = frame_select(r, keep);           // gradients do not flow back over the board's edge
+            r = rows_written<B>(r, keep, k);     // gradients do not flow back over the board's edge
+            g = rows_written<B>(g, keep, k);     // (BoardFrame: selected in rows_dz already)
             reinterpret_cast<f32x4*>(dx)[o] = r;
             if (dres) reinterpret_cast<f32x4*>(dres)[o] = g;
             ds += (double)((r[0] + r[1]) + (r[2] + r[3]));
@@ -175,7 +232,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_frame_kernel(const float* __
         ds = block_sum_256(ds, sh);
         if (t == 0) dxsum[(size_t)blockIdx.y * dxsum_ld + c] = (float)ds;
     }
-    if (dxmax) {   // [split][C]: max |dx| of this workgroup
+    if (dxmax) {   // [split][C]: max |dx| of this workgroup (the input scale of trunk15_wino3h16_train_kernel's data gradient)
         dm = block_max_256(dm, reinterpret_cast<float*>(sh));
         if (t == 0) dxmax[(size_t)blockIdx.y * C + c] = dm;
     }

@@ -355,151 +355,6 @@ __global__ __launch_bounds__(256) void adam_step_unless_kernel(const AdamTensor*
     adam_step_body(tab, lr_t, b1, b2, eps, rescale);
 }
 
-// ---- the same four kernels for the padded-row layout (plane = 60 float4; pad elements are zero on input, so
-// they add nothing to any sum, and are written back as zero): 16-byte accesses, no per-element index division;
-// a workgroup walks four boards per trip (4 x 60 of its 256 threads)
-__global__ __launch_bounds__(256) void bn_stats_r16_kernel(const float* __restrict__ x, double* __restrict__ part, int n, int C) {
-    __shared__ double sh[4];
-    const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;   // 4 boards per trip, 60 float4 each
-    double s1 = 0.0, s2 = 0.0;
-    if (sub < 4)
-        for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x + ((size_t)b * C + c) * 240)[k];
-            // squares and sums in double, as bn_stats_kernel: an fp32 (v0^2 + v1^2) + ... loses (1 + mean^2 / var) ulps of the
-            // variance to the cancellation in sum x^2 / M - mean^2 (the kernel is bound by its loads)
-            const double d0 = v[0], d1 = v[1], d2 = v[2], d3 = v[3];
-            s1 += (d0 + d1) + (d2 + d3);
-            s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-    s1 = block_sum_256(s1, sh);
-    s2 = block_sum_256(s2, sh);
-    if (t == 0) {
-        part[2 * ((size_t)c * gridDim.y + blockIdx.y)] = s1;
-        part[2 * ((size_t)c * gridDim.y + blockIdx.y) + 1] = s2;
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_apply_r16_kernel(const float* __restrict__ x, const float* __restrict__ resid,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           const double* __restrict__ part, int psplits, BnFinal fin,
-                                                           float* __restrict__ y, unsigned char* __restrict__ mask, int n, int C,
-                                                           int relu) {
-    __shared__ double sh[4];
-    const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
-    float m, is;
-    channel_stats(part, c, psplits, sh, fin, m, is);
-    const float sc = is * (gamma ? gamma[c] : 1.f), shf = beta[c] - m * sc;
-    if (sub >= 4) return;
-    for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
-        const size_t o = ((size_t)b * C + c) * 60 + k;
-        f32x4 a = reinterpret_cast<const f32x4*>(x)[o];
-        a = a * sc + shf;
-        if (resid) a += reinterpret_cast<const f32x4*>(resid)[o];
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) a[e] = fmaxf(a[e], 0.f);
-        }
-        if ((k & 3) == 3) a[3] = 0.f;            // the pad column (60 float4 per plane: 4 per row)
-        reinterpret_cast<f32x4*>(y)[o] = a;
-        // the ReLU decisions of these four elements for the backward pass: one byte per 16 bytes of y (bn_bwd_* then read
-        // 3.9 MB instead of the 63 MB output tensor per 512-board layer, twice)
-        if (mask) mask[o] = (unsigned char)((a[0] > 0.f) | ((a[1] > 0.f) << 1) | ((a[2] > 0.f) << 2) | ((a[3] > 0.f) << 3));
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_reduce_r16_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                const float* __restrict__ out, const float* __restrict__ mean,
-                                                                const float* __restrict__ invstd, double* __restrict__ part,
-                                                                const unsigned char* __restrict__ mask, int n, int C, int relu) {
-    __shared__ double sh[4];
-    const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
-    const float m = mean[c], is = invstd[c];
-    double s1 = 0.0, s2 = 0.0;
-    if (sub < 4)
-        for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
-            const size_t o = ((size_t)b * C + c) * 60 + k;
-            f32x4 g = reinterpret_cast<const f32x4*>(dy)[o];
-            const f32x4 xv = reinterpret_cast<const f32x4*>(x)[o];
-            if (relu && mask) {
-                const unsigned bits = mask[o];
-#pragma unroll
-                for (int e = 0; e < 4; e++) g[e] = (bits >> e) & 1u ? g[e] : 0.f;
-            } else if (relu) {
-                const f32x4 ov = reinterpret_cast<const f32x4*>(out)[o];
-#pragma unroll
-                for (int e = 0; e < 4; e++) g[e] = ov[e] > 0.f ? g[e] : 0.f;
-            }
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                a1 += g[e];
-                a2 += g[e] * ((xv[e] - m) * is);
-            }
-            s1 += a1;
-            s2 += a2;
-        }
-    s1 = block_sum_256(s1, sh);
-    s2 = block_sum_256(s2, sh);
-    if (t == 0) {
-        part[2 * ((size_t)c * gridDim.y + blockIdx.y)] = s1;
-        part[2 * ((size_t)c * gridDim.y + blockIdx.y) + 1] = s2;
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_r16_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                               const float* __restrict__ out, const float* __restrict__ gamma,
-                                                               const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                               const double* __restrict__ part, int psplits,
-                                                               float* __restrict__ dx, float* __restrict__ dres,
-                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               float* __restrict__ dxsum, int dxsum_ld,
-                                                               const unsigned char* __restrict__ mask, int n, int C, int relu,
-                                                               double M, float* __restrict__ dxmax) {
-    __shared__ double sh[4];
-    const int c = blockIdx.x, t = threadIdx.x, sub = t / 60, k = t - sub * 60;
-    double s1, s2;
-    channel_sums(part, c, psplits, sh, s1, s2);
-    if (blockIdx.y == 0 && t == 0) {
-        if (dbeta) dbeta[c] = (float)s1;
-        if (dgamma) dgamma[c] = (float)s2;
-    }
-    const float m = mean[c], is = invstd[c], k0 = (float)(s1 / M), k1 = (float)(s2 / M);
-    const float gi = (gamma ? gamma[c] : 1.f) * is;
-    double ds = 0.0;
-    float dm = 0.f;
-    if (sub < 4)
-        for (int b = blockIdx.y * 4 + sub; b < n; b += gridDim.y * 4) {
-            const size_t o = ((size_t)b * C + c) * 60 + k;
-            f32x4 g = reinterpret_cast<const f32x4*>(dy)[o];
-            const f32x4 xv = reinterpret_cast<const f32x4*>(x)[o];
-            if (relu && mask) {
-                const unsigned bits = mask[o];
-#pragma unroll
-                for (int e = 0; e < 4; e++) g[e] = (bits >> e) & 1u ? g[e] : 0.f;
-            } else if (relu) {
-                const f32x4 ov = reinterpret_cast<const f32x4*>(out)[o];
-#pragma unroll
-                for (int e = 0; e < 4; e++) g[e] = ov[e] > 0.f ? g[e] : 0.f;
-            }
-            f32x4 r;
-#pragma unroll
-            for (int e = 0; e < 4; e++) r[e] = gi * (g[e] - k0 - (xv[e] - m) * is * k1);
-            if ((k & 3) == 3) r[3] = 0.f, g[3] = 0.f;
-            reinterpret_cast<f32x4*>(dx)[o] = r;
-            if (dres) reinterpret_cast<f32x4*>(dres)[o] = g;
-            ds += (double)((r[0] + r[1]) + (r[2] + r[3]));
-            if (dxmax) dm = fmaxf(dm, fmaxf(fmaxf(fabsf(r[0]), fabsf(r[1])), fmaxf(fabsf(r[2]), fabsf(r[3]))));
-        }
-    if (dxsum) {
-        ds = block_sum_256(ds, sh);
-        if (t == 0) dxsum[(size_t)blockIdx.y * dxsum_ld + c] = (float)ds;
-    }
-    if (dxmax) {   // [split][C]: max |dx| of this workgroup (the input scale of trunk15_wino3h16_train_kernel's data gradient)
-        dm = block_max_256(dm, reinterpret_cast<float*>(sh));
-        if (t == 0) dxmax[(size_t)blockIdx.y * C + c] = dm;
-    }
-}
-
 template <int H, int W, bool R16 = false>
 struct WgradGeo {
     static constexpr int WP = R16 ? 16 : W;                         // stored row length (padded-row layout: 16)

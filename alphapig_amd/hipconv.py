@@ -303,10 +303,10 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, resid=None, relu=True, layout=DENS
         _ck(L, L.apz_bn_fwd_frame(hnd, x.data_ptr(), _ptr(resid), _ptr(gamma), beta.data_ptr(), _ptr(run_mean), _ptr(run_var),
                                   y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(mask), n, c, layout, int(relu), momentum,
                                   eps, _frame_side(side, layout, stats), stream))
-        return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
-    _ck(L, L.apz_bn_fwd_stats(hnd, x.data_ptr(), _ptr(resid), _ptr(gamma), beta.data_ptr(), _ptr(run_mean), _ptr(run_var),
-                              y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(stats), _ptr(mask), n, c, layout, int(relu),
-                              momentum, eps, stream))
+    else:
+        _ck(L, L.apz_bn_fwd_stats(hnd, x.data_ptr(), _ptr(resid), _ptr(gamma), beta.data_ptr(), _ptr(run_mean), _ptr(run_var),
+                                  y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(stats), _ptr(mask), n, c, layout,
+                                  int(relu), momentum, eps, stream))
     return (y, mean, invstd, mask) if want_mask else (y, mean, invstd)
 
 
@@ -339,10 +339,10 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
         _ck(L, L.apz_bn_bwd_frame(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(),
                                   invstd.data_ptr(), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld,
                                   _ptr(dxmax), n, c, layout, int(relu), _frame_side(side, layout), stream))
-        return dx, dres, dgamma, dbeta
-    _ck(L, L.apz_bn_bwd_max(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(), invstd.data_ptr(),
-                            dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld, _ptr(dxmax), n, c,
-                            layout, int(relu), stream))
+    else:
+        _ck(L, L.apz_bn_bwd_max(hnd, dy.data_ptr(), x.data_ptr(), _ptr(y), _ptr(mask), _ptr(gamma), mean.data_ptr(),
+                                invstd.data_ptr(), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dxsum), ld,
+                                _ptr(dxmax), n, c, layout, int(relu), stream))
     return dx, dres, dgamma, dbeta
 
 

@@ -240,8 +240,9 @@ int apz_bn_fwd_stats(apz_engine *e, const void *x_dev, const void *resid_dev, co
  *               sums (apz_colsum) are the bias gradient of the convolution that produced x; a caller with
  *               several layers gives each its own C columns of one matrix and adds them all in one launch.
  * Channel sums: double precision, per (channel, batch split) partials (no atomics) that every consumer workgroup
- * adds in a fixed order (csrc/conv_train.h) -- two launches per call, the same bits on every run.  The training
- * entry points share per-engine scratch: calls on one engine must be ordered by ONE stream at a time.
+ * adds in a fixed order (csrc/conv_train.h; the padded-row passes: csrc/bn_frame.h) -- two launches per call, the same bits
+ * on every run.  The training entry points share per-engine scratch: calls on one engine must be ordered by ONE stream at a
+ * time.
  *   apz_colsum  out[j] = scale * sum_i in[i][j] over rows x cols floats, fixed order (double accumulation) */
 int apz_bn_fwd(apz_engine *e, const void *x_dev, const void *resid_dev, const void *gamma_dev,
                const void *beta_dev, void *run_mean_dev, void *run_var_dev, void *y_dev, void *mean_dev,

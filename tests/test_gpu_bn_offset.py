@@ -1,5 +1,5 @@
 """Training-mode BatchNorm on channels with an offset: x[:, c] = sigma_c (randn + r), r = |mean| / std up to 100, on the four
-routes to the statistics -- bn_stats_kernel (dense), bn_stats_r16_kernel (padded rows), and the epilogues of the two trunk
+routes to the statistics -- bn_stats_kernel (dense), bn_stats_rows_kernel (padded rows), and the epilogues of the two trunk
 convolutions (conv3x3_fwd_stats, conv3x3_fwd_stats_f16x2), where the convolution's bias makes the offset.  Float64 reference
 on the CPU from the same float32 tensors; the bars are tests/test_bn_stat_bounds.py's (derived from the arithmetic, u = 2^-24):
 flat in r for the routes that square and add in double, (12.5 (1 + r^2) + 2) u of invstd for the per-board fp32 trees.
@@ -106,7 +106,7 @@ def _run(x, layout, bars, r, g, stats=None, label=""):
     if r <= 3:
         prop_y = np.zeros_like(prop_y)
         prop_dx = np.zeros_like(prop_y)
-    elif layout == 1:        # bn_apply_r16_kernel folds the shift: y = x sc + (beta - mean sc)
+    elif layout == 1:        # bn_apply_rows_kernel folds the shift: y = x sc + (beta - mean sc)
         fold = 2 * U * np.abs(ga64) * np.abs(m64) / np.sqrt(v64)
         prop_y = prop_y + fold
         prop_dx = None if prop_dx is None else prop_dx + fold
@@ -132,7 +132,7 @@ def _run(x, layout, bars, r, g, stats=None, label=""):
 @pytest.mark.parametrize("r", LADDER)
 @pytest.mark.parametrize("layout,n,c", [(0, 7, 128), (0, 7, 4), (1, 9, 128)])
 def test_own_statistics_pass(layout, n, c, r):
-    """bn_stats_kernel / bn_stats_r16_kernel (9 boards: three splits, the last trip of four boards holds one): sums and
+    """bn_stats_kernel / bn_stats_rows_kernel (9 boards: three splits, the last trip of four boards holds one): sums and
     squares in double, so invstd to 4 u and the mean to 2 u whatever the offset."""
     from alphapig_amd import hipconv
     x = torch.from_numpy(offset_channels(np.random.RandomState(100 * r + 10 * layout + c), n, c, r))

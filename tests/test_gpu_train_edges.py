@@ -113,7 +113,7 @@ def layer3():
 @pytest.mark.parametrize("layout", [0, 1])
 def test_constant_channels(layout):
     """Channel 3 is 0 everywhere, channel 7 is 3.5 (variance exactly 0: invstd = 1 / sqrt(eps), y = beta), channel 11 is
-    constant on every board but differs between boards.  On padded rows bn_apply_r16_kernel folds the shift,
+    constant on every board but differs between boards.  On padded rows bn_apply_rows_kernel folds the shift,
     y = x sc + (beta - mean sc): y = beta up to the two roundings of mean sc (2 u |gamma| |mean| invstd); dense: exactly.
     ((x - mean) sc + beta there would give exactly beta too, as the dense kernel does; not chosen: it would change the bits
     of every padded-row BatchNorm output for one more operation per element.)"""

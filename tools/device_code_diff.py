@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of apz_engine.hip between two source trees, kernel by kernel.
 
-    tools/device_code_diff.py <tree A> <tree B> [--keep DIR]
+    tools/device_code_diff.py <tree A> <tree B> [--keep DIR] [--rename OLD=NEW ...]
 
 A tree is a checkout (or an export of one) with alphapig_amd/csrc and include/, or the a.s / b.s that an earlier run left
 under --keep.  Each tree's apz_engine.hip is compiled
@@ -11,6 +11,9 @@ one verdict:
     scalar-only  the same number of instructions and the same count per mnemonic, the same sequence of non-scalar
                  instructions once SGPR operands are masked, and the same resource metadata (registers, spills, LDS, scratch)
     different    anything else, a kernel that exists on one side only included
+--rename OLD=NEW (repeatable): kernel OLD of tree A is compared with kernel NEW of tree B and listed as "OLD -> NEW", instead
+of one gone and one added.  Both are demangled names without arguments and without a template's "void " in front, e.g.
+apz::bn_stats_r16_kernel='apz::bn_stats_rows_kernel<apz::Board15>'.
 Exit status 1 if any kernel is "different".  CPU only: nothing here runs a kernel.
 """
 import collections
@@ -80,22 +83,46 @@ def verdict(a, b):
     return "different"
 
 
+def plain(symbol):
+    """mangled symbol -> demangled name without arguments"""
+    demangled = subprocess.run(["c++filt", symbol], capture_output=True, text=True).stdout.strip() or symbol
+    return demangled.split("(")[0]
+
+
+def bare(name):
+    """... without the return type that a template's name carries"""
+    return name[5:] if name.startswith("void ") else name
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--keep"]
-    keep = sys.argv[sys.argv.index("--keep") + 1] if "--keep" in sys.argv else None
-    if keep:
-        args.remove(keep)
+    args, renames, keep = [], {}, None
+    argv = sys.argv[1:]
+    while argv:
+        a = argv.pop(0)
+        if a == "--keep" and argv:
+            keep = argv.pop(0)
+        elif a == "--rename" and argv and "=" in argv[0]:
+            old, new = argv.pop(0).split("=", 1)
+            renames[old] = new
+        else:
+            args.append(a)
     if len(args) != 2:
         sys.exit(__doc__)
     work = keep or tempfile.mkdtemp(prefix="device_code_diff_")
     os.makedirs(work, exist_ok=True)
     ka, kb = (kernels(assemble(t, os.path.join(work, n))) for t, n in zip(args, ("a.s", "b.s")))
+    names = {sym: plain(sym) for sym in set(ka) | set(kb)}
+    # A's symbol -> B's symbol: its own, or the one whose name the rename gives
+    b_by_name = {bare(names[sym]): sym for sym in kb}
+    partner = {sym: b_by_name.get(renames[bare(names[sym])]) for sym in ka if bare(names[sym]) in renames}
+    missing = (set(renames) - {bare(names[sym]) for sym in partner}) | {renames[bare(names[s])] for s, t in partner.items() if not t}
+    if missing:
+        sys.exit("--rename: no such kernel: %s" % ", ".join(sorted(missing)))
     count = collections.Counter()
-    for name in sorted(set(ka) | set(kb)):
-        v = verdict(ka.get(name), kb.get(name))
+    for sym in sorted((set(ka) | set(kb)) - set(partner.values())):
+        v = verdict(ka.get(sym), kb.get(partner.get(sym, sym)))
         count[v] += 1
-        demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
-        print("%-12s %s" % (v, demangled.split("(")[0]))
+        print("%-12s %s" % (v, names[sym] + (" -> " + names[partner[sym]] if sym in partner else "")))
     print("kernels: %d in A, %d in B; " % (len(ka), len(kb)) + ", ".join("%d %s" % (n, v) for v, n in sorted(count.items())))
     sys.exit(1 if count["different"] else 0)
 

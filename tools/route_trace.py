@@ -4,6 +4,8 @@
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/route_trace.py     (on the GPU, once per tree)
     python tools/route_trace.py --compare A_kernel_trace.csv B_kernel_trace.csv            (on the host)
     python tools/route_trace.py --compare --whole A_kernel_trace.csv B_kernel_trace.csv    (traces of any other run)
+    ... --rename OLD=NEW (repeatable): kernel OLD of trace A counts as NEW, the name it has in B -- names without arguments
+    and without a template's "void " in front, as tools/device_code_diff.py --rename takes them
 
 Bits cannot tell the small-batch trunk kernels from the batched ones (they are bit-equal by contract); the launch sequence
 can.  The run makes one forward per case below: every engine of tests/test_gpu_forward_modes.py at 5 and at 40 boards, every
@@ -85,11 +87,18 @@ def run():
         print("%3d %s" % (k, label), flush=True)
 
 
-def forwards(path, whole=False):
+def forwards(path, whole=False, renames=None):
     """kernel-trace CSV -> {case + 1: [(kernel, grid, workgroup, LDS)] between the case's two sampler launches}
-    (whole: {1: every launch of the trace})"""
+    (whole: {1: every launch of the trace}; renames: see --rename, None = names as the trace has them)"""
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
-    shape = lambda r: (r["Kernel_Name"].split("(")[0],) + tuple(
+
+    def name(r):
+        n = r["Kernel_Name"].split("(")[0]
+        if renames is None:
+            return n
+        n = n[5:] if n.startswith("void ") else n
+        return renames.get(n, n)
+    shape = lambda r: (name(r),) + tuple(
         int(r[c + a]) for c in ("Grid_Size_", "Workgroup_Size_") for a in "XYZ") + (int(r["LDS_Block_Size"]),)
     out, cur = ({1: []}, None) if whole else ({}, None)
     if whole:
@@ -105,8 +114,8 @@ def forwards(path, whole=False):
     return out
 
 
-def compare(a, b, whole=False):
-    fa, fb = forwards(a, whole), forwards(b, whole)
+def compare(a, b, whole=False, renames=None):
+    fa, fb = forwards(a, whole, renames), forwards(b, whole, renames and {})
     bad = 0
     for k in sorted(set(fa) | set(fb)):
         same = fa.get(k) == fb.get(k)
@@ -124,6 +133,8 @@ def compare(a, b, whole=False):
 if __name__ == "__main__":
     if "--compare" in sys.argv:
         i = sys.argv.index("--compare")
-        paths = [a for a in sys.argv[i + 1:] if a != "--whole"]
-        sys.exit(compare(paths[0], paths[1], "--whole" in sys.argv))
+        rest = sys.argv[i + 1:]
+        pairs = [rest[j + 1].split("=", 1) for j, a in enumerate(rest[:-1]) if a == "--rename"]
+        paths = [a for j, a in enumerate(rest) if a not in ("--whole", "--rename") and (j == 0 or rest[j - 1] != "--rename")]
+        sys.exit(compare(paths[0], paths[1], "--whole" in sys.argv, dict(pairs) or None))
     run()
