@@ -131,7 +131,8 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_set_trunk_act_exponents", "apz_get_trunk_act_exponents", "apz_calibrate_trunk_planes", "apz_calibrate_trunk_codes",
                "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host",
                "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys",
-               "apz_bn_fwd_frame", "apz_bn_bwd_frame", "apz_frame_planes_dev", "apz_conv1x1_fwd_frame", "apz_conv1x1_bwd2_frame"]
+               "apz_bn_fwd_frame", "apz_bn_bwd_frame", "apz_frame_planes_dev", "apz_conv1x1_fwd_frame", "apz_conv1x1_bwd2_frame",
+               "apz_set_legal_policy", "apz_get_legal_policy", "apz_occupancy_planes", "apz_pv_loss_legal"]
 
 
 def _one_hip_runtime():
@@ -314,6 +315,10 @@ def hip():
         "apz_frame_planes_dev": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
         "apz_conv1x1_fwd_frame": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "apz_conv1x1_bwd2_frame": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "apz_set_legal_policy": (C.c_int, [vp, C.c_int]),
+        "apz_get_legal_policy": (C.c_int, [vp]),
+        "apz_occupancy_planes": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "apz_pv_loss_legal": (C.c_int, [vp] * 6 + [C.c_int] + [vp] * 6),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -178,6 +178,10 @@ struct apz_engine {
     // apz_set_leaf_symmetry (csrc/leaf_sym.h): what forward_codes_sym puts around forward_from_codes.  APZ_SYM_NONE: nothing.
     int sym_mode = APZ_SYM_NONE;
     uint64_t sym_seed = 0;
+    // apz_set_legal_policy: the heads take their softmax over the empty cells of each board.  The occupancy is the code bytes
+    // of the forward where it was given codes (the heads read them in place); a forward given planes stages it in `occ`.
+    bool legal_policy = false;
+    unsigned char* occ = nullptr;            // [max_batch][hw], allocated by the first call that turns the switch on
     int* perm_pinv = nullptr;                // [8][hw]: perm_pinv[k][perm_p[k][p]] = p, uploaded by the first call that turns a mode on
     // the forward's own input and output under a mode: the image codes, the head's answers on them and the boards' keys --
     // one set per submission slot + one for the synchronous entry points (index APZ_MAX_SLOTS), allocated at first use,
@@ -850,6 +854,15 @@ int run_trunk(apz_engine* e, const FwdMode& m, const float* planes, const unsign
     return APZ_OK;
 }
 
+// planes [n][c_in][H][W] -> occ [n][H*W] (occupancy_planes_kernel, csrc/heads.h) on the engine's stream
+int launch_occupancy_planes(apz_engine* e, const float* planes, int n, int c_in, int H, int W, unsigned char* occ) {
+    const long total = (long)n * H * W;
+    hipLaunchKernelGGL(apz::occupancy_planes_kernel, dim3((int)std::min<long>((total + 255) / 256, e->num_cu * 8)), dim3(256), 0,
+                       e->stream, planes, occ, total, H, W, c_in);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
 void drop_forward_graphs(apz_engine* e) {
     for (auto& kv : e->fwd_graphs) hipGraphExecDestroy(kv.second);
     e->fwd_graphs.clear();
@@ -871,10 +884,31 @@ int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsi
     int rc = run_trunk(e, m, planes, codes_dev, n, (int)e->convs.size() - 1, &trunk);
     if (rc) return rc;
     const int hw = e->hw;
+    // legal policy: byte m of row b of `occ` is non-zero where move m is occupied -- the codes as they are, or the planes'
+    // occupancy staged in e->occ (timed with the head that reads it)
+    const unsigned char* occ = nullptr;
+    int occ_stride = 0;
+    auto stage_occupancy = [&]() -> int {
+        if (!e->legal_policy) return APZ_OK;
+        if (codes_dev) {
+            occ = codes_dev;
+            occ_stride = e->code_stride;
+            return APZ_OK;
+        }
+        if (int rc2 = launch_occupancy_planes(e, planes, n, e->cfg.c_in, e->cfg.height, e->cfg.width, e->occ)) return rc2;
+        occ = e->occ;
+        occ_stride = hw;
+        return APZ_OK;
+    };
     if (e->small8) {                    // both 1x1 convolutions, both FullyConnected layers, softmax and tanh in one launch
         Timed tm(e, APZ_K_HEAD_FC);
-        hipLaunchKernelGGL(apz::head8_kernel, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0, e->stream, trunk, e->w6, e->b6,
-                           e->wfc_raw, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, e->clast);
+        if (int rc2 = stage_occupancy()) return rc2;
+        if (occ)
+            hipLaunchKernelGGL(apz::head8_legal_kernel, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0, e->stream, trunk, e->w6,
+                               e->b6, e->wfc_raw, e->bfc, e->wv, e->bv, occ, occ_stride, probs, values, logits, vlogits, n, e->clast);
+        else
+            hipLaunchKernelGGL(apz::head8_kernel, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0, e->stream, trunk, e->w6, e->b6,
+                               e->wfc_raw, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, e->clast);
         HIP_TRY(hipGetLastError());
         e->last_n = n;
         return APZ_OK;
@@ -897,8 +931,9 @@ int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsi
         const int grid = (n + 15) / 16;
         const int tpw = (ntile + 3) / 4;
         // (framed engines take the two-launch form at every size: at 6x6 and 7x7, hw <= 64, the fused form would be a path
-        // no engine has run before)
-        if (tpw <= 1 && !e->frame_s) {
+        // no engine has run before; the legal policy likewise: the fused softmax has no masked form)
+        if (int rc2 = stage_occupancy()) return rc2;
+        if (tpw <= 1 && !e->frame_s && !occ) {
             if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1>, lds)) return rc2;
             hipLaunchKernelGGL(apz::head_fc_kernel<1>, dim3(grid), dim3(256), lds, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw);
@@ -908,8 +943,12 @@ int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsi
             if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1, true>, lds1)) return rc2;
             hipLaunchKernelGGL((apz::head_fc_kernel<1, true>), dim3(grid, tpw), dim3(256), lds1, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw, e->fc_logits);
-            hipLaunchKernelGGL(apz::head_softmax_value_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits, e->featv,
-                               e->wv, e->bv, probs, values, logits, vlogits, n, hw, ntile * 16);
+            if (occ)
+                hipLaunchKernelGGL(apz::head_softmax_value_legal_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits,
+                                   e->featv, e->wv, e->bv, occ, occ_stride, probs, values, logits, vlogits, n, hw, ntile * 16);
+            else
+                hipLaunchKernelGGL(apz::head_softmax_value_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits,
+                                   e->featv, e->wv, e->bv, probs, values, logits, vlogits, n, hw, ntile * 16);
         } else {
             return fail(APZ_E_UNSUPPORTED, "policy head: board too large");
         }
@@ -1417,6 +1456,7 @@ void apz_destroy(apz_engine* e) {
                             &e->wino_scratch[0], &e->wino_scratch[1]})
         b->release();
     if (e->perm_pinv) hipFree(e->perm_pinv);
+    if (e->occ) hipFree(e->occ);
     for (auto& st : e->sym) {
         void* stage[] = {st.codes, st.k, st.probs, st.values};
         for (void* p : stage)
@@ -2543,23 +2583,54 @@ int apz_dropout(apz_engine* e, const void* x_dev, void* y_dev, int64_t count, fl
     });
 }
 
-int apz_pv_loss(apz_engine* e, const void* logits_dev, const void* vlogit_dev, const void* pi_dev, const void* z_dev, int n,
-                void* loss3_dev, void* dlogits_dev, void* dvlogit_dev, void* probs_dev, void* values_dev, void* stream) {
+// apz_pv_loss (occ_dev == NULL) and apz_pv_loss_legal: the loss kernel of the form, then the batch means
+static int pv_loss_call(apz_engine* e, const void* logits_dev, const void* vlogit_dev, const void* pi_dev, const void* z_dev,
+                        const void* occ_dev, int n, void* loss3_dev, void* dlogits_dev, void* dvlogit_dev, void* probs_dev,
+                        void* values_dev, void* stream) {
     if (!e || !logits_dev || !vlogit_dev || n < 1) return fail(APZ_E_ARG, "bad argument");
     if ((loss3_dev || dlogits_dev || dvlogit_dev) && (!pi_dev || !z_dev)) return fail(APZ_E_ARG, "targets missing");
     if (e->hw > 4096) return fail(APZ_E_UNSUPPORTED, "board too large");
     return train_call(e, stream, [&]() -> int {
         if (int rc = e->head_scratch.reserve((size_t)n * 3 * sizeof(float))) return rc;
         float* part = e->head_scratch.as<float>();      // the three terms per sample
-        hipLaunchKernelGGL(apz::pv_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, (const float*)logits_dev,
-                           (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev, n, e->hw, 1.0f / (float)n,
-                           loss3_dev ? part : (float*)nullptr, (float*)dlogits_dev, (float*)dvlogit_dev, (float*)probs_dev,
-                           (float*)values_dev);
+        float* terms = loss3_dev ? part : (float*)nullptr;
+        const dim3 grid((n + 3) / 4), block(256);
+        if (occ_dev)
+            hipLaunchKernelGGL(apz::pv_loss_legal_kernel, grid, block, 0, e->stream, (const float*)logits_dev,
+                               (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev, (const unsigned char*)occ_dev, n,
+                               e->hw, 1.0f / (float)n, terms, (float*)dlogits_dev, (float*)dvlogit_dev, (float*)probs_dev,
+                               (float*)values_dev);
+        else
+            hipLaunchKernelGGL(apz::pv_loss_kernel, grid, block, 0, e->stream, (const float*)logits_dev, (const float*)vlogit_dev,
+                               (const float*)pi_dev, (const float*)z_dev, n, e->hw, 1.0f / (float)n, terms, (float*)dlogits_dev,
+                               (float*)dvlogit_dev, (float*)probs_dev, (float*)values_dev);
         if (loss3_dev)  // (value loss, policy loss, entropy): batch means, samples summed in index order
             hipLaunchKernelGGL(apz::colsum_kernel, dim3(1), dim3(256), 0, e->stream, (const float*)part, (float*)loss3_dev, n, 3,
                                1.0f / (float)n);
         return APZ_OK;
     });
+}
+
+int apz_pv_loss(apz_engine* e, const void* logits_dev, const void* vlogit_dev, const void* pi_dev, const void* z_dev, int n,
+                void* loss3_dev, void* dlogits_dev, void* dvlogit_dev, void* probs_dev, void* values_dev, void* stream) {
+    return pv_loss_call(e, logits_dev, vlogit_dev, pi_dev, z_dev, nullptr, n, loss3_dev, dlogits_dev, dvlogit_dev, probs_dev,
+                        values_dev, stream);
+}
+
+int apz_pv_loss_legal(apz_engine* e, const void* logits_dev, const void* vlogit_dev, const void* pi_dev, const void* z_dev,
+                      const void* occ_dev, int n, void* loss3_dev, void* dlogits_dev, void* dvlogit_dev, void* probs_dev,
+                      void* values_dev, void* stream) {
+    if (!occ_dev) return fail(APZ_E_ARG, "bad argument");
+    return pv_loss_call(e, logits_dev, vlogit_dev, pi_dev, z_dev, occ_dev, n, loss3_dev, dlogits_dev, dvlogit_dev, probs_dev,
+                        values_dev, stream);
+}
+
+int apz_occupancy_planes(apz_engine* e, const void* planes_dev, int n, int c_in, int H, int W, void* occ_dev, void* stream) {
+    if (!e || !planes_dev || !occ_dev) return fail(APZ_E_ARG, "null argument");
+    if (c_in != 9 && c_in != 4) return fail(APZ_E_ARG, "occupancy: c_in must be 9 or 4");
+    if (n < 0 || H < 1 || W < 1) return fail(APZ_E_ARG, "occupancy: bad batch / board");
+    if (n == 0) return APZ_OK;
+    return train_call(e, stream, [&]() -> int { return launch_occupancy_planes(e, (const float*)planes_dev, n, c_in, H, W, (unsigned char*)occ_dev); });
 }
 
 int apz_layout_convert(apz_engine* e, const void* src_dev, void* dst_dev, int64_t planes, int to_rows16, void* stream) {
@@ -2914,6 +2985,20 @@ int apz_set_leaf_symmetry(apz_engine* e, int mode, uint64_t seed) {
     e->sym_seed = seed;
     return APZ_OK;
 }
+
+int apz_set_legal_policy(apz_engine* e, int on) {
+    if (!e) return fail(APZ_E_ARG, "null engine");
+    EngineLock guard(e->submit_lock);
+    for (const auto& sl : e->slots)
+        if (sl.busy) return fail(APZ_E_STATE, "legal policy: a slot is still in flight: call apz_wait first");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (on && !e->occ) HIP_TRY(hipMalloc((void**)&e->occ, (size_t)e->cfg.max_batch * e->hw));
+    if ((on != 0) != e->legal_policy) drop_forward_graphs(e);      // a captured launch sequence holds the other heads
+    e->legal_policy = on != 0;
+    return APZ_OK;
+}
+
+int apz_get_legal_policy(apz_engine* e) { return e ? (int)e->legal_policy : fail(APZ_E_ARG, "null engine"); }
 
 int apz_get_leaf_symmetry(apz_engine* e, int* mode, uint64_t* seed) {
     if (!e || !mode || !seed) return fail(APZ_E_ARG, "null argument");

@@ -294,4 +294,80 @@ __global__ __launch_bounds__(256) void head8_kernel(const float* __restrict__ x,
     }
 }
 
+// The legal-move form of head8_kernel (apz_set_legal_policy): the softmax over the EMPTY cells only.  occ [n][occ_stride]
+// u8, byte m != 0 where move m is occupied (the position codes, or occupancy_planes_kernel's bytes).  Everything up to the
+// logit is head8_kernel's text; an occupied cell is then left out by selection, so with no stone on the board both kernels
+// run the same operations on the same values, and whatever an occupied logit holds changes no output bit.  Occupied cells
+// get +0; a row without an empty cell is all +0.
+__global__ __launch_bounds__(256) void head8_legal_kernel(const float* __restrict__ x, const float* __restrict__ w6,
+                                                          const float* __restrict__ b6, const float* __restrict__ wfc,
+                                                          const float* __restrict__ bfc, const float* __restrict__ wv,
+                                                          const float* __restrict__ bv, const unsigned char* __restrict__ occ,
+                                                          int occ_stride, float* __restrict__ probs, float* __restrict__ values,
+                                                          float* __restrict__ logits_out, float* __restrict__ vlogits_out, int n,
+                                                          int C) {
+    __shared__ float part[4][6][64];
+    __shared__ __attribute__((aligned(16))) float feat[6 * 64];
+    __shared__ float fcp[4][64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cq = C >> 2;
+    for (int b = blockIdx.x; b < n; b += gridDim.x) {
+        {
+            const float* xb = x + ((size_t)b * C + wave * cq) * 64 + lane;
+            const float* wq = w6 + wave * cq;
+            float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int c0 = 0; c0 < cq; c0 += 16) {
+                float v[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) v[u] = xb[(size_t)(c0 + u) * 64];
+#pragma unroll
+                for (int u = 0; u < 16; u++)
+#pragma unroll
+                    for (int o = 0; o < 6; o++) a[o] = fmaf(wq[o * C + c0 + u], v[u], a[o]);
+            }
+#pragma unroll
+            for (int o = 0; o < 6; o++) part[wave][o][lane] = a[o];
+        }
+        __syncthreads();
+        for (int i = tid; i < 6 * 64; i += 256) {
+            const int o = i >> 6, p = i & 63;
+            const float s = ((part[0][o][p] + part[1][o][p]) + part[2][o][p]) + part[3][o][p];
+            feat[i] = fmaxf(s + b6[o], 0.f);
+        }
+        __syncthreads();
+        {
+            const f32x4* wr = reinterpret_cast<const f32x4*>(wfc + (size_t)lane * 256 + wave * 64);
+            const f32x4* fr = reinterpret_cast<const f32x4*>(feat + wave * 64);
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const f32x4 w4 = wr[k], f4 = fr[k];
+#pragma unroll
+                for (int e = 0; e < 4; e++) s = fmaf(w4[e], f4[e], s);
+            }
+            fcp[wave][lane] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const float lg = (((fcp[0][lane] + fcp[1][lane]) + fcp[2][lane]) + fcp[3][lane]) + bfc[lane];
+            const bool emp = occ[(size_t)b * occ_stride + lane] == 0;
+            const float mx = head8_wave_max(emp ? lg : -INFINITY);
+            const float ex = emp ? expf(lg - mx) : 0.f;
+            const float sm = head8_wave_sum(ex);
+            probs[(size_t)b * 64 + lane] = emp ? ex / sm : 0.f;
+            if (logits_out) logits_out[(size_t)b * 64 + lane] = lg;
+        } else if (wave == 1) {
+            float d = fmaf(feat[256 + lane], wv[lane], 0.f);
+            d = fmaf(feat[320 + lane], wv[64 + lane], d);
+            d = head8_wave_sum(d) + bv[0];
+            if (lane == 0) {
+                values[b] = tanhf(d);
+                if (vlogits_out) vlogits_out[b] = d;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace apz

@@ -314,6 +314,82 @@ __global__ __launch_bounds__(256) void head_softmax_value_kernel(const float* __
     }
 }
 
+// The legal-move form of head_softmax_value_kernel (apz_set_legal_policy): the softmax runs over the EMPTY cells of the
+// board only.  occ [n][occ_stride] u8: byte m != 0 where move m is occupied -- the forward's position codes themselves, or
+// what occupancy_planes_kernel made of its planes.  Same ownership of cells by lanes and the same reduction trees as the
+// kernel above, and an occupied cell is left out by SELECTION (its logit never enters an fmaxf, an expf or a sum): with no
+// stone on the board the two kernels execute the same operations on the same values, and a NaN, an inf or the row's largest
+// logit on an occupied cell changes no output bit.  Occupied cells get +0; a row without an empty cell is all +0.
+// logits_out still receives every raw logit; the value head is the kernel's above.
+__global__ __launch_bounds__(256) void head_softmax_value_legal_kernel(const float* __restrict__ logits_ws, const float* __restrict__ featv,
+                                                                       const float* __restrict__ wv, const float* __restrict__ bv,
+                                                                       const unsigned char* __restrict__ occ, int occ_stride,
+                                                                       float* __restrict__ probs, float* __restrict__ values,
+                                                                       float* __restrict__ logits_out, float* __restrict__ vlogits_out,
+                                                                       int n, int HW, int ldl) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const float* row = logits_ws + (size_t)r * ldl;
+    const float* fv = featv + (size_t)r * 2 * HW;
+    const unsigned char* oc = occ + (size_t)r * occ_stride;
+    float l[4], f[8], w[8];
+    bool emp[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int o = lane + 64 * i;
+        l[i] = o < HW ? row[o] : -INFINITY;
+        emp[i] = o < HW && oc[o] == 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int o = lane + 64 * i;
+        f[i] = o < 2 * HW ? fv[o] : 0.f;
+        w[i] = o < 2 * HW ? wv[o] : 0.f;
+    }
+    float le[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) le[i] = emp[i] ? l[i] : -INFINITY;
+    const float m = wave_max(fmaxf(fmaxf(le[0], le[1]), fmaxf(le[2], le[3])));
+    float ex[4], s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        ex[i] = emp[i] ? expf(l[i] - m) : 0.f;
+        s += ex[i];
+    }
+    s = wave_sum(s);
+    const float inv = 1.0f / s;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int o = lane + 64 * i;
+        if (o < HW) {
+            probs[(size_t)r * HW + o] = emp[i] ? ex[i] * inv : 0.f;
+            if (logits_out) logits_out[(size_t)r * HW + o] = l[i];
+        }
+    }
+    float d = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d = fmaf(f[i], w[i], d);
+    d = wave_sum(d) + bv[0];
+    if (lane == 0) {
+        values[r] = tanhf(d);
+        if (vlogits_out) vlogits_out[r] = d;
+    }
+}
+
+// planes [n][c_in][H][W] (top row first: encode_planes_kernel's flip) -> occ [n][H*W] u8 in move order (m = h*W + w, bottom
+// row first): 1 where the "all own stones" or the "all opponent stones" plane is non-zero at cell (H-1-h, w) -- planes 6 and
+// 7 of the 9-plane encoding, 0 and 1 of the 4-plane one
+__global__ void occupancy_planes_kernel(const float* __restrict__ planes, unsigned char* __restrict__ occ, long total, int H, int W,
+                                        int NP) {
+    const int HW = H * W, own = NP == 9 ? 6 : 0;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / HW;
+        const int m = (int)(i - b * HW), h = m / W, w = m - h * W;
+        const float* pb = planes + ((size_t)b * NP + own) * HW + (H - 1 - h) * W + w;
+        occ[i] = (pb[0] != 0.f || pb[HW] != 0.f) ? 1 : 0;
+    }
+}
+
 // ---- position codes -> input planes (Board.current_state, game.py:68-94 / :96-115) ---------
 // codes [n][stride] u8: byte m = h*W+w (un-flipped): 0 empty, 1+min(age,3) own, 5+min(age,3) opp;
 // byte HW = colour plane value.  planes [n][NP][H][W] with the vertical flip of game.py:94.

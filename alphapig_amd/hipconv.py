@@ -444,10 +444,13 @@ def dropout(x, keep, seed, step):
     return y
 
 
-def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=None):
+def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=None, occ=None):
     """The reference's loss head (policy_value_net_mxnet.py:180-193) on [n][H*W] logits and [n] value logits.
     -> dict with loss3 = (value loss, policy loss, entropy) [device, 3 floats], dlogits, dvlogit (grads),
-    probs, values (outputs).  loss3: a contiguous float32 device tensor of 3 to write the losses into."""
+    probs, values (outputs).  loss3: a contiguous float32 device tensor of 3 to write the losses into.
+    occ (default None: the reference's softmax over all cells): a contiguous uint8 device tensor [n][H*W] in move order,
+    non-zero where the move is occupied (occupancy_planes) -- softmax, cross-entropy and entropy then run over the empty
+    cells only and probs / dlogits are exactly +0 on the occupied ones (apz_pv_loss_legal)."""
     n, hw = int(logits.shape[0]), int(logits.shape[1])
     side = int(round(hw ** 0.5))
     L, hnd, stream = _ctx(logits, (side, side))
@@ -458,10 +461,29 @@ def pv_loss(logits, vlogit, pi=None, z=None, grads=True, outputs=False, loss3=No
             out["dlogits"], out["dvlogit"] = _empty((n, hw), logits), _empty((n,), logits)
     if outputs:
         out["probs"], out["values"] = _empty((n, hw), logits), _empty((n,), logits)
-    _ck(L, L.apz_pv_loss(hnd, logits.data_ptr(), vlogit.data_ptr(), _ptr(pi), _ptr(z), n, _ptr(out.get("loss3")),
-                         _ptr(out.get("dlogits")), _ptr(out.get("dvlogit")), _ptr(out.get("probs")), _ptr(out.get("values")),
-                         stream))
+    outs = [_ptr(out.get(k)) for k in ("loss3", "dlogits", "dvlogit", "probs", "values")]
+    if occ is None:
+        _ck(L, L.apz_pv_loss(hnd, logits.data_ptr(), vlogit.data_ptr(), _ptr(pi), _ptr(z), n, *outs, stream))
+    else:
+        if occ.device != logits.device:
+            raise ValueError("occ: a contiguous uint8 tensor [%d][%d] on the device of logits" % (n, hw))
+        _check(occ, "occ: a contiguous uint8 tensor [%d][%d] on the device of logits" % (n, hw), _torch().uint8, (n, hw))
+        _ck(L, L.apz_pv_loss_legal(hnd, logits.data_ptr(), vlogit.data_ptr(), _ptr(pi), _ptr(z), occ.data_ptr(), n, *outs, stream))
     return out
+
+
+def occupancy_planes(planes):
+    """planes [n][c_in][H][W] (c_in 9 or 4, top row first: Board.current_state) -> uint8 [n][H*W] in move order (m = h*W + w,
+    bottom row first, the order of pi): 1 where the "all own stones" or the "all opponent stones" plane is non-zero at the
+    move's cell (apz_occupancy_planes)."""
+    torch = _torch()
+    if planes.dim() != 4 or int(planes.shape[1]) not in (9, 4):
+        raise ValueError("occupancy_planes takes [n][9 or 4][H][W]")
+    L, hnd, stream = _ctx(planes)
+    n, c_in, h, w = (int(v) for v in planes.shape)
+    occ = torch.empty((n, h * w), dtype=torch.uint8, device=planes.device)
+    _ck(L, L.apz_occupancy_planes(hnd, planes.data_ptr(), n, c_in, h, w, occ.data_ptr(), stream))
+    return occ
 
 
 # ---- layout ---------------------------------------------------------------------------------------------------------

@@ -17,6 +17,9 @@ kl_targ, check_freq, pure_mcts_playout_num, game_batch_num, play_batch_size, sgf
     leaf_symmetry, arena_symmetry, symmetry_seed
                        the dihedral leaf symmetry ("none", "keyed", "mean8": PolicyValueNet) of the self-play evaluator and
                        of the evaluator the arena plays with, and the seed of "keyed" (default: the run's seed)
+    legal_policy       False (default): the reference's policy softmax over all H*W cells.  True: over the EMPTY cells of every
+                       position, in every evaluator of every rank (self-play, the trainer thread's KL monitor, the arena's
+                       player: PolicyValueNet's legal_policy) and in the trainer's loss (HipTrainer's legal_policy)
 
 One `game batch` of the reference = ONE self-play game followed by a policy update; here a batch
 collects `play_batch_size` games from the engine, which keeps `concurrent_games` running so that
@@ -158,7 +161,8 @@ class TrainPipeline(object):
         monitor, checkpoints and the arena; default: a second HIP PolicyValueNet, or `policy_value_net` itself when one
         was passed in.  distributed: None = on iff alphapig_amd.dist holds a process group.
         resume: the directory of a checkpoint (save_checkpoint; conf key checkpoint_every) written by a pipeline of the same
-        board, net, batch_size, buffer_size, replay, train_framed, step_guard, clip_norm, concurrent_games and world size:
+        board, net, batch_size, buffer_size, replay, train_framed, legal_policy, step_guard, clip_norm, concurrent_games and
+        world size:
         run() goes on where that one stood."""
         self.async_update = bool(conf.get("async_update", True))
         self.round_seconds = float(conf.get("round_seconds", 0.5))
@@ -202,6 +206,17 @@ class TrainPipeline(object):
             raise ValueError("arena_symmetry=%r differs from leaf_symmetry=%r, and the asynchronous schedule's arena would play "
                              "with the self-play evaluator while it is in use: pass eval_net" %
                              (self.arena_symmetry, self.leaf_symmetry))
+        # legal_policy (default False): the policy softmax over the empty cells of every position (PolicyValueNet's and
+        # HipTrainer's legal_policy), for every evaluator and the trainer alike: priors that sum to 1 over the legal moves,
+        # and a loss that spends no gradient on occupied cells.  An evaluator that was passed in is switched over
+        # (set_legal_policy: ValueError if it has none); with the key absent nothing is called and the run is what it was.
+        self.legal_policy = bool(conf.get("legal_policy", False))
+        if self.legal_policy:
+            for net, what in ((policy_value_net, "policy_value_net"), (eval_net, "eval_net")):
+                if net is not None and not hasattr(net, "set_legal_policy"):
+                    raise ValueError("legal_policy=True needs an evaluator with set_legal_policy; %s %r has none" % (what, net))
+            if trainer is not None and not getattr(trainer, "legal_policy", True):
+                raise ValueError("legal_policy=True, but the trainer %r was built with legal_policy=False" % (trainer,))
         # replay: what the replay buffer stores (module docstring)
         self.replay = conf.get("replay", "tuples")
         if self.replay not in ("tuples", "compact", "device"):
@@ -272,6 +287,7 @@ class TrainPipeline(object):
                                                      "batch_size", "buffer_size", "concurrent_games")}
         self._conf_match["replay"] = self.replay
         self._conf_match["train_framed"] = self.train_framed
+        self._conf_match["legal_policy"] = self.legal_policy
         self._conf_match["step_guard"] = self.step_guard
         self._conf_match["clip_norm"] = self.clip_norm
         self._conf_match["ema_decay"] = self.ema_decay
@@ -313,7 +329,11 @@ class TrainPipeline(object):
             self.board_width, self.board_height, max(self.batch_size, (concurrent + 1) // 2),
             n_blocks=conf.get("n_blocks", 10), n_filter=conf.get("n_filter", 128), model_params=init_model,
             device=device, seed=seed, uniform_trunk=self.uniform_trunk, leaf_symmetry=self.leaf_symmetry,
-            symmetry_seed=self.symmetry_seed)
+            symmetry_seed=self.symmetry_seed, legal_policy=self.legal_policy)
+        if self.legal_policy:
+            for net in (policy_value_net, eval_net):
+                if net is not None:
+                    net.set_legal_policy(True)
         if self._custom_net and self.leaf_symmetry != "none":
             self.policy_value_net.set_leaf_symmetry(self.leaf_symmetry, self.symmetry_seed)
         self.engine = SelfPlayEngine(self.policy_value_net, self.board_width, self.board_height, self.n_in_row,
@@ -424,7 +444,8 @@ class TrainPipeline(object):
             net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                       device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
                                       trunk_arith=self.train_arith, framed=self.train_framed, step_guard=self.step_guard,
-                                      clip_norm=self.clip_norm, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
+                                      clip_norm=self.clip_norm, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
+                                      legal_policy=self.legal_policy)
         return net._trainer
 
     # ---- the averaged weights (conf ema_decay): what plays is the average, what the KL monitor reads is the raw weights
@@ -710,7 +731,7 @@ class TrainPipeline(object):
     def _resume(self, path):
         state = checkpoint.read_state(path)
         for k, mine in self._conf_match.items():
-            theirs = state["conf"].get(k, False if k in ("train_framed", "step_guard") else None)   # (a checkpoint from before the key: off)
+            theirs = state["conf"].get(k, False if k in ("train_framed", "step_guard", "legal_policy") else None)   # (a checkpoint from before the key: off)
             if k == "ema_warmup" and k not in state["conf"]:
                 continue                        # (from before the averaged weights: ema_decay, compared above, was off)
             if theirs != mine:
@@ -851,7 +872,7 @@ class TrainPipeline(object):
                     kl_net = self._eval_net = PolicyValueNet(
                         self.board_width, self.board_height, self.batch_size, n_blocks=net._n_blocks,
                         n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, device=net._device,
-                        uniform_trunk=self.uniform_trunk)
+                        uniform_trunk=self.uniform_trunk, legal_policy=self.legal_policy)
                     self._own_eval_net = True
                     if self.act_scale == "auto":
                         kl_net.set_act_scale_auto(True)
@@ -862,7 +883,8 @@ class TrainPipeline(object):
                     trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
                                          device_index=net._device, seed=self._seed, trunk_arith=self.train_arith,
                                          framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm,
-                                         ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
+                                         ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
+                                         legal_policy=self.legal_policy)
                 self._async_trainer = trainer
                 tstate = getattr(self, "_async_trainer_state", None)
                 if tstate is not None:                  # resume=: the trainer this thread built continues the saved one

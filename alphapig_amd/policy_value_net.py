@@ -62,7 +62,7 @@ class PolicyValueNet(object):
     def __init__(self, board_width, board_height, batch_size=512, n_blocks=8, n_filter=128,
                  model_params=None, net_kind="resnet", c_in=9, device=0, seed=0, init_style="reference", trunk_arith="auto",
                  uniform_trunk=False, leaf_symmetry="none", symmetry_seed=0, train_framed=False,
-                 train_step_guard=False, train_clip_norm=None, ema_decay=None, ema_warmup=True):
+                 train_step_guard=False, train_clip_norm=None, ema_decay=None, ema_warmup=True, legal_policy=False):
         """trunk_arith: the arithmetic of the 128 -> 128 trunk convolutions of the 15x15 / 128-filter residual net on
         batches of more than 32 boards (smaller batches and every other net always compute exact fp32 products):
           "f32"    exact fp32 products on the fp32 matrix pipe (csrc/trunk15_wino3.h): the bits the parity tests rest on;
@@ -95,7 +95,12 @@ class PolicyValueNet(object):
         whose gradients or losses are not finite is skipped instead of reaching the weights; global-norm clipping.
         ema_decay / ema_warmup: HipTrainer's averaged weights for the trainer train_step builds (ema_params() hands them
         out); this net's own evaluator keeps the RAW weights after train_step, as the reference's predict-module re-sync
-        does."""
+        does.
+        legal_policy (default False: the reference's softmax over all H*W cells; set_legal_policy changes it later): every
+        entry point that returns probabilities takes the policy softmax over the EMPTY cells of each position, occupied
+        cells exactly 0 (apz_set_legal_policy) -- the priors policy_value_fn and the search see sum to 1 over the legal
+        moves.  The trainer train_step builds gets the same switch (HipTrainer(legal_policy=...): the loss over the empty
+        cells)."""
         check_leaf_symmetry(leaf_symmetry)
         from .train import check_ema_decay
         self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
@@ -137,6 +142,9 @@ class PolicyValueNet(object):
         self.leaf_symmetry, self.symmetry_seed = "none", int(symmetry_seed) & (2 ** 64 - 1)
         if leaf_symmetry != "none":
             self.set_leaf_symmetry(leaf_symmetry)
+        self.legal_policy = False
+        if legal_policy:
+            self.set_legal_policy(True)
         if model_params is None:
             model_params = weights.init_params(net_kind, self.board_height, self.board_width, self.channelnum,
                                                self._n_blocks, self._n_filter, seed=seed, style=init_style)
@@ -321,6 +329,13 @@ class PolicyValueNet(object):
         self._ck(self.L.apz_set_leaf_symmetry(self._h, LEAF_SYMMETRIES[mode], seed))
         self.leaf_symmetry, self.symmetry_seed = mode, seed
 
+    def set_legal_policy(self, on):
+        """on: the policy softmax over the empty cells of each position (see __init__); off: over all cells.  Not while a
+        slot is in flight (EvaluatorError).  The evaluator's switch only: a trainer that train_step has built already keeps
+        the loss it was built with."""
+        self._ck(self.L.apz_set_legal_policy(self._h, int(bool(on))))
+        self.legal_policy = bool(on)
+
     def _codes_chunk(self):
         """positions per forward of the code entry points: batchsize, or what 8 images each leave room for"""
         if self.leaf_symmetry != "mean8":
@@ -441,7 +456,7 @@ class PolicyValueNet(object):
             self._trainer = HipTrainer(self.params(), self.net_kind, self._n_blocks, batch_size=self.batchsize,
                                        device_index=self._device, framed=self.train_framed,
                                        step_guard=self.train_step_guard, clip_norm=self.train_clip_norm,
-                                       ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
+                                       ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, legal_policy=self.legal_policy)
         loss, entropy = self._trainer.train_step(state_batch, mcts_probs, winner_batch, learning_rate)
         self._trainer.sync_evaluator(self)
         return np.array([loss], dtype=np.float32), np.array([entropy], dtype=np.float32)
@@ -547,6 +562,7 @@ class LanedEvaluator(object):
         kw.setdefault("uniform_trunk", net.uniform_trunk)      # the lanes compute the bits of the net they stand beside
         kw.setdefault("leaf_symmetry", net.leaf_symmetry)
         kw.setdefault("symmetry_seed", net.symmetry_seed)
+        kw.setdefault("legal_policy", net.legal_policy)
         """`net` plus n_lanes - 1 more PolicyValueNet handles built from its parameters."""
         extra = [PolicyValueNet(net.board_width, net.board_height, net.batchsize, n_blocks=net._n_blocks,
                                 n_filter=net._n_filter, model_params=net.params(), net_kind=net.net_kind, c_in=net.channelnum, device=net._device,
@@ -618,6 +634,11 @@ class LanedEvaluator(object):
         check_leaf_symmetry(mode)
         for ln in self.lanes:
             ln.set_leaf_symmetry(mode, seed)
+
+    def set_legal_policy(self, on):
+        """Every lane: a position's answer does not depend on the lane that gives it."""
+        for ln in self.lanes:
+            ln.set_legal_policy(on)
 
     def params(self):
         return self.lanes[0].params()

@@ -17,6 +17,7 @@ the self-play path.  The module needs the HIP library and a GPU; without them co
   guard     opt-in (step_guard / clip_norm; csrc/grad_guard.h): the global gradient norm taken on the device in front of
             Adam, global-norm clipping inside Adam's rescale factor, and a step whose gradients or losses are not finite
             skipped on the device -- weights, moments, moving statistics and t as if it had not been asked for
+  legal     opt-in (legal_policy): softmax, cross-entropy and entropy over the empty cells of every position
   average   opt-in (ema_decay; csrc/ema.h): an exponential moving average of every parameter and statistic in a shadow copy
             on the device, moved by one launch behind every Adam launch under that launch's skip rule -- what self-play, the
             arena and the saved models of TrainPipeline read while the raw weights go on being trained
@@ -107,7 +108,7 @@ def check_trainable_board(params, framed=False, net_kind="resnet", trunk_arith="
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
                  seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False, step_guard=False,
-                 clip_norm=None, ema_decay=None, ema_warmup=True):
+                 clip_norm=None, ema_decay=None, ema_warmup=True, legal_policy=False):
         """params: name -> array, in any order.  height / width: the board (default: square, from the policy head's size).
         seed / dropout_step0: the dropout masks are a stateless hash of (seed, dropout_step0 + step, element) -- a trainer
         that is re-created (set_params, a resumed checkpoint) or one of several ranks passes its own seed / the steps
@@ -140,7 +141,11 @@ class HipTrainer(object):
         skipped (the guard's verdict) or repeated (an f16x2 overflow) moves the average exactly as often as it moved the
         weights.  ema_updates counts the steps applied, from the read-back the step makes anyway.  The raw weights, the
         moments and the losses are those of a trainer without it, bit for bit: the launch only reads them.
-        ema_params() / sync_evaluator(net, ema=True) hand the average out."""
+        ema_params() / sync_evaluator(net, ema=True) hand the average out.
+        legal_policy: opt in to the legal-move policy: the loss takes its log-softmax, cross-entropy and
+        entropy over the EMPTY cells of every position (hipconv.pv_loss(occ=...)), so no gradient is spent on pushing
+        occupied cells down; the occupancy is made on the device once per uploaded batch, from the planes.  The internal
+        evaluator of the KL monitor is created with the same switch.  Off: the reference's loss, today's launches."""
         if trunk_arith not in ("f32", "f16x2"):
             raise ValueError("trunk_arith must be 'f32' or 'f16x2', not %r" % (trunk_arith,))
         if clip_norm is not None:
@@ -245,9 +250,20 @@ class HipTrainer(object):
             self._ema_buf = self._flat(list(self.p), self.ema_p)
             # (the launch's table, once: from here on the tensors of p and ema_p are only ever written INTO)
             self._ema_tab = hipconv.ema_table([(self.ema_p[k], self.p[k]) for k in self.p])
+        self.legal_policy = bool(legal_policy)
+        self._occ = (None, None, None)  # legal_policy: the states tensor the occupancy was made of, its version, the occupancy
         self._eval = None
         self._eval_t = -1
         self.tape = None
+
+    def _occupancy(self, states):
+        """legal_policy: the occupancy [n][H*W] u8 of a batch's planes, made once per uploaded batch: policy_update hands the
+        same DeviceBatch to every epoch, and a tensor that was written to since (its version moved) is read again"""
+        held, version, occ = self._occ
+        if held is not states or version != states._version:
+            occ = self.ops.occupancy_planes(states)
+            self._occ = (states, states._version, occ)
+        return occ
 
     def _flat(self, names, into):
         """The tensors of p named `names`, copied back to back into ONE new contiguous buffer -> the buffer, flat;
@@ -450,7 +466,8 @@ class HipTrainer(object):
         try:
             logits, vlogit, tape = self._forward(batch.states, self.t)
             tape["step"] = self.t
-            out = self.ops.pv_loss(logits, vlogit, batch.pis, batch.zs, grads=True, loss3=loss3)
+            out = self.ops.pv_loss(logits, vlogit, batch.pis, batch.zs, grads=True, loss3=loss3,
+                                   occ=self._occupancy(batch.states) if self.legal_policy else None)
             self._backward(tape, out["dlogits"], out["dvlogit"])
         finally:
             self._fast = False
@@ -600,7 +617,7 @@ class HipTrainer(object):
             nf = int(next(iter(self.p.values())).shape[0]) if self.kind == "resnet" else 128
             self._eval = PolicyValueNet(self.side, self.side, batch_size=self.batch_size, n_blocks=self.n_blocks, n_filter=nf,
                                         model_params=self.get_params(), net_kind=self.kind, c_in=self.c_in,
-                                        device=self.device.index or 0)
+                                        device=self.device.index or 0, legal_policy=self.legal_policy)
             self._eval_t = self.t
         elif self._eval_t != self.t:
             self.sync_evaluator(self._eval)
@@ -625,6 +642,8 @@ class HipTrainer(object):
                         "trunk_arith": self.trunk_arith, "framed": self.framed, "step_guard": self.step_guard,
                         "clip_norm": self.clip_norm, "skipped_steps": int(self.skipped_steps),
                         "clipped_steps": int(self.clipped_steps)}}
+        if self.legal_policy:          # (a trainer without the switch writes what it always wrote)
+            out["meta"]["legal_policy"] = True
         if self.ema_p is not None:
             out["meta"].update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=int(self.ema_updates))
         for tag, group in self._groups(self.ema_p is not None):
@@ -645,6 +664,9 @@ class HipTrainer(object):
         if bool(meta.get("framed", False)) != self.framed:
             raise ValueError("this trainer state was written with framed=%s, the trainer was built with framed=%s" %
                              (bool(meta.get("framed", False)), self.framed))
+        if bool(meta.get("legal_policy", False)) != self.legal_policy:      # (a state from before the switch: off)
+            raise ValueError("this trainer state was written with legal_policy=%s, the trainer was built with legal_policy=%s" %
+                             (bool(meta.get("legal_policy", False)), self.legal_policy))
         todo = []
         with_ema = self.ema_p is not None and any(k.startswith("e/") for k in state)
         for tag, group in self._groups(with_ema):

@@ -16,6 +16,8 @@
  *   PolicyValueNet.policy_value_fn (H2D, forward, D2H) policy_value_net_mxnet.py:261-280
  *   Board.current_state (plane encoding, done on device from compact codes) game.py:68-94
  *   TrainPipeline.get_equi_data (8-fold dihedral augmentation) train_mxnet.py:115-135
+ *   SoftmaxActivation of the policy head (over all cells; opt-in over the empty cells only:
+ *   apz_set_legal_policy, apz_pv_loss_legal)          policy_value_net_mxnet.py:90
  */
 #ifndef ALPHAPIG_HIP_H
 #define ALPHAPIG_HIP_H
@@ -386,6 +388,22 @@ int apz_dropout(apz_engine *e, const void *x_dev, void *y_dev, int64_t count, fl
 int apz_pv_loss(apz_engine *e, const void *logits_dev, const void *vlogit_dev, const void *pi_dev, const void *z_dev,
                 int n, void *loss3_dev, void *dlogits_dev, void *dvlogit_dev, void *probs_dev, void *values_dev,
                 void *stream);
+/* apz_pv_loss over the EMPTY cells of every board (the training side of apz_set_legal_policy; csrc/heads_train.h).
+ * occ_dev [n][H*W] u8 in move order: byte m != 0 where move m is occupied (apz_occupancy_planes).  With E the empty cells
+ * of a row: p = softmax of the logits over E (the maximum over E only), policy loss -sum_E pi log p, entropy -sum_E p log p,
+ * dlogits = (p sum_E(pi) - pi) / n on E; probs and dlogits are exactly +0 on the occupied cells, and a row without an empty
+ * cell has policy loss 0, entropy 0 and all-zero probs / dlogits.  An occupied cell is left out by selection: whatever its
+ * logit holds (NaN, inf, the row's maximum) changes no output bit.  The kernel keeps the unmasked kernel's ownership of
+ * cells by lanes and its reduction trees: with occ_dev all zero every output has apz_pv_loss's bits.  Value terms unchanged. */
+int apz_pv_loss_legal(apz_engine *e, const void *logits_dev, const void *vlogit_dev, const void *pi_dev,
+                      const void *z_dev, const void *occ_dev, int n, void *loss3_dev, void *dlogits_dev,
+                      void *dvlogit_dev, void *probs_dev, void *values_dev, void *stream);
+/* planes_dev [n][c_in][H][W] f32 (the planes of apz_encode_planes: top row first) -> occ_dev [n][H*W] u8 in move order
+ * (m = h*W + w, bottom row first: the order of the position codes and of pi): 1 where cell (H-1-h, w) of the "all own
+ * stones" or of the "all opponent stones" plane is non-zero -- planes 6 and 7 for c_in = 9, planes 0 and 1 for c_in = 4 --
+ * else 0.  Any board size (the engine's own is not looked at); queued on `stream`. */
+int apz_occupancy_planes(apz_engine *e, const void *planes_dev, int n, int c_in, int H, int W, void *occ_dev,
+                         void *stream);
 int apz_layout_convert(apz_engine *e, const void *src_dev, void *dst_dev, int64_t planes, int to_rows16, void *stream);
 
 /* ---- the training step on framed boards (csrc/bn_frame.h, csrc/frame15.h): a board of side S in 6 .. 14 (not 8, not 10)
@@ -480,6 +498,23 @@ int apz_get_leaf_symmetry(apz_engine *e, int *mode, uint64_t *seed);
  *   k   = fmix64(seed ^ (sum_i t_i mod 2^64)) >> 61
  * -> k_out [n], each 0 .. 7.  Takes no engine and needs no GPU: the function the kernel runs, compiled for the host. */
 int apz_leaf_symmetry_keys(const uint8_t *codes_host, int n, int hw, int stride, uint64_t seed, uint8_t *k_out);
+/* Legal-move policy (default off: the reference's softmax over all H*W cells, policy_value_net_mxnet.py:90, and the engine
+ * launches exactly what it launched before this call existed).  on != 0: every entry point that returns probs -- planes and
+ * codes forms, host, device and async, apz_submit_codes / apz_wait with the exact repeat of an overflowed batch,
+ * apz_forward_dev_host, HIP-graph replay -- takes the policy softmax over the EMPTY cells E of each board:
+ *   probs[m] = exp(l_m - max_E l) / sum_E exp(l - max_E l) on E, exactly +0 on occupied cells,
+ * so the priors of a search node sum to 1 over its legal moves.  Move m = h*W + w is occupied where code byte m != 0 (codes
+ * entry points: the head reads the forward's own code rows in place) or where apz_occupancy_planes says so (planes entry
+ * points: staged by one short launch in front of the head).  Under a leaf symmetry the mask is that of the image the forward
+ * reads, so the folded answer is zero on the position's own occupied cells, under APZ_SYM_MEAN8 as well.  Occupied cells
+ * are left out by selection, never by arithmetic: a NaN, an inf or the row's largest logit there changes no output bit; a
+ * row without an empty cell is all zeros.  The masked heads (csrc/heads.h, csrc/conv8_small.h) keep the unmasked heads'
+ * ownership of cells by lanes and their reduction trees: a board with no stone gets the switch-off bits, and a row's bits
+ * depend on neither the batch nor the grid.  Values, logits_dev and vlogits_dev of apz_forward are untouched.
+ * Engine state: apz_load_weights and apz_load_weights_dev keep it; HIP graphs are dropped and captured again.
+ * APZ_E_STATE while a slot is in flight.  apz_get_legal_policy: 0 / 1. */
+int apz_set_legal_policy(apz_engine *e, int on);
+int apz_get_legal_policy(apz_engine *e);
 int apz_set_profiling(apz_engine *e, int on);
 /* TEST HOOK.  The 15x15 / 128-filter residual net has two trunk convolution kernels: the fused F(4x4,3x3) Winograd kernel
  * (default, csrc/trunk15_wino3.h) and the direct convolution (csrc/trunk15_ring.h) that the tests use as the in-tree

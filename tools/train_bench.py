@@ -7,7 +7,8 @@ product trainer per board side (framed sides: HipTrainer framed=True), alternati
 side's step time and its ratio to the first.  --step-guard: the product trainer without and with the guarded optimiser step
 (HipTrainer step_guard; --clip-norm adds clipping), alternating in the same way, per --arith arithmetic (default f32).
 --ema: the product trainer without and with the averaged weights (HipTrainer ema_decay; --ema-decay), alternating in the same
-way, and the averaging launch on its own between two events."""
+way, and the averaging launch on its own between two events.  --legal-policy: the product trainer without and with the
+legal-move policy (HipTrainer legal_policy: the occupancy launch per uploaded batch, the masked loss), alternating in the same way."""
 import argparse
 import json
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--clip-norm", type=float, default=None, help="--step-guard: the guarded trainer's clip_norm")
     ap.add_argument("--ema", action="store_true", help="HipTrainer ema_decay off / on: alternating runs")
     ap.add_argument("--ema-decay", type=float, default=0.999, help="--ema: the averaging trainer's ema_decay")
+    ap.add_argument("--legal-policy", action="store_true", help="HipTrainer legal_policy off / on: alternating runs")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     prm = weights.init_params("resnet", 15, 15, 9, 10, 128, seed=0, style="bench")
@@ -45,6 +47,8 @@ def main():
         return side_ab(args, rs)
     if args.ema:
         return ema_ab(args, prm, rs)
+    if args.legal_policy:
+        return legal_ab(args, prm, rs)
     if args.step_guard:
         return guard_ab(args, prm, rs)
     if args.arith:
@@ -157,6 +161,44 @@ def guard_ab(args, prm, rs):
                   "   ".join("%s %.3f ms/step (runs %s)" % (k, med[k], ", ".join("%.3f" % x for x in times[k])) for k in trs) +
                   "   ratio guarded/plain %.4f   grad_norm %.4g skipped %d clipped %d" %
                   (med["guarded"] / med["plain"], g.last_grad_norm, g.skipped_steps, g.clipped_steps), flush=True)
+            for tr in trs.values():
+                tr.close()
+    print(json.dumps(out))
+
+
+def legal_ab(args, prm, rs):
+    """The step without and with the legal-move policy per batch size (and --arith arithmetic), alternating like guard_ab: one
+    trainer each from the same weights, `--reps` rounds of (warm-up step, `--steps` timed steps on an uploaded mini-batch) in
+    turn; the median step time of each and all runs (their spread is the yardstick for the difference).  The planes are random
+    bits at density 0.3, so half the cells carry a stone; pi is zero there."""
+    import torch
+    out = {}
+    for B in [int(x) for x in args.batches.split(",")]:
+        states = (rs.rand(B, 9, 15, 15) > 0.7).astype(np.float32)
+        occ = ((states[:, 6] != 0) | (states[:, 7] != 0))[:, ::-1].reshape(B, 225)
+        pis = rs.dirichlet(np.ones(225), size=B) * ~occ
+        pis = (pis / pis.sum(axis=1, keepdims=True)).astype(np.float32)
+        zs = rs.choice([-1.0, 1.0], size=B).astype(np.float32)
+        for a in (args.arith or "f32").split(","):
+            trs = {"plain": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a),
+                   "legal": HipTrainer(prm, "resnet", n_blocks=10, batch_size=B, trunk_arith=a, legal_policy=True)}
+            batches = {k: tr.upload(states, pis, zs) for k, tr in trs.items()}
+            times = {k: [] for k in trs}
+            for _ in range(args.reps):
+                for k, tr in trs.items():
+                    tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    for _ in range(args.steps):
+                        tr.train_step(batches[k], None, None, 1e-3)
+                    torch.cuda.synchronize()
+                    times[k].append(1e3 * (time.perf_counter() - t) / args.steps)
+            med = {k: float(np.median(times[k])) for k in trs}
+            for k in trs:
+                out["B%d_%s_%s" % (B, a, k)] = {"ms_per_step": med[k], "runs_ms": [round(x, 3) for x in times[k]]}
+            print("batch %4d %-5s  " % (B, a) +
+                  "   ".join("%s %.3f ms/step (runs %s)" % (k, med[k], ", ".join("%.3f" % x for x in times[k])) for k in trs) +
+                  "   ratio legal/plain %.4f" % (med["legal"] / med["plain"]), flush=True)
             for tr in trs.values():
                 tr.close()
     print(json.dumps(out))

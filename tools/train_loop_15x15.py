@@ -70,6 +70,8 @@ def main():
     ap.add_argument("--step-guard", action="store_true",
                     help="skip optimiser steps whose gradients or losses are not finite (TrainPipeline step_guard)")
     ap.add_argument("--clip-norm", type=float, default=None, help="clip the global gradient norm (TrainPipeline clip_norm; implies --step-guard)")
+    ap.add_argument("--legal-policy", action="store_true",
+                    help="policy softmax and loss over the empty cells of every position (TrainPipeline legal_policy)")
     ap.add_argument("--resume", default=None, help="a checkpoint directory, or 'latest' for the newest complete one in --checkpoint-dir")
     args = ap.parse_args()
     conf = dict(board_width=args.side, board_height=args.side, train_framed=args.side != 15, n_in_row=5, learn_rate=4e-4, lr_multiplier=1.0, temp=1.0,
@@ -80,7 +82,7 @@ def main():
                 max_update_share=args.max_update_share, exclusive_updates=args.exclusive, train_arith=args.train_arith,
                 act_scale=args.act_scale, replay=args.replay, checkpoint_every=args.checkpoint_every,
                 checkpoint_dir=args.checkpoint_dir, checkpoint_selfplay=args.checkpoint_selfplay,
-                step_guard=args.step_guard, clip_norm=args.clip_norm)
+                step_guard=args.step_guard, clip_norm=args.clip_norm, legal_policy=args.legal_policy)
     resume = args.resume
     if resume == "latest":
         from alphapig_amd import checkpoint
