@@ -70,6 +70,10 @@ checkpoint_every * play_batch_size rank 0 sets the header's tenth field, every r
 boundary, and rank 0 queues a marker behind that round's games; its trainer thread, on reaching the marker, writes the
 trainer, the buffer and the schedule and completes the directory.  The buffer then holds exactly the games handed over
 before the cut; self-play does not wait.  Consistent, and as timing-dependent as the schedule itself.
+
+Every weight set that leaves a trainer for an evaluator goes through trainer_weights / load_weights / sync_weights
+(alphapig_amd/train.py): device to device where both sides can, else through the host.  The optional keys, their checks and
+what a resumed run must share with the checkpoint's are one table, _CONF_KEYS.
 """
 import logging
 import os
@@ -85,8 +89,8 @@ from .arena import Arena, win_ratio
 from .augment import get_equi_data
 from .game import Board, Game
 from .policy_value_net import EvaluatorError, PolicyValueNet, check_leaf_symmetry
-from .selfplay import SelfPlayEngine, episodes_to_tuples
-from .train import policy_update
+from .selfplay import SelfPlayEngine
+from .train import FRAMED_SIDES, check_ema_decay, load_weights, policy_update, sync_weights, trainer_weights
 
 _logger = logging.getLogger(__name__)
 
@@ -151,6 +155,82 @@ class ReplayBuffer(object):
         self._head = 0
 
 
+def _one_of(key, *allowed):
+    def check(value):
+        if value not in allowed:
+            raise ValueError("%s must be %s or %r, not %r" % (key, ", ".join(repr(a) for a in allowed[:-1]), allowed[-1], value))
+        return value
+    return check
+
+
+def _clip_norm(value):
+    if value is None:
+        return None
+    if not (np.isfinite(float(value)) and float(value) > 0):
+        raise ValueError("clip_norm must be None or a finite positive number, not %r" % (value,))
+    return float(value)
+
+
+_SKIP = object()        # last column: a checkpoint without the key is not compared on it
+# The optional configuration keys: (name = attribute, default, check or conversion, a resumed run must share it, what a
+# checkpoint from before the key counts as).  TrainPipeline.__init__ reads them in this order (the first bad value raises),
+# _conf_match holds the shared ones, _resume compares them.  Required keys a resumed run must share: _SHARED_KEYS.
+_CONF_KEYS = (
+    ("async_update", True, bool, False, None),
+    ("round_seconds", 0.5, float, False, None),
+    ("round_steps", None, None, False, None),
+    ("max_update_share", 1.0, float, False, None),
+    # exclusive_updates: rank 0's self-play loop starts no new round while its trainer thread is inside a policy_update
+    # (the in-flight forwards finish): 45 ms updates instead of 130, 277 k leaf evaluations/s against 305 k interleaved
+    # (profiles/r06_train_loop_exclusive.log / _interleaved.log) -- for jobs that want the shortest
+    # update latency.
+    ("exclusive_updates", False, bool, False, None),
+    # train_arith: the trainer's trunk arithmetic (HipTrainer's trunk_arith)
+    ("train_arith", "f32", _one_of("train_arith", "f32", "f16x2"), False, None),
+    # act_scale: the static activation exponents of the self-play evaluator's f16x2 trunk kernel (PolicyValueNet.
+    # calibrate_trunk).  "off": untouched, all 0.  "auto": the evaluators lower their exponents when a forward overflows,
+    # and the self-play evaluator is calibrated on its most recent code batch after every weight installation.
+    ("act_scale", "off", _one_of("act_scale", "off", "auto"), False, None),
+    # leaf_symmetry / arena_symmetry / symmetry_seed (module docstring).  An evaluator that is asked for a mode other than
+    # "none" needs set_leaf_symmetry (ValueError otherwise); with "none" it is never called.  Where the arena plays with the
+    # self-play evaluator itself (lock step), it holds arena_symmetry for the arena's duration only.  state.json holds the
+    # three beside "conf", and only when one is not "none" (_SYMMETRY_KEYS).
+    ("leaf_symmetry", "none", lambda v: check_leaf_symmetry(v, "leaf_symmetry"), True, "none"),
+    ("arena_symmetry", "none", lambda v: check_leaf_symmetry(v, "arena_symmetry"), True, "none"),
+    ("symmetry_seed", None, int, True, _SKIP),
+    # replay: what the replay buffer stores (module docstring)
+    ("replay", "tuples", _one_of("replay", "tuples", "compact", "device"), True, None),
+    # train_framed: HipTrainer's `framed` -- the training step on the framed boards (6x6, 7x7, 9x9, 11x11 .. 14x14: the 15x15
+    # trunk kernels, the board mask in the BatchNorm passes).  On such a board it goes with the tuple buffer and the f32
+    # trainer only; 15x15 and 8x8 train as they always did, whatever the key says.
+    ("train_framed", False, bool, True, False),
+    # legal_policy (module docstring): an evaluator that was passed in is switched over (set_legal_policy: ValueError if it
+    # has none); with the key absent nothing is called and the run is what it was.
+    ("legal_policy", False, bool, True, False),
+    # step_guard / clip_norm: HipTrainer's guarded optimiser step -- a step whose gradients or losses are not finite is
+    # skipped on the device instead of reaching the weights, the moments and, through them, every self-play evaluator and
+    # the next checkpoint; clip_norm (a finite positive number; implies the guard) clips the global gradient norm.  The
+    # history record counts skipped and clipped steps; a skipped one is logged.
+    ("step_guard", False, bool, True, False),
+    ("clip_norm", None, _clip_norm, True, None),
+    # ema_decay / ema_warmup: HipTrainer's averaged weights.  With ema_decay set, everything that leaves the trainer for
+    # play -- the weights the self-play evaluators receive, the arena's, the saved .model files -- is the exponential
+    # moving average of the weights; the raw weights go on being trained, and every forward of the KL monitor runs on them.
+    # With None, none of that code runs.
+    ("ema_decay", None, check_ema_decay, True, None),
+    ("ema_warmup", True, bool, True, _SKIP),      # (from before the averaged weights: ema_decay, compared first, was off)
+    # checkpoints (module docstring).  checkpoint_every: game batches between two of them, 0 = never; checkpoint_keep: how
+    # many complete ones stay on disk; checkpoint_selfplay: "games" saves the games in flight with their trees, "none"
+    # abandons them (the game sequence and the finished games nobody took are kept either way); checkpoint_buffer: whether
+    # the replay buffer travels (default: the code buffers do, the 9 000 B tuples do not)
+    ("checkpoint_every", 0, lambda v: int(v or 0), False, None),
+    ("checkpoint_keep", 2, int, False, None),
+    ("checkpoint_selfplay", "games", _one_of("checkpoint_selfplay", "games", "none"), False, None),
+)
+_SHARED_KEYS = ("board_width", "board_height", "n_in_row", "n_blocks", "n_filter", "batch_size", "buffer_size", "concurrent_games")
+_SYMMETRY_KEYS = ("leaf_symmetry", "arena_symmetry", "symmetry_seed")
+
+
 class TrainPipeline(object):
     def __init__(self, conf, init_model=None, policy_value_net=None, device=0, seed=0, distributed=None, trainer=None,
                  eval_net=None, resume=None):
@@ -164,39 +244,17 @@ class TrainPipeline(object):
         board, net, batch_size, buffer_size, replay, train_framed, legal_policy, step_guard, clip_norm, concurrent_games and
         world size:
         run() goes on where that one stood."""
-        self.async_update = bool(conf.get("async_update", True))
-        self.round_seconds = float(conf.get("round_seconds", 0.5))
-        self.round_steps = conf.get("round_steps")
-        self.max_update_share = float(conf.get("max_update_share", 1.0))
-        # exclusive_updates (default off): rank 0's self-play loop starts no new round while its trainer thread is inside a
-        # policy_update (the in-flight forwards finish).  Measured on one MI355X with the reference's configuration
-        # (profiles/r06_train_loop_exclusive.log / _interleaved.log): an update takes 45 ms instead of 130 (its ~200 small
-        # launches per epoch no longer queue behind the self-play forwards' 60-us full-chip kernels), but self-play is held
-        # 12 % of the wall clock and ends at 277 k leaf evaluations/s against 305 k interleaved: interleaving wins on
-        # throughput; the switch is for jobs that want the shortest update latency.
-        self.exclusive_updates = bool(conf.get("exclusive_updates", False))
-        # train_arith: the trainer's trunk arithmetic (HipTrainer's trunk_arith): "f32" (default) or "f16x2"
-        self.train_arith = conf.get("train_arith", "f32")
-        if self.train_arith not in ("f32", "f16x2"):
-            raise ValueError("train_arith must be 'f32' or 'f16x2', not %r" % (self.train_arith,))
-        # act_scale: the static activation exponents of the self-play evaluator's f16x2 trunk kernel (PolicyValueNet.
-        # calibrate_trunk).  "off" (default): untouched, all 0.  "auto": the evaluators lower their exponents when a forward
-        # overflows, and the self-play evaluator is calibrated on its most recent code batch after every weight installation.
-        self.act_scale = conf.get("act_scale", "off")
-        if self.act_scale not in ("off", "auto"):
-            raise ValueError("act_scale must be 'off' or 'auto', not %r" % (self.act_scale,))
-        # uniform_trunk (default False): the evaluators this pipeline builds itself run batches of <= 32 boards on the
-        # small-batch f16x2 kernel, so that a game's bits do not depend on how many games share a forward
-        # (PolicyValueNet's uniform_trunk).  The trainer's internal evaluator is not concerned.
+        conf = {"symmetry_seed": seed, **conf}          # (the seed of "keyed": by default the run's)
+        for name, default, check, _, _ in _CONF_KEYS:
+            value = conf.get(name, default)
+            setattr(self, name, value if check is None else check(value))
+        self.step_guard = self.step_guard or self.clip_norm is not None
+        # uniform_trunk: the evaluators this pipeline builds itself run batches of <= 32 boards on the small-batch f16x2
+        # kernel, so that a game's bits do not depend on how many games share a forward (PolicyValueNet's uniform_trunk).  The
+        # trainer's internal evaluator is not concerned.
         self.uniform_trunk = bool(conf.get("uniform_trunk", False))
-        # leaf_symmetry / arena_symmetry ("none" (default), "keyed", "mean8": PolicyValueNet's leaf_symmetry): how the
-        # self-play evaluator / the evaluator the arena plays with use the eight dihedral images of a position;
-        # symmetry_seed: the seed of "keyed", by default the run's.  An evaluator that is asked for a mode other than "none"
-        # needs set_leaf_symmetry (ValueError otherwise); with "none" it is never called.  Where the arena plays with the
-        # self-play evaluator itself (lock step), it holds arena_symmetry for the arena's duration only.
-        self.leaf_symmetry = check_leaf_symmetry(conf.get("leaf_symmetry", "none"), "leaf_symmetry")
-        self.arena_symmetry = check_leaf_symmetry(conf.get("arena_symmetry", "none"), "arena_symmetry")
-        self.symmetry_seed = int(conf.get("symmetry_seed", seed))
+        self.checkpoint_buffer =bool(conf.get("checkpoint_buffer", self.replay != "tuples"))
+        # what the keys ask of each other and of the objects passed in
         for net, mode, key in ((policy_value_net, self.leaf_symmetry, "leaf_symmetry"),
                                (eval_net if eval_net is not None else policy_value_net, self.arena_symmetry, "arena_symmetry")):
             if net is not None and mode != "none" and not hasattr(net, "set_leaf_symmetry"):
@@ -206,27 +264,13 @@ class TrainPipeline(object):
             raise ValueError("arena_symmetry=%r differs from leaf_symmetry=%r, and the asynchronous schedule's arena would play "
                              "with the self-play evaluator while it is in use: pass eval_net" %
                              (self.arena_symmetry, self.leaf_symmetry))
-        # legal_policy (default False): the policy softmax over the empty cells of every position (PolicyValueNet's and
-        # HipTrainer's legal_policy), for every evaluator and the trainer alike: priors that sum to 1 over the legal moves,
-        # and a loss that spends no gradient on occupied cells.  An evaluator that was passed in is switched over
-        # (set_legal_policy: ValueError if it has none); with the key absent nothing is called and the run is what it was.
-        self.legal_policy = bool(conf.get("legal_policy", False))
         if self.legal_policy:
             for net, what in ((policy_value_net, "policy_value_net"), (eval_net, "eval_net")):
                 if net is not None and not hasattr(net, "set_legal_policy"):
                     raise ValueError("legal_policy=True needs an evaluator with set_legal_policy; %s %r has none" % (what, net))
             if trainer is not None and not getattr(trainer, "legal_policy", True):
                 raise ValueError("legal_policy=True, but the trainer %r was built with legal_policy=False" % (trainer,))
-        # replay: what the replay buffer stores (module docstring)
-        self.replay = conf.get("replay", "tuples")
-        if self.replay not in ("tuples", "compact", "device"):
-            raise ValueError("replay must be 'tuples', 'compact' or 'device', not %r" % (self.replay,))
-        # train_framed (default False): HipTrainer's `framed` -- the training step on the framed boards (6x6, 7x7, 9x9,
-        # 11x11 .. 14x14: the 15x15 trunk kernels, the board mask in the BatchNorm passes).  On such a board it goes with the
-        # tuple buffer and the f32 trainer only; 15x15 and 8x8 train as they always did, whatever the key says.
-        self.train_framed = bool(conf.get("train_framed", False))
         if self.train_framed:
-            from .train import FRAMED_SIDES
             bw, bh = int(conf["board_width"]), int(conf["board_height"])
             if bw == bh and bw in FRAMED_SIDES:
                 if self.replay != "tuples":
@@ -235,23 +279,6 @@ class TrainPipeline(object):
                 if self.train_arith != "f32":
                     raise ValueError("train_framed on a %dx%d board takes train_arith='f32', not %r: the f16x2 trunk's "
                                      "statistics epilogue and scales see off-board cells" % (bw, bh, self.train_arith))
-        # step_guard / clip_norm (default off / None): HipTrainer's guarded optimiser step -- a step whose gradients or
-        # losses are not finite is skipped on the device instead of reaching the weights, the moments and, through them,
-        # every self-play evaluator and the next checkpoint; clip_norm (a finite positive number; implies the guard) clips
-        # the global gradient norm.  The history record counts skipped and clipped steps; a skipped one is logged.
-        self.clip_norm = conf.get("clip_norm")
-        if self.clip_norm is not None:
-            self.clip_norm = float(self.clip_norm)
-            if not (np.isfinite(self.clip_norm) and self.clip_norm > 0):
-                raise ValueError("clip_norm must be None or a finite positive number, not %r" % (conf.get("clip_norm"),))
-        self.step_guard = bool(conf.get("step_guard", False)) or self.clip_norm is not None
-        # ema_decay / ema_warmup (default None / True): HipTrainer's averaged weights.  With ema_decay set, everything that
-        # leaves the trainer for play -- the weights the self-play evaluators receive, the arena's, the saved .model files --
-        # is the exponential moving average of the weights; the raw weights go on being trained, and every forward of the KL
-        # monitor runs on them.  With None, today's code paths run untouched.
-        from .train import check_ema_decay
-        self.ema_decay = check_ema_decay(conf.get("ema_decay"))
-        self.ema_warmup = bool(conf.get("ema_warmup", True))
         if self.ema_decay is not None and trainer is not None:
             # (a HipTrainer built without ema_decay has both names: ema_p is None and ema_params() raises)
             keeps = (getattr(trainer, "ema_p", None) is not None or
@@ -273,25 +300,6 @@ class TrainPipeline(object):
             if trainer is not None and not hasattr(trainer, "upload"):
                 raise RuntimeError("replay='device' hands the trainer mini-batches in GPU memory; the trainer passed in has "
                                    "no upload(), so it does not take device batches (replay='compact' stays on the host)")
-        # checkpoints (module docstring).  checkpoint_every: game batches between two of them, 0 (default) = never;
-        # checkpoint_keep: how many complete ones stay on disk; checkpoint_selfplay: "games" saves the games in flight with
-        # their trees, "none" abandons them (the game sequence and the finished games nobody took are kept either way);
-        # checkpoint_buffer: whether the replay buffer travels (default: the code buffers do, the 9 000 B tuples do not)
-        self.checkpoint_every = int(conf.get("checkpoint_every", 0) or 0)
-        self.checkpoint_keep = int(conf.get("checkpoint_keep", 2))
-        self.checkpoint_selfplay = conf.get("checkpoint_selfplay", "games")
-        if self.checkpoint_selfplay not in ("games", "none"):
-            raise ValueError("checkpoint_selfplay must be 'games' or 'none', not %r" % (self.checkpoint_selfplay,))
-        self.checkpoint_buffer = bool(conf.get("checkpoint_buffer", self.replay != "tuples"))
-        self._conf_match = {k: conf.get(k) for k in ("board_width", "board_height", "n_in_row", "n_blocks", "n_filter",
-                                                     "batch_size", "buffer_size", "concurrent_games")}
-        self._conf_match["replay"] = self.replay
-        self._conf_match["train_framed"] = self.train_framed
-        self._conf_match["legal_policy"] = self.legal_policy
-        self._conf_match["step_guard"] = self.step_guard
-        self._conf_match["clip_norm"] = self.clip_norm
-        self._conf_match["ema_decay"] = self.ema_decay
-        self._conf_match["ema_warmup"] = self.ema_warmup
         self._gpu_gate = threading.Event()
         self._gpu_gate.set()
         self._custom_net = policy_value_net is not None
@@ -299,6 +307,9 @@ class TrainPipeline(object):
         self._device = device
         self.distributed = dist.is_active() if distributed is None else bool(distributed)
         self.rank, self.world = dist.rank_world() if self.distributed else (0, 1)
+        # what a resumed run must share with the run that wrote the checkpoint (_main_state, _resume)
+        self._conf_match = {k: conf.get(k) for k in _SHARED_KEYS}
+        self._conf_match.update({name: getattr(self, name) for name, _, _, shared, _ in _CONF_KEYS if shared}, world=self.world)
         self._trainer_override = trainer
         self._seed = seed
         self._train_steps = 0
@@ -370,8 +381,12 @@ class TrainPipeline(object):
         self._trainer_error = None
         self._sgf_done = threading.Event()     # asynchronous schedule: set by rank 0's trainer thread behind the SGF bootstrap
         self._last = (0.0, 0.0, 0.0)
-        self._conf_match["world"] = self.world
-        self._batches_done = 0                  # lock step: the loop index run() starts at
+        self._trainer_thread = self._async_trainer = self._async_trainer_state = None
+        self._own_eval_net = False              # the trainer thread built its evaluator itself: close() closes it
+        self._template = None                   # _param_template
+        self._held = None                       # device tensors the self-play evaluator may still be packing from
+        self.last_gathered = self.last_monitors = None
+        self._batches_done = 0                # lock step: the loop index run() starts at
         self._eval_overflows0 = 0               # the self-play evaluator's overflow count before a resume
         self.trainer_history = []
         self._games_collected = 0
@@ -391,25 +406,30 @@ class TrainPipeline(object):
         del self.engine.finished[:n_games]
         self._taken += n_games
         self.episode_len = int(np.mean([len(e.moves) for e in eps]))
-        if not self.distributed:
-            if self.replay != "tuples":         # the episodes' own codes, as they are
-                self.data_buffer.extend_codes(np.concatenate([e.codes for e in eps]), np.concatenate([e.pis for e in eps]),
-                                              np.concatenate([e.zs for e in eps]))
-                return
-            states, pis, zs = episodes_to_tuples(eps, self.engine.pool)
-        else:
-            codes = np.concatenate([e.codes for e in eps])
-            pis = np.concatenate([e.pis for e in eps]).astype(np.float32)
-            zs = np.concatenate([e.zs for e in eps]).astype(np.float32)
-            codes, pis, zs = dist.all_gather_tuples(codes, pis, zs, consumer=None if self.keep_replica_buffers else 0)   # THE exchange of the round (RCCL all-gather)
+        block = self._episodes_block(eps, exchange=self.distributed)
+        if self.distributed:
+            block = dist.all_gather_tuples(*block, consumer=None if self.keep_replica_buffers else 0)   # THE exchange of the round (RCCL all-gather)
             self.last_gathered = dist.last_gather_total
             if self.rank != 0 and not self.keep_replica_buffers:
                 return
-            if self.replay != "tuples":         # the gathered block, as it is
-                self.data_buffer.extend_codes(codes, pis, zs)
-                return
+        self._buffer_block(*block)
+
+    def _episodes_block(self, eps, exchange=True):
+        """Finished episodes as one block (codes, pis, zs), for none the empty block; exchange: pis and zs as float32, the
+        form that travels between ranks and to the trainer thread (a single rank's lock step buffers them as they are)."""
+        if not eps:
+            return (np.zeros((0, self.engine.pool.code_stride), np.uint8),
+                    np.zeros((0, self.board_width * self.board_height), np.float32), np.zeros(0, np.float32))
+        codes, pis, zs = (np.concatenate([getattr(e, k) for e in eps]) for k in ("codes", "pis", "zs"))
+        return (codes, pis.astype(np.float32), zs.astype(np.float32)) if exchange else (codes, pis, zs)
+
+    def _buffer_block(self, codes, pis, zs):
+        """A block into the replay buffer: the codes as they are, or their planes, 8x augmented (get_equi_data)"""
+        if self.replay != "tuples":
+            self.data_buffer.extend_codes(codes, pis, zs)
+        else:
             states = self.engine.pool.codes_to_planes(codes, 9)
-        self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
+            self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
 
     def collect_selfplay_data(self, training_index):
         """train_mxnet.py:137-154: SGF replay phase."""
@@ -432,7 +452,6 @@ class TrainPipeline(object):
         net = self.policy_value_net
         if self._trainer_override is not None:
             return self._trainer_override
-        from .train import HipTrainer
         if getattr(net, "_trainer", None) is None:
             if self.ema_decay is not None and self._train_steps > 0:
                 # none of this pipeline's own paths drops the trainer; an outside set_params on the evaluator does.  With
@@ -441,34 +460,25 @@ class TrainPipeline(object):
                                 "trainer starts its raw weights, its moments and its average from the averaged weights "
                                 "the evaluator holds", self.ema_decay)
             # a re-created trainer (set_params dropped the old one) continues the dropout mask sequence instead of replaying it
-            net._trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
-                                      device_index=net._device, seed=self._seed, dropout_step0=self._train_steps,
-                                      trunk_arith=self.train_arith, framed=self.train_framed, step_guard=self.step_guard,
-                                      clip_norm=self.clip_norm, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
-                                      legal_policy=self.legal_policy)
+            net._trainer = self._new_trainer(net, dropout_step0=self._train_steps)
         return net._trainer
 
+    def _new_trainer(self, net, dropout_step0=0):
+        """A HipTrainer on evaluator `net`'s weights with this pipeline's training keys"""
+        from .train import HipTrainer           # (looked up now: the tests put stand-ins there)
+        return HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size, device_index=net._device,
+                          seed=self._seed, dropout_step0=dropout_step0, trunk_arith=self.train_arith,
+                          framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm,
+                          ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, legal_policy=self.legal_policy)
+
     # ---- the averaged weights (conf ema_decay): what plays is the average, what the KL monitor reads is the raw weights
-    def _ema_host(self, trainer):
-        """The trainer's averaged weights as host arrays"""
-        if hasattr(trainer, "ema_params"):
-            return trainer.ema_params()
-        return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in trainer.ema_p.items()}
-
-    def _install_average(self, trainer, net):
-        """The averaged weights into evaluator `net`: device to device where both sides can, else through the host"""
-        if hasattr(trainer, "sync_evaluator") and hasattr(trainer, "ema_p") and hasattr(net, "load_device_params"):
-            trainer.sync_evaluator(net, ema=True)
-        else:
-            net.set_params(self._ema_host(trainer), _keep_trainer=True)
-
     def _average_for_play(self, trainer, net):
         """Before an arena or a save on the trainer thread's evaluator: it gets the averaged weights, and the next update
         puts the raw ones back before its first forward (policy_update).  The self-play evaluator already holds the average
         (every installation carries it)."""
         if self.ema_decay is None or net is self.policy_value_net:
             return
-        self._install_average(trainer, net)
+        sync_weights(trainer, net, averaged=True, keep_trainer=True)
         self._kl_net_averaged = True
 
     def _note_overflows(self, rec, trainer):
@@ -519,18 +529,10 @@ class TrainPipeline(object):
         trainer = self._trainer() if trainer is None else trainer
         t_before = getattr(trainer, "t", 0)
         mon = {}
-        if self.ema_decay is None:
-            evaluator = _KeepTrainer(net)
-        elif net is self.policy_value_net:
-            evaluator = None
-        else:
-            evaluator = _KeepTrainer(net)
-            if self._kl_net_averaged:
-                if hasattr(trainer, "sync_evaluator") and hasattr(net, "load_device_params"):
-                    trainer.sync_evaluator(net)
-                else:
-                    evaluator.set_params(trainer.get_params())
-                self._kl_net_averaged = False
+        evaluator = None if self.ema_decay is not None and net is self.policy_value_net else _KeepTrainer(net)
+        if evaluator is not None and self._kl_net_averaged:     # (only ema_decay sets it)
+            sync_weights(trainer, net, keep_trainer=True)
+            self._kl_net_averaged = False
         loss, entropy, kl, self.lr_multiplier = policy_update(trainer, mini, self.learn_rate, self.lr_multiplier,
                                                               self.epochs, self.kl_targ, evaluator=evaluator, monitors=mon)
         self._train_steps += max(0, getattr(trainer, "t", 0) - t_before)
@@ -552,7 +554,7 @@ class TrainPipeline(object):
                 rec["loss"], rec["entropy"], rec["kl"] = self.policy_update()
                 self._note_overflows(rec, self._trainer())
                 if self.ema_decay is not None:      # the games that follow are played by the average
-                    self._install_average(self._trainer(), self.policy_value_net)
+                    sync_weights(self._trainer(), self.policy_value_net, averaged=True, keep_trainer=True)
             return
         head = [0.0, 0.0, 0.0, 0.0, self.lr_multiplier]
         if do:
@@ -566,28 +568,20 @@ class TrainPipeline(object):
         rec["lr_multiplier"] = head[4]          # informational on ranks > 0: the adaptive state lives on rank 0
         net = self.policy_value_net
         if self.rank == 0:
-            tr = self._trainer()
+            src = trainer_weights(self._trainer(), self.ema_decay is not None)
             if self.ema_decay is not None:
                 # the broadcast carries the average, and rank 0's own evaluator, which the KL monitor no longer touches, gets it too
-                src = tr.ema_p if (hasattr(tr, "ema_p") and hasattr(tr, "torch")) else self._ema_host(tr)
-                self._install_average(tr, net)
-            else:
-                src = tr.p if hasattr(tr, "p") else tr.get_params()
+                sync_weights(self._trainer(), net, averaged=True, keep_trainer=True)
         else:
             src = self._param_template()
         got = dist.broadcast_params({k: src[k] for k in sorted(src)}, src=0)
-        if self.rank != 0:
-            first = next(iter(got.values()))
-            if getattr(first, "is_cuda", False) and hasattr(net, "load_device_params"):
-                self._held = got                 # the evaluator packs from these tensors asynchronously: keep them alive
-                net.load_device_params(got)
-            else:
-                net.set_params({k: v.cpu().numpy() for k, v in got.items()})
-        self.weight_broadcasts = getattr(self, "weight_broadcasts", 0) + 1
+        if self.rank != 0:      # (the evaluator packs from device tensors asynchronously: _held keeps them alive)
+            self._held = load_weights(net, got, keep_trainer=False) or self._held
+        self.weight_broadcasts += 1
 
     def _param_template(self):
         """Names and shapes of the parameter set (ranks > 0 never build a trainer; values are overwritten by the broadcast)."""
-        if getattr(self, "_template", None) is None:
+        if self._template is None:
             self._template = {k: np.zeros(v.shape, np.float32) for k, v in self.policy_value_net.params().items()}
         return self._template
 
@@ -627,18 +621,8 @@ class TrainPipeline(object):
             if "loss" in rec:                          # the evaluator holds new weights
                 self._calibrate_after_install()
             self._note_act_scale(rec)
-            if lead and (i + 1) % 50 == 0:
-                os.makedirs(self.model_dir, exist_ok=True)
-                self.policy_value_net.save_model(os.path.join(self.model_dir, "current_policy.model"))
-            if lead and (i + 1) % self.check_freq == 0:
-                rec["win_ratio"] = wr = self.policy_evaluate()
-                if wr > self.best_win_ratio:
-                    self.best_win_ratio = wr
-                    os.makedirs(self.model_dir, exist_ok=True)
-                    self.policy_value_net.save_model(os.path.join(self.model_dir, "best_policy_%s.model" % i))
-                    if self.best_win_ratio >= 0.98 and self.pure_mcts_playout_num < 8000:
-                        self.pure_mcts_playout_num += 1000
-                        self.best_win_ratio = 0.0
+            if lead:            # (the self-play evaluator holds what plays, the average included: no trainer is passed)
+                self._schedule_after_batch(i, rec, self.policy_value_net)
             self.history.append(rec)
             _logger.info("batch %s", rec)
             self._batches_done = i + 1
@@ -650,16 +634,15 @@ class TrainPipeline(object):
 
     # ---- checkpoints (alphapig_amd/checkpoint.py holds the file layout) ------------------------------------------------
     def _timed_part(self, directory, part, state):
+        """Write one part; state: the part's state, or a function that returns it (its time counts)"""
         t0 = time.perf_counter()
-        nbytes = checkpoint.write_part(directory, part, state)
+        nbytes = checkpoint.write_part(directory, part, state() if callable(state) else state)
         self.checkpoint_log.append((part, time.perf_counter() - t0, nbytes))
 
     def _write_selfplay_part(self, directory):
         """This rank's engine, between two run_steps calls (the caller's thread is the one that drives the engine)"""
-        t0 = time.perf_counter()
-        state = self.engine.state(games=self.checkpoint_selfplay == "games")
-        nbytes = checkpoint.write_part(directory, "selfplay_rank%d" % self.rank, state)
-        self.checkpoint_log.append(("selfplay_rank%d" % self.rank, time.perf_counter() - t0, nbytes))
+        self._timed_part(directory, "selfplay_rank%d" % self.rank,
+                         lambda: self.engine.state(games=self.checkpoint_selfplay == "games"))
 
     def _write_trainer_parts(self, directory, trainer):
         """Rank 0: the trainer (or, before the first update, the evaluator's weights) and the replay buffer"""
@@ -683,14 +666,15 @@ class TrainPipeline(object):
     def _main_state(self):
         """The values the self-play side owns, and the configuration a resumed run must share"""
         net = self.policy_value_net
-        out = {"format": checkpoint.FORMAT, "conf": dict(self._conf_match), "async_update": self.async_update,
+        conf = {k: v for k, v in self._conf_match.items() if k not in _SYMMETRY_KEYS}
+        out = {"format": checkpoint.FORMAT, "conf": conf, "async_update": self.async_update,
                "next_batch": self._batches_done, "taken": self._taken, "episode_len": self.episode_len,
                "weights_version": self.weights_version, "games_collected": self._games_collected, "round": self._round,
                "training_data": list(self._training_data), "history": list(self.history),
                "checkpoint_selfplay": self.checkpoint_selfplay,
                "eval_trunk_overflows": self._eval_overflows0 + (int(net.trunk_overflows()) if hasattr(net, "trunk_overflows") else 0)}
         if self.leaf_symmetry != "none" or self.arena_symmetry != "none":     # (a run without them writes what it always wrote)
-            out.update(leaf_symmetry=self.leaf_symmetry, arena_symmetry=self.arena_symmetry, symmetry_seed=self.symmetry_seed)
+            out.update({k: self._conf_match[k] for k in _SYMMETRY_KEYS})
         if hasattr(net, "trunk_act_exponents"):
             try:
                 out["act_exponents"] = [int(a) for a in net.trunk_act_exponents()]
@@ -730,24 +714,15 @@ class TrainPipeline(object):
 
     def _resume(self, path):
         state = checkpoint.read_state(path)
+        absent = {name: value for name, _, _, _, value in _CONF_KEYS}     # what a checkpoint from before a key counts as
         for k, mine in self._conf_match.items():
-            theirs = state["conf"].get(k, False if k in ("train_framed", "step_guard", "legal_policy") else None)   # (a checkpoint from before the key: off)
-            if k == "ema_warmup" and k not in state["conf"]:
-                continue                        # (from before the averaged weights: ema_decay, compared above, was off)
-            if theirs != mine:
+            theirs = (state if k in _SYMMETRY_KEYS else state["conf"]).get(k, absent.get(k))
+            if theirs is not _SKIP and theirs != mine:
                 raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
                                  (path, k, theirs, k, mine))
         if bool(state["async_update"]) != self.async_update:
             raise ValueError("the checkpoint %s was written with async_update=%r" % (path, state["async_update"]))
-        # (a checkpoint from before the leaf symmetries, or of a run without them, has no such keys: "none")
-        for k in ("leaf_symmetry", "arena_symmetry"):
-            if state.get(k, "none") != getattr(self, k):
-                raise ValueError("the checkpoint %s was written with %s=%r, this pipeline has %s=%r" %
-                                 (path, k, state.get(k, "none"), k, getattr(self, k)))
-        if "symmetry_seed" in state and int(state["symmetry_seed"]) != self.symmetry_seed:
-            raise ValueError("the checkpoint %s was written with symmetry_seed=%r, this pipeline has symmetry_seed=%r" %
-                             (path, state["symmetry_seed"], self.symmetry_seed))
-        part ="selfplay_rank%d" % self.rank
+        part = "selfplay_rank%d" % self.rank
         if not checkpoint.has_part(path, part):
             raise ValueError("the checkpoint %s has no part %s" % (path, part))
         self.engine.load_state(checkpoint.read_part(path, part))
@@ -776,7 +751,7 @@ class TrainPipeline(object):
         tstate = checkpoint.read_part(path, "trainer") if checkpoint.has_part(path, "trainer") else None
         if tstate is None:
             w = checkpoint.read_part(path, "weights")
-            net.set_params({k: v for k, v in w.items() if k != "meta"}, _keep_trainer=True)
+            load_weights(net, {k: v for k, v in w.items() if k != "meta"}, keep_trainer=True)
         else:
             weights = {k[2:]: v for k, v in tstate.items() if k.startswith("p/")}
             if self.ema_decay is not None and any(k.startswith("e/") for k in tstate):
@@ -786,16 +761,17 @@ class TrainPipeline(object):
                 if not hasattr(tr, "load_state"):
                     raise RuntimeError("resume needs a trainer with state() / load_state(); %r has none" % (tr,))
                 tr.load_state(tstate)
-                if self.ema_decay is not None:
-                    self._install_average(tr, net)
-                elif hasattr(tr, "sync_evaluator") and hasattr(net, "load_device_params"):
-                    tr.sync_evaluator(net)
-                else:
-                    net.set_params(tr.get_params(), _keep_trainer=True)
+                sync_weights(tr, net, averaged=self.ema_decay is not None, keep_trainer=True)
             else:
                 if self.rank == 0:
                     self._async_trainer_state = tstate          # the trainer thread builds its trainer, then loads this
-                self._install_host_weights(weights)
+                if hasattr(net, "load_device_params") and hasattr(net, "_device"):
+                    # through device tensors where the evaluator folds and packs on the device: what a broadcast update does
+                    import torch
+                    dev = torch.device("cuda", int(net._device))
+                    weights = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in weights.items()}
+                    torch.cuda.synchronize(dev)
+                self._held = load_weights(net, weights, keep_trainer=True) or self._held
         if "act_exponents" in state and hasattr(net, "set_trunk_act_exponents") and any(state["act_exponents"]):
             net.set_trunk_act_exponents(state["act_exponents"])
         self._async_resume = {"games_recv": state.get("games_recv", 0), "batches_done": state.get("trainer_batches_done", 0)}
@@ -807,19 +783,6 @@ class TrainPipeline(object):
         if self.async_update:
             self.weights_version = max(self.weights_version, int(self.updates_done))   # (versions count updates; the evaluator holds the trainer's)
         _logger.info("resumed from %s: next batch %d, %d games taken so far", path, self._batches_done, self._taken)
-
-    def _install_host_weights(self, weights):
-        """Weights read from a checkpoint into the self-play evaluator: through device tensors where the evaluator folds
-        and packs on the device (what a broadcast update does on a GPU rank), else through set_params"""
-        net = self.policy_value_net
-        if hasattr(net, "load_device_params") and hasattr(net, "_device"):
-            import torch
-            dev = torch.device("cuda", int(net._device))
-            self._held = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in weights.items()}
-            torch.cuda.synchronize(dev)
-            net.load_device_params(self._held)
-        else:
-            net.set_params(weights, _keep_trainer=True)
 
     # ---- the asynchronous schedule (module docstring) ---------------------------------------------
     def _play_round(self):
@@ -865,7 +828,6 @@ class TrainPipeline(object):
             trainer = self._trainer_override
             if trainer is None:
                 import torch
-                from .train import HipTrainer
                 stream = torch.cuda.Stream(device=net._device)
                 ctx = torch.cuda.stream(stream)      # this thread's kernels: a stream of their own, beside the self-play stream
                 if kl_net is None:
@@ -880,15 +842,10 @@ class TrainPipeline(object):
                 kl_net = self._eval_net = net
             with ctx:
                 if trainer is None:
-                    trainer = HipTrainer(net.params(), net.net_kind, net._n_blocks, batch_size=self.batch_size,
-                                         device_index=net._device, seed=self._seed, trunk_arith=self.train_arith,
-                                         framed=self.train_framed, step_guard=self.step_guard, clip_norm=self.clip_norm,
-                                         ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
-                                         legal_policy=self.legal_policy)
+                    trainer = self._new_trainer(net)
                 self._async_trainer = trainer
-                tstate = getattr(self, "_async_trainer_state", None)
-                if tstate is not None:                  # resume=: the trainer this thread built continues the saved one
-                    trainer.load_state(tstate)
+                if self._async_trainer_state is not None:       # resume=: the trainer this thread built continues the saved one
+                    trainer.load_state(self._async_trainer_state)
                     self._async_trainer_state = None
                 resumed = self._async_resume or {}
                 games_recv = int(resumed.get("games_recv", 0))
@@ -908,16 +865,7 @@ class TrainPipeline(object):
                     if len(self.data_buffer) == before:
                         rec["skipped"] = True                            # an unreadable record: nothing joined the buffer
                     if len(self.data_buffer) > self.batch_size:
-                        t0 = time.time()
-                        loss, entropy, kl = self.policy_update(trainer, kl_net)
-                        snap = self._snapshot(trainer)
-                        self.update_intervals.append((t0, time.time()))
-                        with self._lock:
-                            self.updates_done += 1
-                            self._last = (loss, entropy, kl)
-                            self._fresh = (self.updates_done, snap)
-                        rec.update(loss=loss, entropy=entropy, kl=kl)
-                        self._note_overflows(rec, trainer)
+                        self._async_update(trainer, kl_net, rec)
                     self._schedule_after_batch(i, rec, kl_net, trainer=trainer)
                     with self._lock:
                         self.trainer_history.append(rec)
@@ -937,13 +885,8 @@ class TrainPipeline(object):
                         if isinstance(it[0], str):      # the checkpoint marker: the buffer holds exactly the games before the cut
                             self._write_async_checkpoint(it[1], it[2], trainer, games_recv, batches_done)
                             continue
-                        codes, pis, zs, n_games = it
-                        if self.replay != "tuples":
-                            self.data_buffer.extend_codes(codes, pis, zs)
-                        else:
-                            states = self.engine.pool.codes_to_planes(codes, 9)
-                            self.data_buffer.extend(get_equi_data(list(zip(states, pis, zs)), self.board_height, self.board_width))
-                        games_recv += n_games
+                        self._buffer_block(*it[:3])
+                        games_recv += it[3]
                     due = n_sgf + games_recv // self.play_batch_size - batches_done
                     if due <= 0:
                         continue
@@ -954,25 +897,14 @@ class TrainPipeline(object):
                         now = time.time()
                         if now < busy_until and not stop:
                             time.sleep(busy_until - now)            # max_update_share: leave the device to self-play
-                        t0 = time.time()
                         if self.exclusive_updates:
                             self._gpu_gate.clear()                  # the self-play loop of this rank waits at its next round
                         try:
-                            loss, entropy, kl = self.policy_update(trainer, kl_net)
-                            snap = self._snapshot(trainer)
+                            t0, t1 = self._async_update(trainer, kl_net, rec, skipped=due - 1)
                         finally:
                             self._gpu_gate.set()
-                        t1 = time.time()
-                        self.update_intervals.append((t0, t1))
                         if self.max_update_share < 1.0:
                             busy_until = t1 + (t1 - t0) * (1.0 / max(self.max_update_share, 1e-3) - 1.0)
-                        with self._lock:
-                            self.updates_done += 1
-                            self.updates_skipped += due - 1
-                            self._last = (loss, entropy, kl)
-                            self._fresh = (self.updates_done, snap)
-                        rec.update(loss=loss, entropy=entropy, kl=kl)
-                        self._note_overflows(rec, trainer)
                     self._schedule_after_batch(batches_done - 1, rec, kl_net, first=first, trainer=trainer)
                     with self._lock:
                         self.trainer_history.append(rec)
@@ -984,16 +916,32 @@ class TrainPipeline(object):
         """How many leading game batches replay SGF records (0 without records), never more than game_batch_num."""
         return min(int(self.sgf_batches), int(self.game_batch_num)) if self._training_data else 0
 
+    def _async_update(self, trainer, kl_net, rec, skipped=0):
+        """One update on the trainer thread: policy_update, the snapshot the next round installs, the counters the round
+        header carries (skipped: game batches this update covers beyond its own) and the record -> its (start, end) wall
+        clock"""
+        t0 = time.time()
+        loss, entropy, kl = self.policy_update(trainer, kl_net)
+        snap = self._snapshot(trainer)
+        t1 = time.time()
+        self.update_intervals.append((t0, t1))
+        with self._lock:
+            self.updates_done += 1
+            self.updates_skipped += skipped
+            self._last = (loss, entropy, kl)
+            self._fresh = (self.updates_done, snap)
+        rec.update(loss=loss, entropy=entropy, kl=kl)
+        self._note_overflows(rec, trainer)
+        return t0, t1
+
     def _snapshot(self, trainer):
         """A private copy of the trainer's weights for the main thread to broadcast / load while the trainer goes on
         (ema_decay: of its averaged weights)."""
-        if self.ema_decay is not None and not (hasattr(trainer, "ema_p") and hasattr(trainer, "torch")):
-            return dict(self._ema_host(trainer))
-        if hasattr(trainer, "p") and hasattr(trainer, "torch"):
-            snap = {k: v.clone() for k, v in (trainer.p if self.ema_decay is None else trainer.ema_p).items()}
+        snap = trainer_weights(trainer, self.ema_decay is not None)
+        if hasattr(next(iter(snap.values())), "clone"):         # the trainer's own device tensors
+            snap = {k: v.clone() for k, v in snap.items()}
             trainer.torch.cuda.current_stream(trainer.device).synchronize()
-            return snap
-        return trainer.get_params()
+        return snap
 
     def _install_weights(self, version, snap):
         """One round's weight exchange: rank 0 sends snapshot `snap`, everybody (rank 0 included) loads it into the
@@ -1001,13 +949,7 @@ class TrainPipeline(object):
         net = self.policy_value_net
         src = snap if self.rank == 0 else self._param_template()
         got = dist.broadcast_params({k: src[k] for k in sorted(src)}, src=0) if self.distributed else dict(src)
-        first = next(iter(got.values()))
-        if getattr(first, "is_cuda", False) and hasattr(net, "load_device_params"):
-            self._held = got                 # the evaluator packs from these tensors asynchronously: keep them alive
-            net.load_device_params(got)
-        else:
-            net.set_params({k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in got.items()},
-                           **({"_keep_trainer": True} if self._custom_net else {}))
+        self._held = load_weights(net, got, keep_trainer=self._custom_net) or self._held
         self._calibrate_after_install()
         self.weights_version = version
         self.weight_broadcasts += 1
@@ -1054,13 +996,7 @@ class TrainPipeline(object):
             self._taken += len(eps)
             if eps:
                 self.episode_len = int(np.mean([len(e.moves) for e in eps]))
-                codes = np.concatenate([e.codes for e in eps])
-                pis = np.concatenate([e.pis for e in eps]).astype(np.float32)
-                zs = np.concatenate([e.zs for e in eps]).astype(np.float32)
-            else:
-                codes = np.zeros((0, self.engine.pool.code_stride), np.uint8)
-                pis = np.zeros((0, self.board_width * self.board_height), np.float32)
-                zs = np.zeros(0, np.float32)
+            codes, pis, zs = self._episodes_block(eps)
             n_games = len(eps)
             if self.distributed and not draining:
                 n_games = int(round(dist.all_reduce_sum(len(eps))))
@@ -1147,9 +1083,9 @@ class TrainPipeline(object):
     def close(self):
         self.engine.close()
         self.policy_value_net.close()
-        if getattr(self, "_own_eval_net", False):
+        if self._own_eval_net:
             self._eval_net.close()
-        tr = getattr(self, "_async_trainer", None)
+        tr = self._async_trainer
         if tr is not None and tr is not self._trainer_override and hasattr(tr, "close"):
             tr.close()
 

@@ -711,6 +711,45 @@ def explained_variance(winner_z, value):
         return float(1.0 - np.var(z - v) / np.var(z))
 
 
+# ---- the weight hand-off: a trainer's weights into an evaluator, device to device where both sides can, else through the host.
+# Trainers and evaluators are duck-typed (HipTrainer / PolicyValueNet / LanedEvaluator, the tests' stand-ins): what an object
+# can do is asked here and nowhere else.
+def _host_array(v):
+    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+
+
+def trainer_weights(trainer, averaged=False, host=False):
+    """{name: weight} of `trainer` (averaged: of its averaged weights): the device tensors themselves where the trainer keeps
+    them (`p` / `ema_p` beside `torch`) and host=False, else host arrays (get_params() / ema_params() / ema_p)."""
+    if not host and hasattr(trainer, "torch") and hasattr(trainer, "ema_p" if averaged else "p"):
+        return trainer.ema_p if averaged else trainer.p
+    if not averaged:
+        return trainer.get_params()
+    if hasattr(trainer, "ema_params"):
+        return trainer.ema_params()
+    return {k: _host_array(v) for k, v in trainer.ema_p.items()}
+
+
+def load_weights(net, weights, keep_trainer, stream=None):
+    """The mapping `weights` into evaluator `net`: load_device_params where the values are device tensors and the evaluator
+    has it -- it packs from them asynchronously, so the caller keeps what this returns alive -- else set_params with host
+    arrays (-> None).  keep_trainer: set_params must not drop the evaluator's own trainer (PolicyValueNet's _keep_trainer)."""
+    if getattr(next(iter(weights.values())), "is_cuda", False) and hasattr(net, "load_device_params"):
+        net.load_device_params(weights, *(() if stream is None else (stream,)))
+        return weights
+    net.set_params({k: _host_array(v) for k, v in weights.items()}, **({"_keep_trainer": True} if keep_trainer else {}))
+    return None
+
+
+def sync_weights(trainer, net, averaged=False, keep_trainer=False):
+    """The trainer's current (averaged: averaged) weights into evaluator `net`: HipTrainer.sync_evaluator, on torch's current
+    stream, where the trainer has it and the evaluator takes device tensors, else through the host."""
+    if hasattr(trainer, "sync_evaluator") and hasattr(net, "load_device_params") and (not averaged or hasattr(trainer, "ema_p")):
+        trainer.sync_evaluator(net, **({"ema": True} if averaged else {}))
+    else:
+        load_weights(net, trainer_weights(trainer, averaged, host=True), keep_trainer)
+
+
 def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epochs=8, kl_targ=0.02, evaluator=None, monitors=None):
     """train_mxnet.py:194-240: epochs x train_step with KL early stop and the adaptive LR multiplier.
     mini_batch: list of (state, mcts_prob, winner_z).  `evaluator.policy_value(states)` (the HIP
@@ -756,10 +795,7 @@ def policy_update(trainer, mini_batch, learn_rate=1e-3, lr_multiplier=1.0, epoch
         loss, entropy = trainer.train_step(batch, pis, zs, learn_rate * lr_multiplier)
         steps += 1
         if evaluator is not None:
-            if hasattr(trainer, "sync_evaluator") and hasattr(evaluator, "load_device_params"):
-                trainer.sync_evaluator(evaluator)
-            else:
-                evaluator.set_params(trainer.get_params())
+            sync_weights(trainer, evaluator)
         new_probs, new_v = pv(states)
         kl = float(np.mean(np.sum(old_probs * (np.log(old_probs + 1e-10) - np.log(new_probs + 1e-10)), axis=1)))
         if kl > kl_targ * 4:
