@@ -863,26 +863,10 @@ int launch_occupancy_planes(apz_engine* e, const float* planes, int n, int c_in,
     return APZ_OK;
 }
 
-void drop_forward_graphs(apz_engine* e) {
-    for (auto& kv : e->fwd_graphs) hipGraphExecDestroy(kv.second);
-    e->fwd_graphs.clear();
-    e->fwd_seen.clear();
-}
-
-// codes_dev != nullptr (stem_takes_codes(e) only): the position codes instead of `planes`
-int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsigned char* codes_dev, int n, float* probs,
-                float* values, float* logits = nullptr, float* vlogits = nullptr) {
-    if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
-    if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
-    if (n == 0) return APZ_OK;
-    e->prof_now = e->profiling && (e->prof_phase++ % e->prof_stride == 0);
-    if (e->profiling) resolve_ready(e);
-    // the whole forward under one pair, EVERY forward while profiling is on: sum / wall clock = the GPU-busy fraction of a
-    // measured window (two records per ~2 ms forward, at the forward's edges where the slot's `done` event sits anyway)
-    Timed whole(e, APZ_K_FORWARD, true);
-    float* trunk = nullptr;
-    int rc = run_trunk(e, m, planes, codes_dev, n, (int)e->convs.size() - 1, &trunk);
-    if (rc) return rc;
+// the heads on the trunk's output: the fused 8x8 kernel, or the two 1x1 convolutions, then the policy FullyConnected with
+// softmax and value head in one launch or two.  planes / codes_dev are the forward's input, for the legal policy's mask only
+int launch_heads(apz_engine* e, const float* trunk, const float* planes, const unsigned char* codes_dev, int n, float* probs,
+                 float* values, float* logits, float* vlogits) {
     const int hw = e->hw;
     // legal policy: byte m of row b of `occ` is non-zero where move m is occupied -- the codes as they are, or the planes'
     // occupancy staged in e->occ (timed with the head that reads it)
@@ -895,22 +879,18 @@ int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsi
             occ_stride = e->code_stride;
             return APZ_OK;
         }
-        if (int rc2 = launch_occupancy_planes(e, planes, n, e->cfg.c_in, e->cfg.height, e->cfg.width, e->occ)) return rc2;
+        if (int rc = launch_occupancy_planes(e, planes, n, e->cfg.c_in, e->cfg.height, e->cfg.width, e->occ)) return rc;
         occ = e->occ;
         occ_stride = hw;
         return APZ_OK;
     };
     if (e->small8) {                    // both 1x1 convolutions, both FullyConnected layers, softmax and tanh in one launch
         Timed tm(e, APZ_K_HEAD_FC);
-        if (int rc2 = stage_occupancy()) return rc2;
-        if (occ)
-            hipLaunchKernelGGL(apz::head8_legal_kernel, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0, e->stream, trunk, e->w6,
-                               e->b6, e->wfc_raw, e->bfc, e->wv, e->bv, occ, occ_stride, probs, values, logits, vlogits, n, e->clast);
-        else
-            hipLaunchKernelGGL(apz::head8_kernel, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0, e->stream, trunk, e->w6, e->b6,
-                               e->wfc_raw, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, e->clast);
+        if (int rc = stage_occupancy()) return rc;
+        hipLaunchKernelGGL(occ ? apz::head8_kernel<true> : apz::head8_kernel<false>, dim3(std::min(n, e->num_cu * 8)), dim3(256), 0,
+                           e->stream, trunk, e->w6, e->b6, e->wfc_raw, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n,
+                           e->clast, occ, occ_stride);
         HIP_TRY(hipGetLastError());
-        e->last_n = n;
         return APZ_OK;
     }
     {
@@ -932,28 +912,48 @@ int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsi
         const int tpw = (ntile + 3) / 4;
         // (framed engines take the two-launch form at every size: at 6x6 and 7x7, hw <= 64, the fused form would be a path
         // no engine has run before; the legal policy likewise: the fused softmax has no masked form)
-        if (int rc2 = stage_occupancy()) return rc2;
+        if (int rc = stage_occupancy()) return rc;
         if (tpw <= 1 && !e->frame_s && !occ) {
-            if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1>, lds)) return rc2;
+            if (int rc = need_lds(e, (const void*)apz::head_fc_kernel<1>, lds)) return rc;
             hipLaunchKernelGGL(apz::head_fc_kernel<1>, dim3(grid), dim3(256), lds, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw);
         } else if (tpw <= 4) {
             // the n-tiles over four workgroups per 16 boards, then one wavefront per board for softmax + value head
             const int lds1 = 16 * (4 * hw + 1) * (int)sizeof(float);
-            if (int rc2 = need_lds(e, (const void*)apz::head_fc_kernel<1, true>, lds1)) return rc2;
+            if (int rc = need_lds(e, (const void*)apz::head_fc_kernel<1, true>, lds1)) return rc;
             hipLaunchKernelGGL((apz::head_fc_kernel<1, true>), dim3(grid, tpw), dim3(256), lds1, e->stream, e->featp, e->featv,
                                e->wfc_pk, e->bfc, e->wv, e->bv, probs, values, logits, vlogits, n, hw, e->fc_logits);
-            if (occ)
-                hipLaunchKernelGGL(apz::head_softmax_value_legal_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits,
-                                   e->featv, e->wv, e->bv, occ, occ_stride, probs, values, logits, vlogits, n, hw, ntile * 16);
-            else
-                hipLaunchKernelGGL(apz::head_softmax_value_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits,
-                                   e->featv, e->wv, e->bv, probs, values, logits, vlogits, n, hw, ntile * 16);
+            hipLaunchKernelGGL(occ ? apz::head_softmax_value_kernel<true> : apz::head_softmax_value_kernel<false>,
+                               dim3((n + 3) / 4), dim3(256), 0, e->stream, e->fc_logits, e->featv, e->wv, e->bv, occ, occ_stride,
+                               probs, values, logits, vlogits, n, hw, ntile * 16);
         } else {
             return fail(APZ_E_UNSUPPORTED, "policy head: board too large");
         }
         HIP_TRY(hipGetLastError());
     }
+    return APZ_OK;
+}
+
+void drop_forward_graphs(apz_engine* e) {
+    for (auto& kv : e->fwd_graphs) hipGraphExecDestroy(kv.second);
+    e->fwd_graphs.clear();
+    e->fwd_seen.clear();
+}
+
+// trunk, then heads.  codes_dev != nullptr (stem_takes_codes(e) only): the position codes instead of `planes`
+int forward_dev(apz_engine* e, const FwdMode& m, const float* planes, const unsigned char* codes_dev, int n, float* probs,
+                float* values, float* logits = nullptr, float* vlogits = nullptr) {
+    if (!e->loaded) return fail(APZ_E_STATE, "weights not loaded");
+    if (n < 0 || n > e->cfg.max_batch) return fail(APZ_E_ARG, "batch exceeds max_batch");
+    if (n == 0) return APZ_OK;
+    e->prof_now = e->profiling && (e->prof_phase++ % e->prof_stride == 0);
+    if (e->profiling) resolve_ready(e);
+    // the whole forward under one pair, EVERY forward while profiling is on: sum / wall clock = the GPU-busy fraction of a
+    // measured window (two records per ~2 ms forward, at the forward's edges where the slot's `done` event sits anyway)
+    Timed whole(e, APZ_K_FORWARD, true);
+    float* trunk = nullptr;
+    if (int rc = run_trunk(e, m, planes, codes_dev, n, (int)e->convs.size() - 1, &trunk)) return rc;
+    if (int rc = launch_heads(e, trunk, planes, codes_dev, n, probs, values, logits, vlogits)) return rc;
     e->last_n = n;
     return APZ_OK;
 }
@@ -2595,15 +2595,10 @@ static int pv_loss_call(apz_engine* e, const void* logits_dev, const void* vlogi
         float* part = e->head_scratch.as<float>();      // the three terms per sample
         float* terms = loss3_dev ? part : (float*)nullptr;
         const dim3 grid((n + 3) / 4), block(256);
-        if (occ_dev)
-            hipLaunchKernelGGL(apz::pv_loss_legal_kernel, grid, block, 0, e->stream, (const float*)logits_dev,
-                               (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev, (const unsigned char*)occ_dev, n,
-                               e->hw, 1.0f / (float)n, terms, (float*)dlogits_dev, (float*)dvlogit_dev, (float*)probs_dev,
-                               (float*)values_dev);
-        else
-            hipLaunchKernelGGL(apz::pv_loss_kernel, grid, block, 0, e->stream, (const float*)logits_dev, (const float*)vlogit_dev,
-                               (const float*)pi_dev, (const float*)z_dev, n, e->hw, 1.0f / (float)n, terms, (float*)dlogits_dev,
-                               (float*)dvlogit_dev, (float*)probs_dev, (float*)values_dev);
+        hipLaunchKernelGGL(occ_dev ? apz::pv_loss_kernel<true> : apz::pv_loss_kernel<false>, grid, block, 0, e->stream,
+                           (const float*)logits_dev, (const float*)vlogit_dev, (const float*)pi_dev, (const float*)z_dev,
+                           (const unsigned char*)occ_dev, n, e->hw, 1.0f / (float)n, terms, (float*)dlogits_dev,
+                           (float*)dvlogit_dev, (float*)probs_dev, (float*)values_dev);
         if (loss3_dev)  // (value loss, policy loss, entropy): batch means, samples summed in index order
             hipLaunchKernelGGL(apz::colsum_kernel, dim3(1), dim3(256), 0, e->stream, (const float*)part, (float*)loss3_dev, n, 3,
                                1.0f / (float)n);

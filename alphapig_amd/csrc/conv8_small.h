@@ -30,6 +30,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_reduce.h"
 #include "wino_common.h"
 
 namespace apz {
@@ -208,27 +209,25 @@ __global__ __launch_bounds__(256) void conv8_kernel(const float* __restrict__ in
     }
 }
 
-__device__ __forceinline__ float head8_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float head8_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // x: dense [n][C][64] (the last convolution's output).  w6 [6][C] / b6 [6]: both 1x1 convolutions, BatchNorm folded (rows
 // 0-3 policy, 4-5 value); wfc [64][256], bfc [64]: policy FullyConnected on the row-major flatten of [4][8][8]
 // (fc_3_1_1); wv [128], bv [1]: value FullyConnected (fc_3_2_1).  probs [n][64], values [n]; logits / vlogits optional.
 // All sums in a fixed order: a board's bits do not depend on the batch.
+// LEGAL (apz_set_legal_policy): the softmax runs over the EMPTY cells only.  occ [n][occ_stride] u8, byte m != 0 where move
+// m is occupied (the position codes, or occupancy_planes_kernel's bytes); the plain form never reads it.  Both forms are
+// this one text up to and past the logit: an occupied cell is left out by selection, not arithmetic, so with no stone on
+// the board the two forms run the same operations on the same values, and whatever an occupied logit holds changes no
+// output bit.  Occupied cells get +0; a row without an empty cell is all +0; logits_out receives every raw logit.
+// (occ / occ_stride are the LAST arguments: the kernel spills SGPRs to VGPR lanes, so its scalar schedule follows the
+// argument layout, and this one leaves the plain form's vector code as it was -- profiles/r30_head_forms.md.)
+template <bool LEGAL>
 __global__ __launch_bounds__(256) void head8_kernel(const float* __restrict__ x, const float* __restrict__ w6,
                                                     const float* __restrict__ b6, const float* __restrict__ wfc,
                                                     const float* __restrict__ bfc, const float* __restrict__ wv,
                                                     const float* __restrict__ bv, float* __restrict__ probs,
                                                     float* __restrict__ values, float* __restrict__ logits_out,
-                                                    float* __restrict__ vlogits_out, int n, int C) {
+                                                    float* __restrict__ vlogits_out, int n, int C,
+                                                    const unsigned char* __restrict__ occ, int occ_stride) {
     __shared__ float part[4][6][64];
     __shared__ __attribute__((aligned(16))) float feat[6 * 64];       // [4][64] policy features, then [2][64] value features
     __shared__ float fcp[4][64];
@@ -276,97 +275,22 @@ __global__ __launch_bounds__(256) void head8_kernel(const float* __restrict__ x,
         __syncthreads();
         if (wave == 0) {
             const float lg = (((fcp[0][lane] + fcp[1][lane]) + fcp[2][lane]) + fcp[3][lane]) + bfc[lane];
-            const float mx = head8_wave_max(lg);
-            const float ex = expf(lg - mx);
-            const float sm = head8_wave_sum(ex);
-            probs[(size_t)b * 64 + lane] = ex / sm;
+            const bool emp = !LEGAL || occ[(size_t)b * occ_stride + lane] == 0;
+            const float mx = wave_max(emp ? lg : -INFINITY);
+            const float ex = emp ? expf(lg - mx) : 0.f;
+            const float sm = wave_sum(ex);
+            probs[(size_t)b * 64 + lane] = emp ? ex / sm : 0.f;
             if (logits_out) logits_out[(size_t)b * 64 + lane] = lg;
         } else if (wave == 1) {
             float d = fmaf(feat[256 + lane], wv[lane], 0.f);
             d = fmaf(feat[320 + lane], wv[64 + lane], d);
-            d = head8_wave_sum(d) + bv[0];
+            d = wave_sum(d) + bv[0];
             if (lane == 0) {
                 values[b] = tanhf(d);
                 if (vlogits_out) vlogits_out[b] = d;
             }
         }
         __syncthreads();                            // part / feat / fcp are reused by the next board
-    }
-}
-
-// The legal-move form of head8_kernel (apz_set_legal_policy): the softmax over the EMPTY cells only.  occ [n][occ_stride]
-// u8, byte m != 0 where move m is occupied (the position codes, or occupancy_planes_kernel's bytes).  Everything up to the
-// logit is head8_kernel's text; an occupied cell is then left out by selection, so with no stone on the board both kernels
-// run the same operations on the same values, and whatever an occupied logit holds changes no output bit.  Occupied cells
-// get +0; a row without an empty cell is all +0.
-__global__ __launch_bounds__(256) void head8_legal_kernel(const float* __restrict__ x, const float* __restrict__ w6,
-                                                          const float* __restrict__ b6, const float* __restrict__ wfc,
-                                                          const float* __restrict__ bfc, const float* __restrict__ wv,
-                                                          const float* __restrict__ bv, const unsigned char* __restrict__ occ,
-                                                          int occ_stride, float* __restrict__ probs, float* __restrict__ values,
-                                                          float* __restrict__ logits_out, float* __restrict__ vlogits_out, int n,
-                                                          int C) {
-    __shared__ float part[4][6][64];
-    __shared__ __attribute__((aligned(16))) float feat[6 * 64];
-    __shared__ float fcp[4][64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cq = C >> 2;
-    for (int b = blockIdx.x; b < n; b += gridDim.x) {
-        {
-            const float* xb = x + ((size_t)b * C + wave * cq) * 64 + lane;
-            const float* wq = w6 + wave * cq;
-            float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            for (int c0 = 0; c0 < cq; c0 += 16) {
-                float v[16];
-#pragma unroll
-                for (int u = 0; u < 16; u++) v[u] = xb[(size_t)(c0 + u) * 64];
-#pragma unroll
-                for (int u = 0; u < 16; u++)
-#pragma unroll
-                    for (int o = 0; o < 6; o++) a[o] = fmaf(wq[o * C + c0 + u], v[u], a[o]);
-            }
-#pragma unroll
-            for (int o = 0; o < 6; o++) part[wave][o][lane] = a[o];
-        }
-        __syncthreads();
-        for (int i = tid; i < 6 * 64; i += 256) {
-            const int o = i >> 6, p = i & 63;
-            const float s = ((part[0][o][p] + part[1][o][p]) + part[2][o][p]) + part[3][o][p];
-            feat[i] = fmaxf(s + b6[o], 0.f);
-        }
-        __syncthreads();
-        {
-            const f32x4* wr = reinterpret_cast<const f32x4*>(wfc + (size_t)lane * 256 + wave * 64);
-            const f32x4* fr = reinterpret_cast<const f32x4*>(feat + wave * 64);
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const f32x4 w4 = wr[k], f4 = fr[k];
-#pragma unroll
-                for (int e = 0; e < 4; e++) s = fmaf(w4[e], f4[e], s);
-            }
-            fcp[wave][lane] = s;
-        }
-        __syncthreads();
-        if (wave == 0) {
-            const float lg = (((fcp[0][lane] + fcp[1][lane]) + fcp[2][lane]) + fcp[3][lane]) + bfc[lane];
-            const bool emp = occ[(size_t)b * occ_stride + lane] == 0;
-            const float mx = head8_wave_max(emp ? lg : -INFINITY);
-            const float ex = emp ? expf(lg - mx) : 0.f;
-            const float sm = head8_wave_sum(ex);
-            probs[(size_t)b * 64 + lane] = emp ? ex / sm : 0.f;
-            if (logits_out) logits_out[(size_t)b * 64 + lane] = lg;
-        } else if (wave == 1) {
-            float d = fmaf(feat[256 + lane], wv[lane], 0.f);
-            d = fmaf(feat[320 + lane], wv[64 + lane], d);
-            d = head8_wave_sum(d) + bv[0];
-            if (lane == 0) {
-                values[b] = tanhf(d);
-                if (vlogits_out) vlogits_out[b] = d;
-            }
-        }
-        __syncthreads();
     }
 }
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv3x3_mfma.h"
+#include "wave_reduce.h"
 
 namespace apz {
 
@@ -63,17 +64,6 @@ __global__ __launch_bounds__(256) void head_conv1x1_kernel(const float* __restri
             if (Q > 1) __syncthreads();                   // `part` is reused by the next board
         }
     }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // One workgroup = 16 boards.  K = 4*HW (policy FC depth), NOUT = HW.
@@ -267,8 +257,17 @@ __global__ __launch_bounds__(256) void head_fc_kernel(const float* __restrict__ 
 
 // Second half of the split policy head: one wavefront per board -- row softmax of the logits head_fc_kernel<1, true>
 // left in logits_ws [n][ldl] (SoftmaxActivation, instance mode), and the value head (2*HW -> 1 dot product + tanh).
+// LEGAL (apz_set_legal_policy): the softmax runs over the EMPTY cells of the board only.  occ [n][occ_stride] u8: byte
+// m != 0 where move m is occupied -- the forward's position codes themselves, or what occupancy_planes_kernel made of its
+// planes; the plain form never reads it.  Both forms are this one text: the same ownership of cells by lanes and the same
+// reduction trees, and an occupied cell is left out by SELECTION, not arithmetic (its logit never enters an fmaxf, an expf
+// or a sum).  So with no stone on the board the two forms execute the same operations on the same values, and a NaN, an
+// inf or the row's largest logit on an occupied cell changes no output bit.  Occupied cells get +0; a row without an empty
+// cell is all +0.  logits_out receives every raw logit in both forms; the value head does not know the form.
+template <bool LEGAL>
 __global__ __launch_bounds__(256) void head_softmax_value_kernel(const float* __restrict__ logits_ws, const float* __restrict__ featv,
                                                                  const float* __restrict__ wv, const float* __restrict__ bv,
+                                                                 const unsigned char* __restrict__ occ, int occ_stride,
                                                                  float* __restrict__ probs, float* __restrict__ values,
                                                                  float* __restrict__ logits_out, float* __restrict__ vlogits_out,
                                                                  int n, int HW, int ldl) {
@@ -278,67 +277,14 @@ __global__ __launch_bounds__(256) void head_softmax_value_kernel(const float* __
     // (HW <= 256: four logits per lane; 2 HW <= 512: eight value-head terms per lane)
     const float* row = logits_ws + (size_t)r * ldl;
     const float* fv = featv + (size_t)r * 2 * HW;
-    float l[4], f[8], w[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) l[i] = (lane + 64 * i < HW) ? row[lane + 64 * i] : -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int o = lane + 64 * i;
-        f[i] = o < 2 * HW ? fv[o] : 0.f;
-        w[i] = o < 2 * HW ? wv[o] : 0.f;
-    }
-    const float m = wave_max(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])));
-    float ex[4], s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        ex[i] = (lane + 64 * i < HW) ? expf(l[i] - m) : 0.f;
-        s += ex[i];
-    }
-    s = wave_sum(s);
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int o = lane + 64 * i;
-        if (o < HW) {
-            probs[(size_t)r * HW + o] = ex[i] * inv;
-            if (logits_out) logits_out[(size_t)r * HW + o] = l[i];
-        }
-    }
-    float d = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d = fmaf(f[i], w[i], d);
-    d = wave_sum(d) + bv[0];
-    if (lane == 0) {
-        values[r] = tanhf(d);
-        if (vlogits_out) vlogits_out[r] = d;
-    }
-}
-
-// The legal-move form of head_softmax_value_kernel (apz_set_legal_policy): the softmax runs over the EMPTY cells of the
-// board only.  occ [n][occ_stride] u8: byte m != 0 where move m is occupied -- the forward's position codes themselves, or
-// what occupancy_planes_kernel made of its planes.  Same ownership of cells by lanes and the same reduction trees as the
-// kernel above, and an occupied cell is left out by SELECTION (its logit never enters an fmaxf, an expf or a sum): with no
-// stone on the board the two kernels execute the same operations on the same values, and a NaN, an inf or the row's largest
-// logit on an occupied cell changes no output bit.  Occupied cells get +0; a row without an empty cell is all +0.
-// logits_out still receives every raw logit; the value head is the kernel's above.
-__global__ __launch_bounds__(256) void head_softmax_value_legal_kernel(const float* __restrict__ logits_ws, const float* __restrict__ featv,
-                                                                       const float* __restrict__ wv, const float* __restrict__ bv,
-                                                                       const unsigned char* __restrict__ occ, int occ_stride,
-                                                                       float* __restrict__ probs, float* __restrict__ values,
-                                                                       float* __restrict__ logits_out, float* __restrict__ vlogits_out,
-                                                                       int n, int HW, int ldl) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const float* row = logits_ws + (size_t)r * ldl;
-    const float* fv = featv + (size_t)r * 2 * HW;
     const unsigned char* oc = occ + (size_t)r * occ_stride;
     float l[4], f[8], w[8];
-    bool emp[4];
+    bool emp[4];                                // the cell is on the board and (LEGAL) empty
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int o = lane + 64 * i;
         l[i] = o < HW ? row[o] : -INFINITY;
-        emp[i] = o < HW && oc[o] == 0;
+        emp[i] = o < HW && (!LEGAL || oc[o] == 0);
     }
 #pragma unroll
     for (int i = 0; i < 8; i++) {

@@ -297,78 +297,35 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 //   p = softmax(logits), v = tanh(u);   terms[i] = ((z - v)^2, -sum_j pi_j log p_j, -sum_j p_j log p_j)
 //   dlogits = (p * sum_j pi_j - pi) * gscale,   du = 2 (v - z) (1 - v^2) * gscale        (gscale = 1 / batch: the means)
 // probs / values (may be NULL) get p and v (the inference outputs of the same forward).
-__global__ __launch_bounds__(256) void pv_loss_kernel(const float* __restrict__ logits, const float* __restrict__ u,
-                                                      const float* __restrict__ pi, const float* __restrict__ z, int n, int HW,
-                                                      float gscale, float* __restrict__ terms, float* __restrict__ dlogits,
-                                                      float* __restrict__ du, float* __restrict__ probs, float* __restrict__ values) {
-    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const float* lr = logits + (size_t)i * HW;
-    float m = -INFINITY;
-    for (int j = lane; j < HW; j += 64) m = fmaxf(m, lr[j]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int j = lane; j < HW; j += 64) s += expf(lr[j] - m);
-    s = wave_sum(s);
-    const float logs = logf(s);
-    float ce = 0.f, ent = 0.f, spi = 0.f;
-    for (int j = lane; j < HW; j += 64) {
-        const float lp = lr[j] - m - logs, p = expf(lp);
-        const float t = pi ? pi[(size_t)i * HW + j] : 0.f;
-        ce -= t * lp;
-        ent -= p * lp;
-        spi += t;
-        if (probs) probs[(size_t)i * HW + j] = p;
-    }
-    ce = wave_sum(ce);
-    ent = wave_sum(ent);
-    spi = wave_sum(spi);
-    if (dlogits)
-        for (int j = lane; j < HW; j += 64) {
-            const float p = expf(lr[j] - m - logs);
-            dlogits[(size_t)i * HW + j] = (p * spi - pi[(size_t)i * HW + j]) * gscale;
-        }
-    if (lane == 0) {
-        const float v = tanhf(u[i]);
-        if (values) values[i] = v;
-        if (terms) {
-            const float d = (z ? z[i] : 0.f) - v;
-            terms[(size_t)i * 3 + 0] = d * d;
-            terms[(size_t)i * 3 + 1] = ce;
-            terms[(size_t)i * 3 + 2] = ent;
-        }
-        if (du) du[i] = 2.f * (v - z[i]) * (1.f - v * v) * gscale;
-    }
-}
-
-// The legal-move form of pv_loss_kernel (apz_pv_loss_legal): occ [n][HW] u8, byte j != 0 where move j is occupied.  The
+// LEGAL (apz_pv_loss_legal): occ [n][HW] u8, byte j != 0 where move j is occupied; the plain form never reads it.  The
 // log-softmax, the cross-entropy, the entropy and sum_j pi_j run over the EMPTY cells only; probs and dlogits are +0 on the
-// occupied ones.  Same ownership of cells by lanes and the same reduction trees as the kernel above, and an occupied cell is
-// left out by selection (its logit and its pi never enter an operation): with no stone on the board the two kernels execute
-// the same operations on the same values, and whatever an occupied logit holds changes no output bit.  A row without an
-// empty cell: ce = ent = 0, probs and dlogits +0.  The value terms are the kernel's above.
-__global__ __launch_bounds__(256) void pv_loss_legal_kernel(const float* __restrict__ logits, const float* __restrict__ u,
-                                                            const float* __restrict__ pi, const float* __restrict__ z,
-                                                            const unsigned char* __restrict__ occ, int n, int HW, float gscale,
-                                                            float* __restrict__ terms, float* __restrict__ dlogits,
-                                                            float* __restrict__ du, float* __restrict__ probs,
-                                                            float* __restrict__ values) {
+// occupied ones.  Both forms are this one text: the same ownership of cells by lanes and the same reduction trees, and an
+// occupied cell is left out by selection, not arithmetic (its logit and its pi never enter an operation).  So with no stone
+// on the board the two forms execute the same operations on the same values, and whatever an occupied logit holds changes
+// no output bit.  A row without an empty cell: ce = ent = 0, probs and dlogits +0.  The value terms do not know the form.
+template <bool LEGAL>
+__global__ __launch_bounds__(256) void pv_loss_kernel(const float* __restrict__ logits, const float* __restrict__ u,
+                                                      const float* __restrict__ pi, const float* __restrict__ z,
+                                                      const unsigned char* __restrict__ occ, int n, int HW, float gscale,
+                                                      float* __restrict__ terms, float* __restrict__ dlogits,
+                                                      float* __restrict__ du, float* __restrict__ probs,
+                                                      float* __restrict__ values) {
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const float* lr = logits + (size_t)i * HW;
     const unsigned char* oc = occ + (size_t)i * HW;
     float m = -INFINITY;
     for (int j = lane; j < HW; j += 64)
-        if (!oc[j]) m = fmaxf(m, lr[j]);
+        if (!LEGAL || oc[j] == 0) m = fmaxf(m, lr[j]);
     m = wave_max(m);
     float s = 0.f;
     for (int j = lane; j < HW; j += 64)
-        if (!oc[j]) s += expf(lr[j] - m);
+        if (!LEGAL || oc[j] == 0) s += expf(lr[j] - m);
     s = wave_sum(s);
     const float logs = logf(s);
     float ce = 0.f, ent = 0.f, spi = 0.f;
     for (int j = lane; j < HW; j += 64) {
-        if (!oc[j]) {
+        if (!LEGAL || oc[j] == 0) {
             const float lp = lr[j] - m - logs, p = expf(lp);
             const float t = pi ? pi[(size_t)i * HW + j] : 0.f;
             ce -= t * lp;
@@ -385,7 +342,7 @@ __global__ __launch_bounds__(256) void pv_loss_legal_kernel(const float* __restr
     if (dlogits)
         for (int j = lane; j < HW; j += 64) {
             float g = 0.f;
-            if (!oc[j]) {
+            if (!LEGAL || oc[j] == 0) {
                 const float p = expf(lr[j] - m - logs);
                 g = (p * spi - pi[(size_t)i * HW + j]) * gscale;
             }

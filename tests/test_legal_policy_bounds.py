@@ -1,5 +1,5 @@
-"""The error envelopes of the legal-move forms of the heads and of the loss (head_softmax_value_legal_kernel,
-head8_legal_kernel, pv_loss_legal_kernel): the bars of tests/test_head_loss_bounds.py with t_j, H and
+"""The error envelopes of the legal-move forms of the heads and of the loss (head_softmax_value_kernel<true>,
+head8_kernel<true>, pv_loss_kernel<true>): the bars of tests/test_head_loss_bounds.py with t_j, H and
 LAM_j taken over the EMPTY cells E of a row -- t_j = l_j - max_E l, H = sum_E p_k |t_k|, every sum over cells a sum over E
 -- the same ROOM and the same cuts; a float32 NumPy restatement of each masked kernel's operation order; and CPU tests that
 every restatement stays inside its bar against float64 with ROOM to spare.  tests/test_gpu_legal_policy.py asserts the same
@@ -72,7 +72,7 @@ def _masked_max(l, emp):
 
 
 def legal_softmax_tail_f32(logits, occ, form, max_over="empty"):
-    """form "mul": head_softmax_value_legal_kernel;  "div": head8_legal_kernel.  max_over "all": what a kernel that took its
+    """form "mul": head_softmax_value_kernel<true>;  "div": head8_kernel<true>.  max_over "all": what a kernel that took its
     maximum over every cell would compute (kept to show what "max on a stone" catches)"""
     l, emp = np.asarray(logits, dtype=F32), np.asarray(occ) == 0
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
@@ -85,7 +85,7 @@ def legal_softmax_tail_f32(logits, occ, form, max_over="empty"):
 
 
 def legal_pv_loss_f32(logits, u, pi, z, occ):
-    """pv_loss_legal_kernel + colsum_kernel -> dict like alphapig_amd.hipconv.pv_loss(occ=...)"""
+    """pv_loss_kernel<true> + colsum_kernel -> dict like alphapig_amd.hipconv.pv_loss(occ=...)"""
     l, u, pi, z = (np.asarray(a, dtype=F32) for a in (logits, u, pi, z))
     emp = np.asarray(occ) == 0
     n = l.shape[0]

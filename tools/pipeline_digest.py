@@ -16,8 +16,8 @@ games: plain, replay=compact, ema_decay=0.5 with a trainer that keeps an average
 followed by a resume to 6 batches, sgf_batches=1 on the golden records.
 Without it: PolicyValueNet + HipTrainer, the 8x8 simple net (an evaluator passed in) and a 15x15 resnet of 1 block x 128
 (the evaluator the pipeline builds), batch_size 16, n_playout 8, 4 concurrent games, 3 game batches: plain, replay=device,
-train_arith=f16x2, step_guard + clip_norm, ema_decay, legal_policy, act_scale=auto, train_framed on side 6, checkpoint and
-resume.  The same run under rocprofv3 --kernel-trace is the launch sequence tools/route_trace.py --compare --whole compares.
+train_arith=f16x2, step_guard + clip_norm, ema_decay, legal_policy (both nets: the fused 8x8 head, the two-launch head and
+the loss in their legal-move forms), act_scale=auto, train_framed on side 6, checkpoint and resume.  The same run under rocprofv3 --kernel-trace is the launch sequence tools/route_trace.py --compare --whole compares.
 
 --workdir DIR keeps the checkpoints under DIR/<case>/; --checkpoints-from DIR2 makes every resume read the checkpoint
 another run (another tree's) left under DIR2/<case>/ instead of its own: both must continue to the same digest."""
@@ -198,6 +198,7 @@ def real(args):
                  conf(tag + "_ema_ckpt", side, game_batch_num=2, checkpoint_every=2, ema_decay=0.9, checkpoint_buffer=True), args,
                  resume_to=4)
     run_case("resnet 15x15 train_arith=f16x2", resnet, conf("resnet_f16x2", train_arith="f16x2"), args)
+    run_case("simple 8x8 legal_policy", simple, conf("simple_legal", 8, legal_policy=True), args)
     run_case("resnet 15x15 legal_policy", resnet, conf("resnet_legal", legal_policy=True), args)
     run_case("resnet 15x15 act_scale=auto", resnet, conf("resnet_act", act_scale="auto"), args)
     run_case("resnet 6x6 train_framed", resnet, conf("resnet_framed", 6, train_framed=True), args)

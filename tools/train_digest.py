@@ -9,8 +9,9 @@ last step's gradients, every tensor in name order; the step's (loss, entropy) pa
 residual path), the 8x8 simple net (n = 4), one f16x2 step that overflows and is repeated exactly (bnA1_gamma of one
 channel at 5e3, n = 40), and one policy_update each on a list mini-batch and on a DeviceBatch.  Behind those, the guard
 and the average: guarded f32, guarded f32 with a clip_norm that clips, a guarded step that is skipped (NaN z) between two
-good ones, the overflowing step guarded, ema_decay on in both arithmetics, framed boards of side 6 and 14, and a state() ->
-fresh trainer -> load_state() -> one more step round trip with guard and average on.  Every case also prints its counters
+good ones, the overflowing step guarded, ema_decay on in both arithmetics, framed boards of side 6 and 14, legal_policy at
+15x15 and 8x8 (the states are random planes: about two cells in three count as occupied), and a state() -> fresh trainer ->
+load_state() -> one more step round trip with guard and average on.  Every case also prints its counters
 and the guard's three last_* values, and the averaged weights' digest where they exist.  The tests "the same bits on
 every run" are what makes the comparison meaningful.  The same run under rocprofv3 --kernel-trace is the launch sequence
 that tools/route_trace.py --compare --whole compares."""
@@ -123,6 +124,8 @@ def main():
     steps("average f16x2", "resnet", 15, 6, 2, 128, seed=11, trunk_arith="f16x2", ema_decay=0.9)
     steps("framed 6x6 2x128 n=6", "resnet", 6, 6, 2, 128, seed=14, framed=True)
     steps("framed 14x14 2x128 n=6", "resnet", 14, 6, 2, 128, seed=15, framed=True)
+    steps("legal_policy 15x15 2x128 n=6", "resnet", 15, 6, 2, 128, seed=16, legal_policy=True)
+    steps("legal_policy 8x8 1x64 n=4", "resnet", 8, 4, 1, 64, seed=17, legal_policy=True)
     round_trip()
 
 
