@@ -132,7 +132,8 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_set_act_scale_auto", "apz_set_trunk_uniform", "apz_replay_gather", "apz_forward_dev_host",
                "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys",
                "apz_bn_fwd_frame", "apz_bn_bwd_frame", "apz_frame_planes_dev", "apz_conv1x1_fwd_frame", "apz_conv1x1_bwd2_frame",
-               "apz_set_legal_policy", "apz_get_legal_policy", "apz_occupancy_planes", "apz_pv_loss_legal"]
+               "apz_set_legal_policy", "apz_get_legal_policy", "apz_occupancy_planes", "apz_pv_loss_legal",
+               "apz_conv15h_fwd"]
 
 
 def _one_hip_runtime():
@@ -251,6 +252,7 @@ def hip():
         "apz_wino_packed_size": (C.c_int64, []),
         "apz_wino_pack": (C.c_int, [vp, vp, C.c_int, vp, vp]),
         "apz_wino_pack_many": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+        "apz_conv15h_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "apz_wino_conv": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "apz_bn_fwd": (C.c_int, [vp] * 10 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp]),
         "apz_wino_conv_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),

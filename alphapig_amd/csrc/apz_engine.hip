@@ -24,6 +24,7 @@
 #include "trunk15_wino3h16.h"
 #include "trunk15_wino3hs.h"
 #include "conv8_split.h"
+#include "conv15_split.h"
 #include "conv8_small.h"
 #include "wgrad_wino3.h"
 #include "wgrad_wino3h.h"
@@ -81,7 +82,7 @@ struct ConvLayer {
     void* upk3b = nullptr;  // trunk15_wino3b_kernel (apz_set_trunk_arith(APZ_ARITH_BF16X3) only): U as three bf16 terms (Wino3B)
     void* upk3h = nullptr;  // trunk15_wino3h_kernel (APZ_ARITH_F16X2 only): U S[co] as two fp16 terms (Wino3H)
     float* bias3h = nullptr;   // ... and its [128 biases][128 x 1 / S[co]]
-    void* wpk8h = nullptr;  // conv8h_kernel (8x8 boards, APZ_ARITH_F16X2, C_in a multiple of 64): w S[co] as two fp16 terms (Conv8H)
+    void* wpk8h = nullptr;  // conv8h_kernel / conv15h_kernel (8x8 boards and generic 15x15 nets, APZ_ARITH_F16X2, C_in a multiple of 64): w S[co] as two fp16 terms (Conv8H)
     float* bias8h = nullptr;   // ... and its [cout biases][cout x 1 / S[co]]
     float* bias = nullptr;
     // APZ_ARITH_F16X2, 15x15 trunk layers: the static exponent a of the layer's input scale 2^a (trunk15_wino3h16.h,
@@ -245,6 +246,7 @@ struct apz_engine {
     DeviceBuffer guard_part;                       // apz_grad_norm / apz_adam_step_guarded: [32 ntensors] doubles, then as many words
     DeviceBuffer gather_entries;                   // apz_replay_gather: device copy of the entry words
     DeviceBuffer wino_scratch[2];                  // apz_wino_conv: rows16 input / output copies
+    DeviceBuffer conv15h_scratch;                  // apz_conv15h_fwd: the call's scale / shift, bias8h and packed weights
     hipStream_t scratch_stream = nullptr;          // the stream of the last entry point that may have used the scratch buffers
     bool scratch_stream_valid = false;
     TicketExchange<apz::Wino3S> w3s;         // trunk15_wino3s_kernel
@@ -660,7 +662,23 @@ int launch_conv8h_t(apz_engine* e, const FwdMode& m, const ConvLayer& L, const f
     return APZ_OK;
 }
 
-// The kernel of a 15x15 trunk convolution or of an 8x8 board: DESIGN.md section 4, "Which arithmetic a batch gets"
+// ... and on 15x15 boards (conv15_split.h): the same items and weights, the same rule for the grid
+template <bool RESID>
+int launch_conv15h_t(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n, int relu,
+                     unsigned* flag) {
+    using T = apz::Conv15H;
+    const int grid = (int)T::grid_for((long)n * (L.cout / 16), e->num_cu);
+    if (int rc = need_lds(e, (const void*)apz::conv15h_kernel<RESID>, T::LDS_BYTES)) return rc;
+    hipLaunchKernelGGL((apz::conv15h_kernel<RESID>), dim3(grid), dim3(256), T::LDS_BYTES, e->stream, in, (const void*)L.wpk8h,
+                       L.bias8h, resid, out, n, L.cin, L.cout, relu, flag);
+    HIP_TRY(hipGetLastError());
+    return APZ_OK;
+}
+
+int launch_conv_generic(apz_engine* e, const ConvLayer& L, const float* in, const float* resid, float* out, int n);
+
+// The kernel of a 15x15 trunk convolution, of an 8x8 board or of a generic net's layer: DESIGN.md section 4, "Which
+// arithmetic a batch gets"
 enum class Route {
     F16X2_SMALL,   // trunk15_wino3hs_kernel: f16x2, <= 32 boards (apz_set_trunk_uniform)
     F16X2_K8,      // trunk15_wino3h_kernel: batched f16x2, 8-channel chunks (APZ_F16X2_K8=1)
@@ -669,7 +687,9 @@ enum class Route {
     EXACT,         // trunk15_wino3s_kernel / trunk15_wino3_kernel: exact fp32; small, quarter or batched by launch_wino3_t
     DIRECT,        // trunk15_ring_kernel: the direct convolution, in-tree cross-check of the Winograd kernels
     CONV8H,        // conv8h_kernel: 8x8 boards, f16x2
-    CONV8          // conv8_kernel: 8x8 boards, exact fp32
+    CONV8,         // conv8_kernel: 8x8 boards, exact fp32
+    CONV15H,       // conv15h_kernel: generic 15x15 nets, f16x2
+    GENERIC        // conv3x3_mfma_kernel: generic nets, exact fp32 (launch_conv_generic)
 };
 
 // (engine configuration, layer, batch size, mode) -> kernel, first match wins: the one place that decides it
@@ -677,6 +697,7 @@ Route trunk_route(const apz_engine* e, const ConvLayer& L, int n, const FwdMode&
     // the f16x2 kernels raise a word: a forward without one (and the exact repeat, and a measuring pass) runs exact fp32
     const bool f16x2 = e->trunk_arith == APZ_ARITH_F16X2 && !m.exact && m.ovf;
     if (e->small8) return f16x2 && L.wpk8h ? Route::CONV8H : Route::CONV8;     // one kernel family for every batch size
+    if (!e->ring) return f16x2 && L.wpk8h ? Route::CONV15H : Route::GENERIC;   // generic nets: likewise
     if (e->trunk_kernel != APZ_TRUNK_WINOGRAD || !L.upk2) return Route::DIRECT;
     const bool batched = n > apz::Wino3S::MAX_BOARDS || e->no_small_trunk || m.batched;
     if (f16x2 && L.upk3h) {
@@ -701,6 +722,8 @@ int launch_routed_t(apz_engine* e, const FwdMode& m, Route r, const ConvLayer& L
         case Route::DIRECT: return launch_trunk_ring_t<4>(e, L, in, resid, out, n);
         case Route::CONV8H: return launch_conv8h_t<RESID>(e, m, L, in, resid, out, n);
         case Route::CONV8: return launch_conv8_t<RESID, false>(e, L, in, resid, out, n);
+        case Route::CONV15H: return launch_conv15h_t<RESID>(e, L, in, resid, out, n, 1, m.ovf);
+        case Route::GENERIC: return launch_conv_generic(e, L, in, resid, out, n);
     }
 }
 
@@ -792,7 +815,6 @@ int launch_first_layer(apz_engine* e, const FwdMode& m, const float* planes, con
 
 // a layer behind the first
 int launch_conv(apz_engine* e, const FwdMode& m, const ConvLayer& L, const float* in, const float* resid, float* out, int n) {
-    if (!e->small8 && !e->ring) return launch_conv_generic(e, L, in, resid, out, n);
     if (int rc = launch_routed(e, m, L, in, resid, out, n)) return rc;
     // framed engines: the off-board cells zero again (skipped behind the net's last layer: the heads read on-board cells only)
     return e->frame_s && &L != &e->convs.back() ? launch_frame_clear(e, out, n) : APZ_OK;
@@ -1288,7 +1310,8 @@ int alloc_packed(apz_engine* e) {
         get(&L.wpk, frags * (wino ? 12 : 9) * sizeof(float));
         get(&L.bias, L.cout * sizeof(float));
         if (e->small8) get(&L.wpk12, frags * 12 * sizeof(float));
-        if (e->small8 && f16x2 && apz::Conv8H::supports(L.cin, L.cout)) {
+        // (generic engines take APZ_ARITH_F16X2 on 15x15 boards only: apz_set_trunk_arith)
+        if ((e->small8 || !e->ring) && f16x2 && apz::Conv8H::supports(L.cin, L.cout)) {
             get(&L.wpk8h, apz::Conv8H::pk_bytes(L.cin, L.cout));
             get(&L.bias8h, 2 * (size_t)L.cout * sizeof(float));
         }
@@ -1385,7 +1408,7 @@ struct StreamScope {      // run the engine's launch helpers on a caller-supplie
     StreamScope(apz_engine* e_, void* s) : e(e_), saved(e_->stream) {
         if (s != APZ_ENGINE_STREAM) e->stream = (hipStream_t)s;   // NULL is a valid handle: the null stream
         // The training entry points share per-engine scratch (the DeviceBuffers of apz_engine: bn_part, wgw_scratch,
-        // head_scratch, adam_tab, guard_part, gather_entries, wino_scratch; and fold_ws).  Calls on ONE stream are ordered by the
+        // head_scratch, adam_tab, guard_part, gather_entries, wino_scratch, conv15h_scratch; and fold_ws).  Calls on ONE stream are ordered by the
         // stream; a caller that switches streams gets the new stream ordered behind everything queued on the previous
         // one, so two streams never work on the scratch at once.
         if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
@@ -1453,7 +1476,7 @@ void apz_destroy(apz_engine* e) {
     for (void* p : dev)
         if (p) hipFree(p);
     for (DeviceBuffer* b : {&e->bn_part, &e->wgw_scratch, &e->head_scratch, &e->adam_tab, &e->guard_part, &e->gather_entries,
-                            &e->wino_scratch[0], &e->wino_scratch[1]})
+                            &e->wino_scratch[0], &e->wino_scratch[1], &e->conv15h_scratch})
         b->release();
     if (e->perm_pinv) hipFree(e->perm_pinv);
     if (e->occ) hipFree(e->occ);
@@ -1927,6 +1950,41 @@ int apz_conv3x3_fwd(apz_engine* e, const void* x_dev, const void* wpk_dev, const
         L.wpk = nullptr;
         L.bias = nullptr;
         if (rc == APZ_E_UNSUPPORTED) return fail(rc, "conv3x3_fwd: unsupported board size");
+        return rc;
+    });
+}
+
+int apz_conv15h_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const void* bias_dev, const void* resid_dev,
+                    void* y_dev, int n, int cin, int cout, int relu, void* flag_dev, void* stream) {
+    if (!e || !x_dev || !w_dev || !y_dev || !flag_dev || n < 1 || cin < 1 || cout < 1) return fail(APZ_E_ARG, "bad argument");
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, "conv15h_fwd: 15x15 boards only");
+    if (!apz::Conv15H::supports(cin, cout))
+        return fail(APZ_E_UNSUPPORTED, "conv15h_fwd: C_in must be a multiple of 64 and C_out a multiple of 16, not " +
+                                           std::to_string(cin) + " -> " + std::to_string(cout));
+    if ((int64_t)cin * apz::Conv15H::HW * 4 > 0x7fffffffLL || (int64_t)n * (cout / 16) > 0x7fffffffLL)
+        return fail(APZ_E_UNSUPPORTED, "conv15h_fwd: too many channels or items for one launch");
+    return train_call(e, stream, [&]() -> int {
+        // [scale cout][shift cout] doubles, [bias][1 / S] floats, the packed weights (16-byte aligned: cout is a multiple of 16)
+        const size_t fold_bytes = 2 * (size_t)cout * sizeof(double), bias_bytes = 2 * (size_t)cout * sizeof(float);
+        if (int rc = e->conv15h_scratch.reserve(fold_bytes + bias_bytes + apz::Conv8H::pk_bytes(cin, cout))) return rc;
+        char* base = e->conv15h_scratch.as<char>();
+        double* scale = (double*)base;
+        ConvLayer L;
+        L.cin = cin;
+        L.cout = cout;
+        L.bias8h = (float*)(base + fold_bytes);
+        L.wpk8h = base + fold_bytes + bias_bytes;
+        hipLaunchKernelGGL(apz::conv15h_plain_fold_kernel, dim3((cout + 63) / 64), dim3(64), 0, e->stream, (const float*)bias_dev,
+                           scale, scale + cout, cout);
+        hipLaunchKernelGGL(apz::pack_conv8h_kernel, dim3(cout), dim3(256), 0, e->stream, (const float*)w_dev, scale, scale + cout,
+                           (unsigned short*)L.wpk8h, L.bias8h, cin, cout);
+        HIP_TRY(hipGetLastError());
+        const int rc = with_flag(resid_dev != nullptr, [&](auto RESID) {
+            return launch_conv15h_t<RESID()>(e, L, (const float*)x_dev, (const float*)resid_dev, (float*)y_dev, n, relu != 0,
+                                             (unsigned*)flag_dev);
+        });
+        L.wpk8h = nullptr;        // the scratch buffer's, not the layer's
+        L.bias8h = nullptr;
         return rc;
     });
 }
@@ -2849,8 +2907,8 @@ int apz_set_trunk_arith(apz_engine* e, int arith) {
     EngineLock guard(e->submit_lock);
     if (arith == APZ_ARITH_BF16X3 && !e->ring)
         return fail(APZ_E_UNSUPPORTED, "the bf16 x 3 trunk kernel exists for the 15x15 / 128-filter residual net only");
-    if (arith == APZ_ARITH_F16X2 && !e->ring && !e->small8)
-        return fail(APZ_E_UNSUPPORTED, "the fp16 x 2 split kernels exist for the 15x15 / 128-filter residual net and for 8x8 boards");
+    if (arith == APZ_ARITH_F16X2 && !e->ring && !e->small8 && !(e->cfg.height == 15 && e->cfg.width == 15))
+        return fail(APZ_E_UNSUPPORTED, "the fp16 x 2 split kernels exist for 15x15 boards, for the 128-filter residual net on the boards framed in them and for 8x8 boards");
     if (arith == APZ_ARITH_F16X2 && !e->ovf_host) {
         HIP_TRY(hipSetDevice(e->cfg.device));
         HIP_TRY(hipHostMalloc((void**)&e->ovf_host, (APZ_MAX_SLOTS + 1) * sizeof(unsigned), hipHostMallocMapped));

@@ -179,6 +179,39 @@ def conv3x3_wgrad_f16x2(x, dy, dymax, flag):
     return dw
 
 
+def conv3x3_fwd_f16x2_dense(x, weight, bias=None, resid=None, relu=False, flag=None):
+    """y = act(conv2d(x, weight, bias, padding=1) (+ resid)) on the fp16 matrix pipe with two-term operands
+    (csrc/conv15_split.h, apz_conv15h_fwd): dense x [n][C_in][15][15], raw weight [C_out][C_in][3][3], C_in a multiple of 64,
+    C_out a multiple of 16, inputs up to 65 504 in magnitude.  A board's bits do not depend on the batch.  flag: a device
+    int32 word (one element) that the launch sets to 1 -- never clears -- when a sum in front of the ReLU is not finite;
+    None: a word of the call's own, which nobody reads."""
+    if x.dim() != 4 or tuple(x.shape[2:]) != (15, 15):
+        raise ValueError("conv3x3_fwd_f16x2_dense: dense [n][C_in][15][15] tensors only, not %s" % (tuple(x.shape),))
+    L, hnd, stream = _ctx(x, (15, 15))
+    torch = _torch()
+    n, cin = int(x.shape[0]), int(x.shape[1])
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (cin, 3, 3):
+        raise ValueError("conv3x3_fwd_f16x2_dense: weight must be [C_out][%d][3][3], not %s" % (cin, tuple(weight.shape)))
+    cout = int(weight.shape[0])
+    if n < 1 or cin % 64 or cout % 16:
+        raise ValueError("conv3x3_fwd_f16x2_dense: C_in must be a multiple of 64, C_out a multiple of 16 and the batch not "
+                         "empty, not %d boards of %d -> %d channels" % (n, cin, cout))
+    _check(weight, "conv3x3_fwd_f16x2_dense: weight must be a contiguous float32 device tensor")
+    if bias is not None:
+        _check(bias, "conv3x3_fwd_f16x2_dense: bias must be a contiguous float32 device tensor [C_out]", None, (cout,))
+    if resid is not None:
+        _check(resid, "conv3x3_fwd_f16x2_dense: resid must be a contiguous float32 device tensor of y's shape", None,
+               (n, cout, 15, 15))
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=x.device)
+    else:
+        _check(flag, "conv3x3_fwd_f16x2_dense: flag must be an int32 device tensor of one element", torch.int32, (1,))
+    y = _empty((n, cout, 15, 15), x)
+    _ck(L, L.apz_conv15h_fwd(hnd, x.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(resid), y.data_ptr(), n, cin, cout,
+                             int(bool(relu)), flag.data_ptr(), stream))
+    return y
+
+
 def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     """conv(x, W) (flip: the data-gradient convolution with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]) + bias + resid.
     upk: the layer's transformed weights in that orientation when the caller packed them already (wino_pack_many)."""

@@ -77,6 +77,11 @@ class PolicyValueNet(object):
         15x15 trunk kernels with the board mask in the BatchNorm passes) and raises ValueError otherwise.
         8x8 boards (round 6): "f16x2" runs every convolution with a multiple of 64 input channels on the fp16 matrix pipe with
         split operands (csrc/conv8_split.h), for EVERY batch size: a board's bits do not depend on the batch there.
+        Every other 15x15 net (the simple net, the residual nets of 64 and 256 filters): "f16x2" is opt-in -- "auto" stays
+        "f32" there -- and runs every convolution with a multiple of 64 input channels on csrc/conv15_split.h, the 8x8
+        kernel's arithmetic on dense 15x15 planes, for EVERY batch size with a board's bits independent of the batch; the
+        other layers and the repeat of an overflowed forward run the fp32 generic kernel (csrc/conv3x3_mfma.h).  The
+        trainer stays on fp32 for these nets; no activation exponents, uniform_trunk has no effect.
         uniform_trunk (default False): with "f16x2" on the 15x15 / 128-filter net, batches of <= 32 boards run the small-batch
         form of the f16x2 kernel (csrc/trunk15_wino3hs.h, bit-equal to the batched kernel) instead of the exact-fp32 one, so
         a position's bits no longer depend on how many boards share its forward (apz_set_trunk_uniform; forwards that

@@ -168,6 +168,15 @@ int apz_conv3x3_pack(apz_engine *e, const void *w_dev, int cin, int cout, int tr
                      void *wpk_dev, void *stream);
 int apz_conv3x3_fwd(apz_engine *e, const void *x_dev, const void *wpk_dev, const void *bias_dev,
                     void *y_dev, int n, int cin_p, int cout_p, int relu, void *stream);
+/* The forward convolution on the fp16 matrix pipe with two-term operands (csrc/conv15_split.h; 15x15 boards, cin a multiple
+ * of 64, cout a multiple of 16, APZ_E_UNSUPPORTED otherwise): y = conv(x, w) (+ bias_dev if not NULL) (+ resid_dev if not
+ * NULL) (ReLU if relu) on dense tensors x [n][cin][15][15], y / resid [n][cout][15][15]; w_dev = the raw fp32 weights
+ * [cout][cin][3][3], split and packed into engine scratch by the evaluator's packing kernel in front of the launch.
+ * flag_dev: a device word the kernel sets to 1 -- never clears -- when a sum in front of the ReLU is not finite (an input
+ * beyond 65 504 in magnitude). */
+int apz_conv15h_fwd(apz_engine *e, const void *x_dev, const void *w_dev, const void *bias_dev,
+                    const void *resid_dev, void *y_dev, int n, int cin, int cout, int relu,
+                    void *flag_dev, void *stream);
 /* activation layouts of the training primitives: dense NCHW, or the trunk's padded rows [n][C][15][16]
  * (15x15 boards; pad column zero) in which the self-play kernels keep their activations */
 #define APZ_LAYOUT_DENSE 0
@@ -533,6 +542,11 @@ int apz_set_profiling(apz_engine *e, int on);
  * 8x8 boards (policy_value_net_mxnet_simple.py:68-92 and the 8x8 residual nets): APZ_ARITH_F16X2 runs every 3x3 convolution
  * with a multiple of 64 input channels on csrc/conv8_split.h (the same two-term split, no Winograd transform: activations up
  * to 65 504 are in range) for EVERY batch size, the first layer on conv8_kernel; same overflow word, same repeat.
+ * Every other 15x15 net (the simple net, the residual nets of 64 and 256 filters; default APZ_ARITH_F32): APZ_ARITH_F16X2
+ * runs every 3x3 convolution with a multiple of 64 input channels on csrc/conv15_split.h -- conv8_split.h's arithmetic and
+ * weights on dense 15x15 planes, for EVERY batch size, a board's bits independent of the batch; the other layers on the
+ * fp32 generic kernel (csrc/conv3x3_mfma.h), which also runs the repeat of a forward that raised the overflow word.  No
+ * activation exponents there; apz_set_trunk_uniform does nothing.
  * APZ_ARITH_BF16X3 exists for the 15x15 / 128-filter net only (APZ_E_UNSUPPORTED elsewhere). */
 #define APZ_ARITH_F32 0
 #define APZ_ARITH_BF16X3 1
