@@ -133,7 +133,7 @@ HIP_SYMBOLS = ["apz_last_error", "apz_version", "apz_device_count", "apz_create"
                "apz_set_leaf_symmetry", "apz_get_leaf_symmetry", "apz_leaf_symmetry_keys",
                "apz_bn_fwd_frame", "apz_bn_bwd_frame", "apz_frame_planes_dev", "apz_conv1x1_fwd_frame", "apz_conv1x1_bwd2_frame",
                "apz_set_legal_policy", "apz_get_legal_policy", "apz_occupancy_planes", "apz_pv_loss_legal",
-               "apz_conv15h_fwd"]
+               "apz_conv15h_fwd", "apz_conv15h_packed_size", "apz_conv15h_pack_many", "apz_conv15h_fwd_packed", "apz_conv15h_dgrad"]
 
 
 def _one_hip_runtime():
@@ -253,6 +253,10 @@ def hip():
         "apz_wino_pack": (C.c_int, [vp, vp, C.c_int, vp, vp]),
         "apz_wino_pack_many": (C.c_int, [vp, vp, C.c_int, vp, vp]),
         "apz_conv15h_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "apz_conv15h_packed_size": (C.c_int64, [C.c_int, C.c_int]),
+        "apz_conv15h_pack_many": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+        "apz_conv15h_fwd_packed": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "apz_conv15h_dgrad": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
         "apz_wino_conv": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "apz_bn_fwd": (C.c_int, [vp] * 10 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp]),
         "apz_wino_conv_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),

@@ -247,6 +247,7 @@ struct apz_engine {
     DeviceBuffer gather_entries;                   // apz_replay_gather: device copy of the entry words
     DeviceBuffer wino_scratch[2];                  // apz_wino_conv: rows16 input / output copies
     DeviceBuffer conv15h_scratch;                  // apz_conv15h_fwd: the call's scale / shift, bias8h and packed weights
+    DeviceBuffer conv15h_tab;                      // apz_conv15h_pack_many: the step's layer table
     hipStream_t scratch_stream = nullptr;          // the stream of the last entry point that may have used the scratch buffers
     bool scratch_stream_valid = false;
     TicketExchange<apz::Wino3S> w3s;         // trunk15_wino3s_kernel
@@ -1408,7 +1409,7 @@ struct StreamScope {      // run the engine's launch helpers on a caller-supplie
     StreamScope(apz_engine* e_, void* s) : e(e_), saved(e_->stream) {
         if (s != APZ_ENGINE_STREAM) e->stream = (hipStream_t)s;   // NULL is a valid handle: the null stream
         // The training entry points share per-engine scratch (the DeviceBuffers of apz_engine: bn_part, wgw_scratch,
-        // head_scratch, adam_tab, guard_part, gather_entries, wino_scratch, conv15h_scratch; and fold_ws).  Calls on ONE stream are ordered by the
+        // head_scratch, adam_tab, guard_part, gather_entries, wino_scratch, conv15h_scratch, conv15h_tab; and fold_ws).  Calls on ONE stream are ordered by the
         // stream; a caller that switches streams gets the new stream ordered behind everything queued on the previous
         // one, so two streams never work on the scratch at once.
         if (e->scratch_stream_valid && e->scratch_stream != e->stream) (void)stream_wait(e, e->stream, e->scratch_stream);
@@ -1476,7 +1477,7 @@ void apz_destroy(apz_engine* e) {
     for (void* p : dev)
         if (p) hipFree(p);
     for (DeviceBuffer* b : {&e->bn_part, &e->wgw_scratch, &e->head_scratch, &e->adam_tab, &e->guard_part, &e->gather_entries,
-                            &e->wino_scratch[0], &e->wino_scratch[1], &e->conv15h_scratch})
+                            &e->wino_scratch[0], &e->wino_scratch[1], &e->conv15h_scratch, &e->conv15h_tab})
         b->release();
     if (e->perm_pinv) hipFree(e->perm_pinv);
     if (e->occ) hipFree(e->occ);
@@ -1989,6 +1990,65 @@ int apz_conv15h_fwd(apz_engine* e, const void* x_dev, const void* w_dev, const v
     });
 }
 
+// ---- the training step of the generic 15x15 nets on conv15h_kernel (HipTrainer(trunk_arith="f16x2"), csrc/conv15_split.h)
+int64_t apz_conv15h_packed_size(int cin, int cout) {
+    if (cin < 1 || cout < 1 || !apz::Conv15H::supports(cin, cout)) return fail(APZ_E_ARG, "bad argument");
+    return (int64_t)(apz::Conv8H::pk_bytes(cin, cout) / 4);
+}
+
+namespace {
+int conv15h_packed_check(const apz_engine* e, const void* x, const void* pk, const void* bias8h, const void* y, const void* flag,
+                         int n, int cin, int cout, const char* who) {
+    if (!e || !x || !pk || !bias8h || !y || !flag || n < 1 || cin < 1 || cout < 1) return fail(APZ_E_ARG, "bad argument");
+    if (e->cfg.height != 15 || e->cfg.width != 15) return fail(APZ_E_UNSUPPORTED, std::string(who) + ": 15x15 boards only");
+    if (!apz::Conv15H::supports(cin, cout))
+        return fail(APZ_E_UNSUPPORTED, std::string(who) + ": C_in must be a multiple of 64 and C_out a multiple of 16, not " +
+                                           std::to_string(cin) + " -> " + std::to_string(cout));
+    if ((int64_t)cin * apz::Conv15H::HW * 4 > 0x7fffffffLL || (int64_t)n * (cout / 16) > 0x7fffffffLL)
+        return fail(APZ_E_UNSUPPORTED, std::string(who) + ": too many channels or items for one launch");
+    return APZ_OK;
+}
+}  // namespace
+
+int apz_conv15h_fwd_packed(apz_engine* e, const void* x_dev, const void* pk_dev, const void* bias8h_dev, const void* resid_dev,
+                           void* y_dev, int n, int cin, int cout, void* flag_dev, void* stream) {
+    if (int rc = conv15h_packed_check(e, x_dev, pk_dev, bias8h_dev, y_dev, flag_dev, n, cin, cout, "conv15h_fwd_packed")) return rc;
+    return train_call(e, stream, [&]() -> int {
+        ConvLayer L;
+        L.cin = cin;
+        L.cout = cout;
+        L.bias8h = (float*)const_cast<void*>(bias8h_dev);
+        L.wpk8h = const_cast<void*>(pk_dev);
+        const int rc = with_flag(resid_dev != nullptr, [&](auto RESID) {
+            return launch_conv15h_t<RESID()>(e, L, (const float*)x_dev, (const float*)resid_dev, (float*)y_dev, n, 0,
+                                             (unsigned*)flag_dev);
+        });
+        L.wpk8h = nullptr;        // the caller's, not the layer's
+        L.bias8h = nullptr;
+        return rc;
+    });
+}
+
+int apz_conv15h_dgrad(apz_engine* e, const void* dy_dev, const void* pk_dev, const void* bias8h_dev, const void* add_dev,
+                      void* dx_dev, int n, int c_dy, int c_dx, const void* dymax_dev, int dymax_count, void* flag_dev,
+                      void* stream) {
+    if (!dymax_dev || dymax_count < 1) return fail(APZ_E_ARG, "bad argument");
+    if (int rc = conv15h_packed_check(e, dy_dev, pk_dev, bias8h_dev, dx_dev, flag_dev, n, c_dy, c_dx, "conv15h_dgrad")) return rc;
+    using T = apz::Conv15H;
+    return train_call(e, stream, [&]() -> int {
+        const int grid = (int)T::grid_for((long)n * (c_dx / 16), e->num_cu);
+        return with_flag(add_dev != nullptr, [&](auto RESID) -> int {
+            const auto kern = apz::conv15h_kernel<RESID(), apz::CONV15H_DGRAD, const float*, int>;
+            if (int rc = need_lds(e, (const void*)kern, T::LDS_BYTES)) return rc;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), T::LDS_BYTES, e->stream, (const float*)dy_dev, pk_dev,
+                               (const float*)bias8h_dev, (const float*)add_dev, (float*)dx_dev, n, c_dy, c_dx, 0, (unsigned*)flag_dev,
+                               (const float*)dymax_dev, dymax_count);
+            HIP_TRY(hipGetLastError());
+            return APZ_OK;
+        });
+    });
+}
+
 int64_t apz_wino_packed_size(void) { return (int64_t)apz::WinoPack::UPK_FLOATS; }
 
 int apz_wino_pack(apz_engine* e, const void* w_dev, int transpose_flip, void* upk_dev, void* stream) {
@@ -2246,7 +2306,8 @@ int bn_bwd_launch(apz_engine* e, const void* dy_dev, const void* x_dev, const vo
             hipLaunchKernelGGL(apz::bn_bwd_apply_kernel, dim3(C, splits), dim3(256), 0, e->stream, (const float*)dy_dev,
                                (const float*)x_dev, (const float*)out_dev, (const float*)gamma_dev, (const float*)mean_dev,
                                (const float*)invstd_dev, part, splits, (float*)dx_dev, (float*)dres_dev, (float*)dgamma_dev,
-                               (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu, (double)n * H * W);
+                               (float*)dbeta_dev, (float*)dxsum_dev, dxsum_ld, n, C, ps, rs, H, W, relu, (double)n * H * W,
+                               (float*)dxmax_dev);
         }
         return APZ_OK;
     });
@@ -2292,7 +2353,10 @@ int apz_bn_bwd_max(apz_engine* e, const void* dy_dev, const void* x_dev, const v
     if (!e || !dy_dev || !x_dev || !mean_dev || !invstd_dev || !dx_dev || n < 1 || C < 1 || C > 256 ||
         (relu && !out_dev && !mask_dev) || (dxsum_dev && dxsum_ld < C) || (mask_dev && layout != APZ_LAYOUT_ROWS16))
         return fail(APZ_E_ARG, "bad argument");
-    if (dxmax_dev && layout != APZ_LAYOUT_ROWS16) return fail(APZ_E_UNSUPPORTED, "bn_bwd_max: padded-row layout only");
+    // the maxima feed the f16x2 data gradients, which exist on 15x15 boards only: padded rows (trunk15_wino3h16.h) and, dense,
+    // the generic nets (conv15_split.h); a dense 8x8 tensor has no consumer for them and keeps its refusal
+    if (dxmax_dev && layout != APZ_LAYOUT_ROWS16 && (e->cfg.height != 15 || e->cfg.width != 15))
+        return fail(APZ_E_UNSUPPORTED, "bn_bwd_max: padded-row layout only");
     int ps, rs;
     if (int rc = bn_geometry(e, layout, &ps, &rs)) return rc;
     return bn_bwd_launch(e, dy_dev, x_dev, out_dev, mask_dev, gamma_dev, mean_dev, invstd_dev, dx_dev, dres_dev, dgamma_dev,
@@ -2397,6 +2461,31 @@ int upload_table(apz_engine* e, DeviceBuffer& buf, const void* table_host, int c
 }
 }  // namespace
 }  // extern "C++"
+
+// (csrc/conv15_split.h, pack_conv15h_many_kernel: the table goes the way of the optimiser's)
+int apz_conv15h_pack_many(apz_engine* e, const void* table_host, int count, void* flag_dev, void* stream) {
+    if (!e || !table_host || count < 1 || count > 4096) return fail(APZ_E_ARG, "bad argument");
+    static_assert(sizeof(apz::Conv15HPackEntry) == 56, "apz_conv15h_pack_entry layout");
+    const apz::Conv15HPackEntry* host = (const apz::Conv15HPackEntry*)table_host;
+    int maxc = 0;
+    for (int i = 0; i < count; i++) {
+        const apz::Conv15HPackEntry& E = host[i];
+        if (!E.w || !E.pk[0] || !E.pk[1] || !E.bias8h[0] || !E.bias8h[1] || E.cin < 1 || E.cout < 1)
+            return fail(APZ_E_ARG, "bad argument");
+        // both orientations run on the kernel: C_in -> C_out and C_out -> C_in
+        if (E.cin % 64 || E.cout % 64 || E.cin > 65536 || E.cout > 65536)
+            return fail(APZ_E_UNSUPPORTED, "conv15h_pack_many: C_in and C_out must be multiples of 64, not " + std::to_string(E.cin) +
+                                               " -> " + std::to_string(E.cout));
+        maxc = std::max(maxc, std::max(E.cin, E.cout));
+    }
+    return train_call(e, stream, [&]() -> int {
+        const apz::Conv15HPackEntry* tab;
+        if (int rc = upload_table(e, e->conv15h_tab, table_host, count, &tab)) return rc;
+        hipLaunchKernelGGL(apz::pack_conv15h_many_kernel, dim3(maxc, 2 * count), dim3(256), 0, e->stream, tab, (unsigned*)flag_dev);
+        HIP_TRY(hipGetLastError());
+        return APZ_OK;
+    });
+}
 
 int apz_adam_step(apz_engine* e, const void* table_host, int ntensors, float lr_t, float b1, float b2, float eps,
                   float rescale, void* stream) {

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv8_split.h"
+#include "trunk15_wino3h16.h"
 
 namespace apz {
 
@@ -58,12 +59,27 @@ __global__ void conv15h_plain_fold_kernel(const float* __restrict__ bias, double
     }
 }
 
+// The training step's data-gradient form (HipTrainer(trunk_arith="f16x2") on the generic 15x15 nets; apz_conv15h_dgrad): the
+// same convolution on the flipped, transposed weights (pack_conv15h_many_kernel's second orientation: bias zero), RESID adds
+// the skip gradient.  Its input is the gradient of a mean loss, far below 2^-3, where the lo term of the split is subnormal
+// and carries an ABSOLUTE error of up to 2^-25.  So the launch scales its input by 2^a, chosen on the
+// device exactly as trunk15_wino3h16_kernel<..., WINO3H16_DGRAD> does: `dymax` holds `dymax_n` partial maxima of |input|
+// (bn_bwd's dxmax, one per batch split and channel), every workgroup folds them (max: exact in any order; NaN entries are
+// ignored), wino3h16_dgrad_exponent puts the maximum into [2^7, 2^8), the staged values are multiplied by 2^a in front of the
+// split and 2^-a goes into the 1 / S of the bias FMA (both exact; 2^-a / S may be an fp32 subnormal: this library is built
+// with fp32 denormals on).  A +inf maximum raises flag[0]; a zero maximum gives a = 0 and dx = exactly `resid`, or +0.
+enum { CONV15H_PLAIN = 0, CONV15H_DGRAD = 1 };
+
 // in: dense [n][cin][225] floats; out / resid: dense [n][cout][225]; pk: Conv8H layout; bias8h: [cout bias][cout 1/S].
-template <bool RESID>
+// FORM CONV15H_PLAIN (the evaluator's kernel, and with relu = 0 the training step's forward: apz_conv15h_fwd_packed) takes no
+// further argument; CONV15H_DGRAD takes (const float* dymax, int dymax_n) behind `flag` and relu = 0: in = dy [n][cin = C of
+// dy][225], out = dx, resid = the skip gradient.
+template <bool RESID, int FORM = CONV15H_PLAIN, class... AUX>
 __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict__ in, const void* __restrict__ pk,
                                                          const float* __restrict__ bias8h, const float* __restrict__ resid,
                                                          float* __restrict__ out, int n, int cin, int cout, int relu,
-                                                         unsigned* __restrict__ flag) {
+                                                         unsigned* __restrict__ flag, AUX... aux) {
+    static_assert(sizeof...(AUX) == (FORM == CONV15H_DGRAD ? 2 : 0), "CONV15H_DGRAD: (dymax, dymax_n); CONV15H_PLAIN: nothing");
     using T = Conv15H;
     extern __shared__ __attribute__((aligned(16))) char lds15[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -75,6 +91,27 @@ __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict
     auto zero_tile = [&]() {       // border cells are never written with anything else in the main loop
         for (int i = lane * 16; i < T::WAVE_BYTES; i += 1024) *reinterpret_cast<f32x4*>(tile + i) = f32x4{0.f, 0.f, 0.f, 0.f};
     };
+    // DGRAD: the input scale 2^a and 2^-a from the partial maxima (the four wave maxima pass through the first words of the
+    // tile memory, which is zeroed only behind the second barrier)
+    float xsc = 1.f, xisc = 1.f;
+    bool max_inf = false;                           // DGRAD: a partial maximum is +inf -- no scale fits, the result is void
+    if constexpr (FORM == CONV15H_DGRAD) {
+        const float* dymax;
+        int dymax_n;
+        [&](const float* p, int c) { dymax = p, dymax_n = c; }(aux...);
+        float m = 0.f;
+        for (int i = tid; i < dymax_n; i += 256) m = fmaxf(m, fabsf(dymax[i]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        float* wm = reinterpret_cast<float*>(lds15);
+        if (lane == 0) wm[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+        __syncthreads();
+        const int a = __builtin_amdgcn_readfirstlane(wino3h16_dgrad_exponent(m));
+        max_inf = !(m <= 3.4028234664e38f);
+        f16x2_pow2_pair(a, xsc, xisc);
+    }
     zero_tile();
     wave_lds_fence();
 
@@ -93,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict
     const int brd = j * T::CELL + (kg & 1) * 16;
     const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(pk), 0, (unsigned)Conv8H::pk_bytes(cin, cout), 0x00020000);
     const unsigned board_bytes = (unsigned)cin * T::HW * 4u;
-    unsigned nonfinite = 0;
+    unsigned nonfinite = max_inf ? 1u : 0u;
 
     for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
         const int b = item / ncot, cot = item - b * ncot;
@@ -118,7 +155,10 @@ __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict
 #pragma unroll
                 for (int m = 0; m < 8; m++) {
                     unsigned hu, lu;
-                    f16x2_split(pre[q][2 * m], pre[q][2 * m + 1], hu, lu);
+                    if constexpr (FORM == CONV15H_DGRAD)
+                        f16x2_split(pre[q][2 * m] * xsc, pre[q][2 * m + 1] * xsc, hu, lu);
+                    else
+                        f16x2_split(pre[q][2 * m], pre[q][2 * m + 1], hu, lu);
                     h[m >> 2][m & 3] = hu;
                     l[m >> 2][m & 3] = lu;
                 }
@@ -194,7 +234,10 @@ __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict
             float sum = rp[0] + rp[T::WAVE_BYTES / 4];
             sum = sum + rp[2 * (T::WAVE_BYTES / 4)];
             sum = sum + rp[3 * (T::WAVE_BYTES / 4)];
-            sum = __builtin_fmaf(sum, bias8h[cout + cot * 16 + co], bias8h[cot * 16 + co]);
+            if constexpr (FORM == CONV15H_DGRAD)
+                sum = __builtin_fmaf(sum, bias8h[cout + cot * 16 + co] * xisc, bias8h[cot * 16 + co]);
+            else
+                sum = __builtin_fmaf(sum, bias8h[cout + cot * 16 + co], bias8h[cot * 16 + co]);
             const size_t o = ((size_t)b * cout + cot * 16) * T::HW + i;
             if (RESID) sum = sum + resid[o];
             nonfinite |= ((sum - sum) != 0.f) ? 1u : 0u;        // an overflow of the fp16 split shows as +-inf / NaN here
@@ -206,6 +249,54 @@ __global__ __launch_bounds__(256, 2) void conv15h_kernel(const float* __restrict
         wave_lds_fence();
     }
     if (nonfinite && flag) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
+}
+
+// The training step's weights, one launch per step: `count` layers of any eligible shape, each in both orientations.
+//   orientation 0 (forward)        out channel = co, in channel = ci, tap = ky 3 + kx, bias = the layer's (null: 0) -- bit for
+//                                  bit what conv15h_plain_fold_kernel + pack_conv8h_kernel leave
+//   orientation 1 (data gradient)  W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]: out channel = ci, in channel = co, bias 0
+// S = f16x2_scale_for(max |w|) over the ORIENTATION's own output channel.  Grid (max channels of any layer, 2 count), block
+// 256: workgroup (oc, 2 l + o) packs output channel oc of orientation o of layer l, or leaves at once.  flag (may be null)
+// is zeroed: the overflow word of the step these weights serve.
+struct Conv15HPackEntry {
+    const float* w;             // [cout][cin][3][3]
+    const float* bias;          // [cout], or null
+    unsigned short* pk[2];      // Conv8H layout of (cin -> cout), of (cout -> cin)
+    float* bias8h[2];           // [2 cout], [2 cin]
+    int cin, cout;
+};
+__global__ __launch_bounds__(256) void pack_conv15h_many_kernel(const Conv15HPackEntry* __restrict__ tab,
+                                                                unsigned* __restrict__ flag) {
+    const Conv15HPackEntry E = tab[blockIdx.y >> 1];
+    const int flip = blockIdx.y & 1, oc = blockIdx.x, tid = threadIdx.x;
+    if (flag && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *flag = 0u;
+    const int noc = flip ? E.cin : E.cout, nic = flip ? E.cout : E.cin;
+    if (oc >= noc) return;
+    auto at = [&](int ic, int tap) -> double {
+        return flip ? (double)E.w[((size_t)ic * E.cin + oc) * 9 + (8 - tap)] : (double)E.w[((size_t)oc * E.cin + ic) * 9 + tap];
+    };
+    double m = 0.0;
+    for (int ic = tid; ic < nic; ic += 256)
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++) m = fmax(m, fabs(at(ic, tap)));
+    __shared__ double red[256];
+    red[tid] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const float S = f16x2_scale_for(red[0]);
+    float* b8 = E.bias8h[flip];
+    if (tid == 0) {
+        b8[oc] = (!flip && E.bias) ? E.bias[oc] : 0.f;
+        b8[noc + oc] = 1.f / S;
+    }
+    unsigned short* pk = E.pk[flip];
+    for (int ic = tid; ic < nic; ic += 256)
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++)
+            f16x2_split(at(ic, tap) * (double)S, pk[Conv8H::pk_index(oc, ic, tap, 0, nic)], pk[Conv8H::pk_index(oc, ic, tap, 1, nic)]);
 }
 
 }  // namespace apz

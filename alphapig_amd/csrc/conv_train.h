@@ -148,7 +148,8 @@ __global__ void rows16_to_dense_kernel(const float* __restrict__ x, float* __res
 //                        workgroup (c, 0) writes dbeta = s1, dgamma = s2; dxsum (may be NULL): row `split` of
 //                        [splits][ld] floats gets the sum of the dx this workgroup wrote -- the bias gradient of the
 //                        convolution in front of the BatchNorm is the column sum of that matrix (colsum_kernel,
-//                        heads_train.h; the trainer adds all layers' rows in ONE launch)
+//                        heads_train.h; the trainer adds all layers' rows in ONE launch); dxmax (may be NULL): row `split` of
+//                        [splits][C] floats gets max |dx| of this workgroup
 struct BnFinal {            // what workgroup (c, 0) of bn_apply writes (run_* may be NULL)
     float* mean;
     float* invstd;
@@ -285,7 +286,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const double* __restrict__ part, int psplits, float* __restrict__ dx,
                                                            float* __restrict__ dres, float* __restrict__ dgamma,
                                                            float* __restrict__ dbeta, float* __restrict__ dxsum, int dxsum_ld,
-                                                           int n, int C, int PS, int RS, int H, int W, int relu, double M) {
+                                                           int n, int C, int PS, int RS, int H, int W, int relu, double M,
+                                                           float* __restrict__ dxmax) {
     __shared__ double sh[4];
     const int c = blockIdx.x, cells = H * RS;
     double s1, s2;
@@ -296,6 +298,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
     const float k0 = (float)(s1 / M), k1 = (float)(s2 / M), m = mean[c], is = invstd[c], g = gamma ? gamma[c] : 1.f;
     double ds = 0.0;
+    float dm = 0.f;
     for (int b = blockIdx.y; b < n; b += gridDim.y) {
         const size_t base = ((size_t)b * C + c) * PS;
         for (int q = threadIdx.x; q < cells; q += 256) {
@@ -310,11 +313,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             dx[base + q] = gx;
             if (dres) dres[base + q] = gr;
             ds += gx;
+            if (dxmax) dm = fmaxf(dm, fabsf(gx));
         }
     }
     if (dxsum) {
         ds = block_sum_256(ds, sh);
         if (threadIdx.x == 0) dxsum[(size_t)blockIdx.y * dxsum_ld + c] = (float)ds;
+    }
+    if (dxmax) {   // [split][C]: max |dx| of this workgroup (the input scale of conv15h_dgrad_kernel, as bn_bwd_apply_rows_kernel's)
+        dm = block_max_256(dm, reinterpret_cast<float*>(sh));
+        if (threadIdx.x == 0) dxmax[(size_t)blockIdx.y * C + c] = dm;
     }
 }
 

@@ -212,6 +212,111 @@ def conv3x3_fwd_f16x2_dense(x, weight, bias=None, resid=None, relu=False, flag=N
     return y
 
 
+_CONV15H_ENTRY = [("w", "u8"), ("bias", "u8"), ("pk0", "u8"), ("pk1", "u8"), ("b0", "u8"), ("b1", "u8"), ("cin", "i4"),
+                  ("cout", "i4")]     # apz_conv15h_pack_entry, 56 bytes
+
+
+def _flag_word(flag, who, like):
+    """The int32 overflow word of an f16x2 launch: the caller's (one element; a float32 view of a word buffer passes as
+    well), or a word of the call's own, which nobody reads"""
+    torch = _torch()
+    if flag is None:
+        return torch.zeros((1,), dtype=torch.int32, device=like.device)
+    if not (flag.is_cuda and flag.is_contiguous() and flag.numel() == 1 and flag.dtype in (torch.int32, torch.float32)):
+        raise ValueError("%s: flag must be a 32-bit device tensor of one element" % who)
+    return flag
+
+
+def conv15h_pack_many(layers, out=None, flag=None):
+    """The training step's weights of the generic 15x15 nets for the f16x2 kernel (csrc/conv15_split.h), one launch for all
+    of them.  layers: [(weight [C_out][C_in][3][3], bias [C_out] or None)] of contiguous float32 device tensors, C_in and
+    C_out multiples of 64 -> [((pk, bias8h) of the forward, (pk, bias8h) of the data gradient)] per layer: pk float32
+    [9 C_in C_out] words (two fp16 terms of w S), bias8h [2][channels] = (bias -- zero for the data gradient --, 1 / S).  The
+    forward pair holds bit for bit what conv3x3_fwd_f16x2_dense packs per call.  out: such a list to fill again (the tensors
+    of `layers` must be the ones it was made for); flag: a 32-bit device word the launch zeroes (the overflow word of the step
+    that follows)."""
+    import numpy as np
+    layers = list(layers)
+    if not layers:
+        raise ValueError("conv15h_pack_many: no layers")
+    L, hnd, stream = _ctx(layers[0][0], (15, 15))
+    tab = np.zeros(len(layers), dtype=_CONV15H_ENTRY)
+    made = []
+    for i, (w, b) in enumerate(layers):
+        _check(w, "conv15h_pack_many: weight %d must be a contiguous float32 device tensor [C_out][C_in][3][3]" % i)
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError("conv15h_pack_many: weight %d must be [C_out][C_in][3][3], not %s" % (i, tuple(w.shape)))
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        if cin % 64 or cout % 64:
+            raise ValueError("conv15h_pack_many: C_in and C_out must be multiples of 64, not %d -> %d (layer %d)" % (cin, cout, i))
+        if b is not None:
+            _check(b, "conv15h_pack_many: bias %d must be a contiguous float32 device tensor [C_out]" % i, None, (cout,))
+        if out is None:
+            words = int(L.apz_conv15h_packed_size(cin, cout))
+            pair = ((_empty((words,), w), _empty((2, cout), w)), (_empty((words,), w), _empty((2, cin), w)))
+        else:
+            pair = out[i]
+            if tuple(pair[0][1].shape) != (2, cout) or tuple(pair[1][1].shape) != (2, cin):
+                raise ValueError("conv15h_pack_many: out[%d] was made for another layer" % i)
+        made.append(pair)
+        tab[i] = (w.data_ptr(), 0 if b is None else b.data_ptr(), pair[0][0].data_ptr(), pair[1][0].data_ptr(),
+                  pair[0][1].data_ptr(), pair[1][1].data_ptr(), cin, cout)
+    if flag is not None:
+        flag = _flag_word(flag, "conv15h_pack_many", layers[0][0])
+    _ck(L, L.apz_conv15h_pack_many(hnd, tab.ctypes.data_as(C.c_void_p), len(tab), _ptr(flag), stream))
+    return made
+
+
+def _conv15h_packed(who, x, packed, resid, what):
+    """The shared argument checks of the two packed operators -> (n, C of x, C of the result)"""
+    if x.dim() != 4 or tuple(x.shape[2:]) != (15, 15):
+        raise ValueError("%s: dense [n][C][15][15] tensors only, not %s" % (who, tuple(x.shape)))
+    _check(x, "%s: contiguous float32 device tensors" % who)
+    pk, b8 = packed
+    n, cin = int(x.shape[0]), int(x.shape[1])
+    _check(pk, "%s: packed weights of conv15h_pack_many" % who)
+    _check(b8, "%s: bias8h of conv15h_pack_many" % who)
+    if b8.dim() != 2 or int(b8.shape[0]) != 2:
+        raise ValueError("%s: bias8h must be [2][C]" % who)
+    cout = int(b8.shape[1])
+    if n < 1 or cin % 64 or cout % 16 or int(pk.numel()) != 9 * cin * cout:
+        raise ValueError("%s: %d boards of %d channels do not fit packed weights of %d words for %d output channels" %
+                         (who, n, cin, int(pk.numel()), cout))
+    if resid is not None:
+        _check(resid, "%s: %s must be a contiguous float32 device tensor of the result's shape" % (who, what), None,
+               (n, cout, 15, 15))
+    return n, cin, cout
+
+
+def conv3x3_fwd_f16x2_dense_packed(x, packed, resid=None, flag=None):
+    """y = conv2d(x, weight, bias, padding=1) (+ resid) as conv3x3_fwd_f16x2_dense(relu=False) computes it, bit for bit, on
+    weights packed once per step: packed = a layer's forward pair of conv15h_pack_many.  flag as there."""
+    n, cin, cout = _conv15h_packed("conv3x3_fwd_f16x2_dense_packed", x, packed, resid, "resid")
+    L, hnd, stream = _ctx(x, (15, 15))
+    flag = _flag_word(flag, "conv3x3_fwd_f16x2_dense_packed", x)
+    y = _empty((n, cout, 15, 15), x)
+    _ck(L, L.apz_conv15h_fwd_packed(hnd, x.data_ptr(), packed[0].data_ptr(), packed[1].data_ptr(), _ptr(resid), y.data_ptr(), n,
+                                    cin, cout, flag.data_ptr(), stream))
+    return y
+
+
+def conv3x3_dgrad_f16x2_dense(dy, packed, dymax, flag=None, add=None):
+    """dx = conv2d_input(dy, weight) (+ add) on the f16x2 kernel, dense tensors: packed = a layer's data-gradient pair of
+    conv15h_pack_many; dymax = bn_bwd's dxmax for this dy (partial maxima of |dy|: the launch's power-of-two input scale; NaN
+    entries are ignored, a +inf entry sets `flag`, an all-zero dymax gives exactly `add`, or +0)."""
+    who = "conv3x3_dgrad_f16x2_dense"
+    n, c_dy, c_dx = _conv15h_packed(who, dy, packed, add, "add")
+    _check(dymax, "%s: dymax must be a contiguous float32 device tensor" % who)
+    if int(dymax.numel()) < 1:
+        raise ValueError("%s: dymax is empty" % who)
+    L, hnd, stream = _ctx(dy, (15, 15))
+    flag = _flag_word(flag, who, dy)
+    dx = _empty((n, c_dx, 15, 15), dy)
+    _ck(L, L.apz_conv15h_dgrad(hnd, dy.data_ptr(), packed[0].data_ptr(), packed[1].data_ptr(), _ptr(add), dx.data_ptr(), n, c_dy,
+                               c_dx, dymax.data_ptr(), int(dymax.numel()), flag.data_ptr(), stream))
+    return dx
+
+
 def _conv3x3_run(x, weight, bias, layout, flip, resid, relu, upk=None):
     """conv(x, W) (flip: the data-gradient convolution with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx]) + bias + resid.
     upk: the layer's transformed weights in that orientation when the caller packed them already (wino_pack_many)."""
@@ -349,8 +454,8 @@ def bn_bwd(dy, x, y, gamma, mean, invstd, relu=True, want_dres=False, layout=DEN
     want_mask result) carries the ReLU decisions.
     dxsum: a [bn_bwd_splits(x, layout)][C] view (row stride >= C) of a float32 matrix that receives the per-split column
     sums of dx -- colsum() of it is the bias gradient of the convolution in front (bias_parts() hands such views out).
-    dxmax (padded rows): a contiguous float32 [bn_bwd_splits(x, layout)][C] tensor that receives max |dx| per split and
-    channel (conv3x3_dgrad_f16x2's dymax).
+    dxmax (padded rows, or dense 15x15 tensors): a contiguous float32 [bn_bwd_splits(x, layout)][C] tensor that receives max |dx| per split and
+    channel (the dymax of conv3x3_dgrad_f16x2 / conv3x3_dgrad_f16x2_dense); without it: the same dx, sums and bits.
     side (padded rows; None: the 15x15 board): the framed board's side, as in bn_fwd -- off-board dy and x may hold
     anything; off-board dx and dres are exactly +0."""
     L, hnd, stream = _ctx(x, _board(x, layout))

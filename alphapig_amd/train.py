@@ -105,6 +105,41 @@ def check_trainable_board(params, framed=False, net_kind="resnet", trunk_arith="
                          "device-chosen scales see off-board cells (%dx%d board)" % (trunk_arith, side, side))
 
 
+def f16x2_route(params, net_kind="resnet", n_blocks=10):
+    """Which form trunk_arith="f16x2" takes on the net of `params` -> "rows16" (the 15x15 residual trunk of 128 filters: the
+    padded-row Winograd kernels, trunk15_wino3h16.h) or "dense" (every other 15x15 net: conv15h_kernel, conv15_split.h, for
+    its 3x3 layers whose channel counts are multiples of 64).  ValueError for everything else: 8x8 and framed boards, and a
+    15x15 net without such a layer (check_trainable_board has refused the framed boards with its own words by then).  Needs
+    no GPU."""
+    hw = int(np.shape(params["fc_3_1_1_bias"])[0])
+    side = int(round(hw ** 0.5))
+    if side * side != hw or side != 15:
+        raise ValueError("trunk_arith='f16x2' needs the 15x15 residual trunk of 128 filters (net_kind %r, %dx%d)" %
+                         (net_kind, side, side))
+    if net_kind == "resnet" and n_blocks > 0 and tuple(np.shape(params["convA1_weight"])) == (128, 128, 3, 3):
+        return "rows16"
+    if not f16x2_dense_layers(params, net_kind, n_blocks):
+        raise ValueError("trunk_arith='f16x2' needs a 3x3 layer whose C_in and C_out are multiples of 64 (net_kind %r, %d blocks)" %
+                         (net_kind, n_blocks))
+    return "dense"
+
+
+def f16x2_dense_layers(params, net_kind, n_blocks):
+    """The parameter prefixes of the 3x3 layers that the dense f16x2 route runs on conv15h_kernel: C_in and C_out multiples
+    of 64 (the kernel's contraction splits over four waves of 16-channel chunks, in both orientations).  The first layer
+    (C_in = 9) never is one."""
+    if net_kind == "resnet":
+        names = ["conv%s%d" % (ab, i) for i in range(1, n_blocks + 1) for ab in "AB"]
+    else:
+        names = list(SIMPLE_CONVS)
+    out = []
+    for k in names:
+        shape = tuple(np.shape(params[k + "_weight"]))
+        if len(shape) == 4 and shape[2:] == (3, 3) and shape[0] % 64 == 0 and shape[1] % 64 == 0:
+            out.append(k)
+    return out
+
+
 class HipTrainer(object):
     def __init__(self, params, net_kind="resnet", n_blocks=10, batch_size=512, wd=1e-4, device_index=0, dropout=0.5,
                  seed=0, height=None, width=None, dropout_step0=0, trunk_arith="f32", framed=False, step_guard=False,
@@ -118,9 +153,14 @@ class HipTrainer(object):
         BatchNorm statistics in its epilogue, the data gradient with a power-of-two input scale chosen on the device),
         at every batch size -- the weight gradient, the stem and the heads stay as they are.  A step in which an f16x2
         launch leaves the fp16 range is taken again on the exact kernels (trunk_overflows counts them) and ends
-        bit-identical to the "f32" trainer's step.  Only the 15x15, 128-filter residual trunk has the f16x2 form:
-        other nets raise ValueError.  (profiles/r07_train_f16x2.md: 0.86 of the "f32" step time at batch 512, but
-        only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)
+        bit-identical to the "f32" trainer's step.  (profiles/r07_train_f16x2.md: 0.86 of the "f32" step time at batch
+        512, but only 0.98 at the reference's batch of 128, where the kernel has 128 work items for 256 CUs.)
+        Every other 15x15 net (rows16 False: the simple net, the residual nets of other filter counts) takes "f16x2" on
+        dense tensors (f16x2_route -> "dense"): every 3x3 layer whose C_in and C_out are multiples of 64 runs its forward and
+        its data gradient on conv15h_kernel (csrc/conv15_split.h; the data gradient with the same device-chosen input
+        scale, from the dense bn_bwd's dxmax), weights packed by one launch per step; the first layer (C_in = 9), the
+        weight gradient, BatchNorm, heads, loss and Adam stay on their exact kernels; overflow is handled the same way
+        (profiles/r32_generic_train_f16x2.md).  8x8 and framed boards have no f16x2 form: ValueError.
         framed: opt in to the training step on the framed boards (6x6, 7x7, 9x9, 11x11 .. 14x14; check_trainable_board):
         the residual net of 128 filters on the 15x15 trunk kernels, the board mask in the BatchNorm passes.  Without it
         those boards raise ValueError as they always did; 15x15 and 8x8 train as they always did whatever it says.
@@ -156,6 +196,8 @@ class HipTrainer(object):
         if "fc_3_1_1_bias" in params:
             # before anything touches the GPU: today's failure would come from the first step
             check_trainable_board(params, framed, net_kind, trunk_arith)
+            if trunk_arith == "f16x2":
+                f16x2_route(params, net_kind, n_blocks)
         import torch
         from . import _native, hipconv
         if not torch.cuda.is_available():
@@ -213,10 +255,13 @@ class HipTrainer(object):
         self.trunk_arith = trunk_arith
         self.trunk_overflows = 0       # f16x2: steps (and loss_and_grads calls) repeated on the exact kernels
         self._fast = False             # the pass being queued runs its trunk on the f16x2 kernel
-        if trunk_arith == "f16x2":
-            if not self.rows16:
-                raise ValueError("trunk_arith='f16x2' needs the 15x15 residual trunk of 128 filters (net_kind %r, %dx%d)" %
-                                 (net_kind, self.side, self.side))
+        # f16x2 on the dense route: the eligible layers by parameter prefix -> their packed (forward, data gradient) pairs of
+        # the pass being queued (hipconv.conv15h_pack_many: one launch at the start of a fast pass)
+        self._gen_names, self._gen, self._gen_out = [], {}, None
+        if trunk_arith == "f16x2" and not self.rows16:
+            f16x2_route(self.p, net_kind, n_blocks)      # (raises for 8x8 and for a net without an eligible layer)
+            self._gen_names = f16x2_dense_layers(self.p, net_kind, n_blocks)
+        if trunk_arith == "f16x2" and self.rows16:
             # the trunk biases back to back as well (wino3h_pack_many packs them with the weights), the moving statistics in
             # one buffer (one copy snapshots them at the start of a step: a repeated step must not move them twice), and
             # a word after the step's three losses: the overflow word, read with the losses in ONE device -> host copy
@@ -290,6 +335,8 @@ class HipTrainer(object):
             x = o.frame_planes(x)
         if w.shape[2] == 1:
             y, blay = o.conv1x1_fwd(x, w, p[name + "_bias"], layout, side=self.frame_side), o.DENSE
+        elif name in self._gen:          # (a fast pass on the dense route)
+            y, blay = o.conv3x3_fwd_f16x2_dense_packed(x, self._gen[name][0], flag=self._flag), layout
         else:
             y, blay = o.conv3x3_fwd(x, w, p[name + "_bias"], layout), layout
         side = self.frame_side if frame else None
@@ -299,20 +346,25 @@ class HipTrainer(object):
                                    1.0 - BN_MOMENTUM, BN_EPS, side=side)
         return a, ConvAct(name, x, y, a, mean, invstd, layout, blay, side)
 
-    def _act_bwd(self, da, rec):
+    def _act_bwd(self, da, rec, dymax=None):
         """conv_act's BatchNorm and relu backwards -> dy in the layout its convolution wrote (framed stem: off-board cells
-        zero, so the dense 15x15 gradients behind it are the S x S board's)"""
+        zero, so the dense 15x15 gradients behind it are the S x S board's); dymax: receives bn_bwd's dxmax"""
         o = self.ops
         dy, _, _, self.grad[rec.name + "_beta"] = o.bn_bwd(da, rec.y, rec.a, None, rec.mean, rec.invstd, True, False, rec.blay,
-                                                         side=rec.side)
+                                                         dxmax=dymax, side=rec.side)
         return o.from_rows16(dy) if rec.side else dy
 
     def _conv_act_bwd(self, da, rec, need_dx):
         """conv_act backwards, 3x3 (the two 1x1 heads share their input: _backward runs them as a pair)"""
         o, g = self.ops, self.grad
-        dy = self._act_bwd(da, rec)
+        # a fast pass on the dense route: the BatchNorm leaves max |dy| for the f16x2 data gradient right behind it
+        fast = need_dx and rec.name in self._gen
+        dymax = o._empty((o.bn_bwd_splits(rec.y, rec.blay), int(rec.y.shape[1])), da) if fast else None
+        dy = self._act_bwd(da, rec, dymax)
         g[rec.name + "_weight"] = o.conv3x3_wgrad(rec.x, dy, rec.layout)
         g[rec.name + "_bias"] = o.bias_grad(dy, rec.layout)
+        if fast:
+            return o.conv3x3_dgrad_f16x2_dense(dy, self._gen[rec.name][1], dymax, self._flag)
         return o.conv3x3_dgrad(dy, self.p[rec.name + "_weight"], rec.layout) if need_dx else None
 
     def _trunk_conv(self, j):
@@ -324,8 +376,10 @@ class HipTrainer(object):
         on the f16x2 kernel in a fast pass, else on the Winograd kernel, whose epilogue leaves the BatchNorm's sums (no
         statistics pass; apz_wino_conv_stats is one launch: up to 16384 boards); other nets plain."""
         o = self.ops
-        if self._fast:
+        if self._fast and self.rows16:
             return o.conv3x3_fwd_stats_f16x2(x, self._u16[0][j, 0], self._u16[1][j, 0], self._flag)
+        if self._trunk_conv(j) in self._gen:       # (a fast pass on the dense route)
+            return o.conv3x3_fwd_f16x2_dense_packed(x, self._gen[self._trunk_conv(j)][0], flag=self._flag), None
         w, b = self.p[self._trunk_conv(j) + "_weight"], self.p[self._trunk_conv(j) + "_bias"]
         if not self.rows16:
             return o.conv3x3_fwd(x, w, b, o.DENSE), None
@@ -337,8 +391,10 @@ class HipTrainer(object):
         """The data gradient of trunk convolution j (+ skip: the skip connection's gradient of the same tensor) on the
         kernel of the pass; dymax: bn_bwd's dxmax for dy (the f16x2 launch's input scale)."""
         o = self.ops
-        if self._fast:
+        if self._fast and self.rows16:
             return o.conv3x3_dgrad_f16x2(dy, self._u16[0][j, 1], self._u16[1][j, 1], dymax, self._flag, add=skip)
+        if self._trunk_conv(j) in self._gen:
+            return o.conv3x3_dgrad_f16x2_dense(dy, self._gen[self._trunk_conv(j)][1], dymax, self._flag, add=skip)
         w = self.p[self._trunk_conv(j) + "_weight"]
         if not self.rows16:
             return o.conv3x3_dgrad(dy, w, o.DENSE, add=skip)
@@ -347,6 +403,10 @@ class HipTrainer(object):
     def _forward(self, states, step):
         o, p = self.ops, self.p
         tape = {"blocks": [], "stack": []}
+        if self._fast and self._gen_names:     # the dense route's weights, both orientations, one launch (it zeroes the overflow word)
+            self._gen_out = o.conv15h_pack_many([(p[k + "_weight"], p[k + "_bias"]) for k in self._gen_names], self._gen_out,
+                                                self._flag)
+            self._gen = dict(zip(self._gen_names, self._gen_out))
         if self.kind == "resnet":
             S = self.frame_side
             x, tape["stem"] = self._conv_act_fwd(states, "res_conv1", o.DENSE, frame=bool(S))
@@ -471,6 +531,7 @@ class HipTrainer(object):
             self._backward(tape, out["dlogits"], out["dvlogit"])
         finally:
             self._fast = False
+            self._gen = {}
         self.tape = tape if keep_tape else None
         return out["loss3"]
 

@@ -177,6 +177,36 @@ int apz_conv3x3_fwd(apz_engine *e, const void *x_dev, const void *wpk_dev, const
 int apz_conv15h_fwd(apz_engine *e, const void *x_dev, const void *w_dev, const void *bias_dev,
                     const void *resid_dev, void *y_dev, int n, int cin, int cout, int relu,
                     void *flag_dev, void *stream);
+/* The training step of the generic 15x15 nets on the same kernel (HipTrainer(trunk_arith="f16x2") on nets without the
+ * padded-row trunk; csrc/conv15_split.h).  Dense tensors, C_in and C_out multiples of 64.
+ *   apz_conv15h_packed_size  floats of one orientation's packed weights of a cin -> cout layer (9 cin cout); beside them an
+ *                            orientation has bias8h = [its output channels: bias][as many: 1 / S] floats.
+ *   apz_conv15h_pack_many    one launch for the step's `count` layers, both orientations each.  table_host: `count` entries
+ *                            of struct apz_conv15h_pack_entry, 56 bytes each, read before the call returns.  Orientation 0 = the forward
+ *                            (bit for bit what apz_conv15h_fwd packs per call), orientation 1 = the data gradient
+ *                            (W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], bias zero); the per-channel scale S is taken over
+ *                            the orientation's own output channel.  flag_dev (NULL: none): a 32-bit word zeroed by the launch.
+ *   apz_conv15h_fwd_packed   y = conv(x) + bias (+ resid_dev; NULL: none), no ReLU, on orientation 0 of a packed layer; a
+ *                            non-finite sum sets *flag_dev = 1.
+ *   apz_conv15h_dgrad        dx [n][c_dx][15][15] = conv(dy [n][c_dy][15][15], W') (+ add_dev; NULL: none) on orientation 1
+ *                            of a packed layer (pk / bias8h of c_dy -> c_dx).  dymax_dev: dymax_count >= 1 partial maxima of
+ *                            |dy| (apz_bn_bwd_max's dxmax) -- the launch scales dy by 2^a with the maximum in [2^7, 2^8)
+ *                            before the fp16 split, as apz_wino3h_conv_dgrad does (NaN entries are ignored, a zero maximum
+ *                            gives a = 0); flag_dev as above, also set when an entry of dymax_dev is +inf. */
+typedef struct apz_conv15h_pack_entry {
+    const float *w;             /* [cout][cin][3][3] fp32, device */
+    const float *bias;          /* [cout], device; NULL: zero */
+    void *pk[2];                /* apz_conv15h_packed_size(cin, cout) floats each, device, 16-byte aligned */
+    float *bias8h[2];           /* [2 cout] and [2 cin] floats, device */
+    int cin, cout;
+} apz_conv15h_pack_entry;
+int64_t apz_conv15h_packed_size(int cin, int cout);
+int apz_conv15h_pack_many(apz_engine *e, const void *table_host, int count, void *flag_dev, void *stream);
+int apz_conv15h_fwd_packed(apz_engine *e, const void *x_dev, const void *pk_dev, const void *bias8h_dev,
+                           const void *resid_dev, void *y_dev, int n, int cin, int cout, void *flag_dev, void *stream);
+int apz_conv15h_dgrad(apz_engine *e, const void *dy_dev, const void *pk_dev, const void *bias8h_dev, const void *add_dev,
+                      void *dx_dev, int n, int c_dy, int c_dx, const void *dymax_dev, int dymax_count, void *flag_dev,
+                      void *stream);
 /* activation layouts of the training primitives: dense NCHW, or the trunk's padded rows [n][C][15][16]
  * (15x15 boards; pad column zero) in which the self-play kernels keep their activations */
 #define APZ_LAYOUT_DENSE 0
@@ -223,8 +253,8 @@ int apz_wino_conv_stats(apz_engine *e, const void *x_dev, const void *upk_dev, c
  *                          in [2^7, 2^8) before the fp16 split (-64 <= a <= 110: maxima down to 1e-31 reach that
  *                          window; NaN entries are ignored); flag_dev as above, also set when an entry of dymax_dev
  *                          is +inf.
- *   apz_bn_bwd_max         apz_bn_bwd (padded-row layout) + dxmax_dev [apz_bn_bwd_splits(n, C, layout)][C] floats: max |dx|
- *                          per batch split and channel.
+ *   apz_bn_bwd_max         apz_bn_bwd (padded rows, or dense 15x15 tensors) + dxmax_dev [apz_bn_bwd_splits(n, C, layout)][C] floats: max |dx|
+ *                          per batch split and channel (NULL: apz_bn_bwd's launches and bits).
  *   apz_adam_step_unless   apz_adam_step, skipped on the device when the 32-bit word at skip_dev is not zero. */
 int64_t apz_wino3h_packed_size(void);
 int apz_wino3h_pack_many(apz_engine *e, const void *w_dev, const void *b_dev, int count, void *upk_dev, void *bias_dev,
